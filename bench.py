@@ -24,6 +24,13 @@ dtype / config / roofline / cpu_baseline / parity + a `configs` map of six numbe
 ``--workload c4`` (BASELINE configs[3]) times the device-resident render of the jobs (`value`); the delivery of every job's samples
 into host arrays (bound by the host link) and the 256-job full-chip rate are sub-records.
 
+A plain run (``--gpus N --steps K --warmup W``) does only what the headline needs: set-up, W warm-up steps, the K timed steps
+(the roofline fields come from those steps' own launch events), the result lines. Everything measured or checked beyond that —
+the device-resident and latency legs, the CPU baselines and the parity checks against the reference engine, the other
+configurations (``configs``), and for ``--workload c4`` the host-delivered, 256-job and CPU legs with their parity check — runs
+only with ``--full``. ``--dump-outputs DIR`` writes what the timed path handed its caller in the LAST timed step as float32
+``DIR/<name>.npy`` (C2: the stereo bus; C4: a fixed seeded sample of the jobs), so that two builds can be compared output for output.
+
 Launch (N > 1):  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
                  --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -219,11 +226,14 @@ def c4_parity(timed_host, inst: int, first: int, total_blocks: int, tail: int = 
             "what": f"last {tail} blocks of the timed region of {len(picks)} render jobs vs reference engines advanced from time zero through all {total_blocks} blocks"}
 
 
-def _emit(full: dict) -> None:
+def _emit(full: dict, records: bool = True) -> None:
     """Every full record on a JSON line of its own, then ONE compact line (< 4 KB: benchmarks/headline.py) LAST — the line the
     driver parses. The full records also go to gpurun_out/bench_records.jsonl (scratch)."""
     sys.path.insert(0, os.path.join(ROOT, "benchmarks"))
     import headline
+    if not records:             # a plain run writes nothing beside its stdout
+        headline.emit(full)
+        return
     rpath = None
     try:
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
@@ -231,6 +241,27 @@ def _emit(full: dict) -> None:
     except OSError:
         pass
     headline.emit(full, records_path=rpath)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """`--dump-outputs DIR`: one float32 DIR/<name>.npy per array a caller of the timed path received in the last timed step."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte bound")
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+def _job_sample(n_jobs: int, k: int = 16):
+    """A fixed, seeded sample of render jobs (sorted indices) for `--dump-outputs` of `--workload c4`."""
+    import numpy as np
+    return np.sort(np.random.default_rng(20261015).choice(n_jobs, size=min(k, n_jobs), replace=False))
 
 
 def run_configs(names, timeout_s: float):
@@ -243,7 +274,7 @@ def run_configs(names, timeout_s: float):
     t_all = time.perf_counter()
     for name in names:
         if name == "c4":
-            cmd = [sys.executable, os.path.abspath(__file__), "--workload", "c4", "--steps", "64", "--warmup", "8"]
+            cmd = [sys.executable, os.path.abspath(__file__), "--workload", "c4", "--steps", "64", "--warmup", "8", "--full"]
         else:
             cmd = [sys.executable, os.path.join(ROOT, "benchmarks", "driver_configs.py"), name]
         t0 = time.perf_counter()
@@ -314,6 +345,7 @@ def main_c4(args) -> None:
     host_mode = world == 1 and args.host_delivered
     out = torch.zeros((spc * B, inst, BLOCK), dtype=torch.float32, device="cuda")
     gathered_elems = 0
+    last_gather = {}
 
     def run(steps: int, host_out=None) -> None:
         nonlocal gathered_elems
@@ -328,6 +360,7 @@ def main_c4(args) -> None:
                 g = gather_outputs(out[:c * B].transpose(0, 1).contiguous(), dst=0)
                 if g is not None:
                     gathered_elems += g.numel()
+                    last_gather["g"] = g
             done += c
 
     warm_host = np.empty((inst, max(1, args.warmup) * B * BLOCK), dtype=np.float32) if host_mode else None
@@ -353,7 +386,23 @@ def main_c4(args) -> None:
     if rank == 0:
         blocks = args.steps * B
         total_blocks = (args.warmup + args.steps) * B
-        if host_mode:
+        if args.dump_outputs:
+            # the last timed step as its caller received it, for a fixed seeded sample of the jobs
+            if host_mode:
+                jobs = _job_sample(inst)
+                last_step = timed_host[jobs, -B * BLOCK:]                                   # [job][frame]
+            elif world == 1:
+                jobs = _job_sample(inst)
+                s0 = ((args.steps - 1) % spc) * B
+                last_step = out[s0:s0 + B][:, torch.from_numpy(jobs).to(out.device)].cpu().numpy()    # [block][job][frame]
+            else:
+                g = last_gather["g"]                                                        # [job][block][frame], every rank's jobs
+                jobs = _job_sample(g.shape[0])
+                last_step = g[torch.from_numpy(jobs).to(g.device), -B:].cpu().numpy()
+            dump_outputs(args.dump_outputs, {"c4_jobs_last_step": last_step})
+        if not args.full:
+            parity = None
+        elif host_mode:
             parity = c4_parity(timed_host, inst, inst * rank, total_blocks)
         elif world == 1:
             # the last timed step is still in the device buffer [block][job][frame]: its last blocks, job by job, against reference engines
@@ -364,7 +413,7 @@ def main_c4(args) -> None:
         else:
             parity = None
         host_delivered = None
-        if world == 1 and not host_mode and not args.no_host_leg:
+        if args.full and world == 1 and not host_mode and not args.no_host_leg:
             hs = max(2, min(args.steps, 8))
             hbuf = np.zeros((inst, hs * B * BLOCK), dtype=np.float32)
             rt.process_blocks_host(None, inst, B * BLOCK, out=hbuf[:, :B * BLOCK])      # staging buffers, pages
@@ -377,7 +426,7 @@ def main_c4(args) -> None:
                               "mode": "elemhip_process_blocks_host: every job's samples delivered to the caller's planar host arrays (the host link is the bound)"}
             del hbuf
         full_chip = None
-        if world == 1 and args.full_chip and inst < 256 :
+        if args.full and world == 1 and args.full_chip and inst < 256 :
             # the half-empty chip is the configuration's choice (1024 jobs over 8 GPUs = 128 per GPU, one island per CU): the same jobs at one per CU
             try:
                 rt2 = Runtime(graphs.C4_SAMPLE_RATE, BLOCK, device=local)
@@ -399,7 +448,7 @@ def main_c4(args) -> None:
                 del rt2, out2
             except Exception as e:      # noqa: BLE001
                 full_chip = {"error": repr(e)[:200]}
-        base = None if args.no_cpu_baseline else c4_cpu_baseline(inst, inst * rank)
+        base = None if args.no_cpu_baseline or not args.full else c4_cpu_baseline(inst, inst * rank)
         traffic, traffic_src = None, None
         tpath = os.path.join(ROOT, "profiles", "traffic_c4.json")
         if os.path.exists(tpath):
@@ -440,7 +489,7 @@ def main_c4(args) -> None:
             "cpu_baseline": base, "speedup_vs_cpu_baseline": (world * inst * BLOCK * blocks / dt) / base["value"] if base else None,
             "speedup_vs_cpu_baseline_note": (f"GPU rate / the reference engine on ALL {base['cores']} host cores this process may use" if base else None),
             "parity": parity,
-        })
+        }, records=args.full)
     if world > 1:
         dist.destroy_process_group()
 
@@ -477,6 +526,11 @@ def main() -> None:
                     help="0: interpreter island kernels only; 2: per-island-shape kernels compiled at plan build (kcache/ on disk)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N > 1: weak = every rank renders --voices voices; strong = the --voices-voice graph is split over the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: device-resident and latency legs, CPU baselines and parity checks, "
+                         "the other configurations (c4: host-delivered, 256-job and CPU legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as float32 DIR/<name>.npy (<= 64 MB in all)")
     args = ap.parse_args()
     if args.workload == "c4":
         return main_c4(args)
@@ -555,6 +609,7 @@ def main() -> None:
                 pinned[:c * B].copy_(buf[:c * B], non_blocking=True)
             done += c
             k += 1
+            last_chunk["n"] = c * B
         for w, b_ in works:
             w.wait()
             if rank == 0:
@@ -594,6 +649,15 @@ def main() -> None:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        # the last timed step as its caller received it: the planar host arrays [2, frames] at N = 1, or rank 0's pinned copy of
+        # the (reduced) bus chunk [blocks, 2, frames] on the device-resident path
+        if host_mode:
+            last_step = timed_host[:, -B * BLOCK:]
+        else:
+            n = last_chunk["n"]
+            last_step = pinned[n - B:n].numpy()
+        dump_outputs(args.dump_outputs, {"c2_bus_last_step": last_step})
 
     if rank == 0:
         stats = rt.stats()
@@ -623,7 +687,7 @@ def main() -> None:
                 traffic = None
         # ---- the device-resident rate (no delivery), same engine, right after the timed region ----
         device_resident = None
-        if host_mode:
+        if host_mode and args.full:
             run_device(min(args.warmup, 2))
             torch.cuda.synchronize()
             t1 = time.perf_counter()
@@ -636,19 +700,21 @@ def main() -> None:
                                        "asynchronously to rank 0's pinned host memory (N > 1 adds the RCCL sum-reduce of the chunk to rank 0 in front of that copy). "
                                        "A 1 -> N curve is self-consistent when its N = 1 point is THIS figure; the headline `value` at N = 1 is the stricter "
                                        "delivery into the caller's planar host arrays (elemhip_process_blocks_host)"}
-        # ---- latency figures outside the timed region ----
-        rt.set_option("time_batch", 1)
-        lv1 = rt.time_launches(2, 100)
-        for _ in range(20):
-            rt.process(None, 2, BLOCK)
-        t1 = time.perf_counter()
-        for _ in range(200):
-            rt.process(None, 2, BLOCK)
-        sync_us = 1e6 * (time.perf_counter() - t1) / 200
+        # ---- latency figures outside the timed region (--full) ----
+        lv1, sync_us = [], None
+        if args.full:
+            rt.set_option("time_batch", 1)
+            lv1 = rt.time_launches(2, 100)
+            for _ in range(20):
+                rt.process(None, 2, BLOCK)
+            t1 = time.perf_counter()
+            for _ in range(200):
+                rt.process(None, 2, BLOCK)
+            sync_us = 1e6 * (time.perf_counter() - t1) / 200
         # the same call from a native host (examples/bench_cli: the reference's cli/Benchmark.cpp protocol, C++ over the C-ABI, no
         # Python between the calls), rank 0 only, outside the timed region
         sync_native = None
-        if rank == 0:
+        if rank == 0 and args.full:
             try:
                 sys.path.insert(0, os.path.join(ROOT, "benchmarks"))
                 import bench_configs as _bc
@@ -707,8 +773,8 @@ def main() -> None:
                                    "compile wait %.0f ms inside plan_build_ms (0 = on-disk cache hit)"
                                    % (stats["spec_shapes"], stats["spec_islands"], stats["spec_launches"], stats["last_jit_wait_ms"]))
                                   if args.specialize and stats["spec_launches"] else "ahead-of-time interpreter kernel",
-                "multi_gpu_note": "no 1 -> 8 GPU curve has been measured by the builder (single-GPU boxes only); N > 1 is covered by 2- and 8-process tests "
-                                  "(gloo on CPU, engines sharing one GPU). N > 1 lines deliver through device-resident render + RCCL reduce + copy to rank 0's "
+                "multi_gpu_note": "no 1 -> 8 GPU curve has been measured by the builder (single-GPU boxes only); N > 1 is covered by 2- and 8-process tests on CPU "
+                                  "(gloo), 2- and 3-process tests of engines sharing one GPU, and 8 ranks on 8 GPUs where a node has them. N > 1 lines deliver through device-resident render + RCCL reduce + copy to rank 0's "
                                   "pinned memory; the N = 1 line's `device_resident` sub-record is that same protocol at N = 1",
             },
             "us_per_block": us_per_block,
@@ -737,7 +803,7 @@ def main() -> None:
                         "inside an island live in LDS and never reach HBM, so traffic sits far below the algorithmic bytes",
             },
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             head_blocks = min(B, (args.warmup if args.warmup else args.steps) * B) if host_mode else 0
             cb = cpu_baseline(keep_blocks=head_blocks, voices=my_voices)
             if cb:
@@ -789,9 +855,9 @@ def main() -> None:
             out["parity_max_abs_err"] = err
             out["parity"] = {"tolerance": 1e-6, "ok": err <= 1e-6 * scale, "scale": scale,
                              "what": f"last {nb} blocks of the rank-0 reduced bus vs the reference engine rendering all {total_voices} voices"}
-        if world == 1 and not args.no_configs and my_voices == 256 and not args.device_resident:
+        if world == 1 and args.full and not args.no_configs and my_voices == 256 and not args.device_resident:
             out["configs"] = run_configs([c for c in args.configs.split(",") if c], args.config_timeout)
-        _emit(out)
+        _emit(out, records=args.full)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -56,3 +56,20 @@ def render_pair(make_a, make_b, roots_fn, sample_rate=44100.0, block=512, blocks
         outs_a.append(a.process(x, n_out, block))
         outs_b.append(b.process(x, n_out, block))
     return np.stack(outs_a), np.stack(outs_b)
+
+
+def render_one(make, roots_fn, sample_rate=44100.0, block=512, blocks=12, n_in=0, n_out=None, inputs=None, resources=None):
+    """render_pair for one engine: the same graph, resources and inputs; returns out [blocks, n_out, block]."""
+    rt = make(sample_rate, block)
+    for name, data in (resources or {}).items():
+        assert rt.add_shared_resource(name, data)
+    roots = roots_fn()
+    n_out = n_out if n_out is not None else len(roots)
+    assert rt.render(*roots)["result"] == 0
+    outs = []
+    for k in range(blocks):
+        x = None
+        if n_in:
+            x = inputs[k] if inputs is not None else np.stack([lcg_noise(block, 1 + c + 97 * k, 0.5) for c in range(n_in)])
+        outs.append(rt.process(x, n_out, block))
+    return np.stack(outs)

@@ -27,12 +27,12 @@ def _render(first, count):
     return np.stack([rt.process(None, 2, BS) for _ in range(BLOCKS)])
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, port, q, voices=VOICES):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from elementary_amd.sharded import gather_outputs, ordered_bus_sum, reduce_bus, shard_range
-    b, e = shard_range(VOICES, world, rank)
+    b, e = shard_range(voices, world, rank)
     bus = torch.from_numpy(_render(b, e - b))
     ordered = ordered_bus_sum(bus)
     per_unit = gather_outputs(torch.full((e - b, 3), float(rank)))
@@ -92,12 +92,12 @@ def _render_instances(first, count):
     return np.stack(outs)                                       # [instances, frames]
 
 
-def _c4_worker(rank, world, port, q):
+def _c4_worker(rank, world, port, q, instances=INSTANCES):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from elementary_amd.sharded import gather_outputs, shard_range
-    b, e = shard_range(INSTANCES, world, rank)
+    b, e = shard_range(instances, world, rank)
     gathered = gather_outputs(torch.from_numpy(_render_instances(b, e - b)))
     if rank == 0:
         q.put(gathered.numpy())
@@ -119,3 +119,37 @@ def test_two_rank_instance_gather_matches_single_engine():
     full = _render_instances(0, INSTANCES)
     assert gathered.shape == full.shape
     assert np.array_equal(gathered, full)        # instances are independent: sharding changes nothing, bit for bit
+
+
+def _run_ranks(target, world, extra):
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=target, args=(r, world, port, q) + extra) for r in range(world)]
+    for p in procs:
+        p.start()
+    got = q.get(timeout=240)
+    for p in procs:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    return got
+
+
+def test_eight_ranks_bus_exchange_and_instance_gather_match_single_engine():
+    """The rank count the driver launches (8): the voice shards' buses reduced (and summed in rank order) across eight ranks, and
+    the render jobs' outputs gathered from eight ranks, against one engine rendering everything — both workloads of the N > 1
+    path at its real world size, CPU checkers standing in for the per-GPU engines."""
+    from elementary_amd.sharded import shard_range
+    voices, instances = 16, 16
+    reduced, ordered, per_unit = _run_ranks(_worker, 8, (voices,))
+    parts = [_render(b, e - b) for b, e in (shard_range(voices, 8, r) for r in range(8))]
+    acc = parts[0].copy()
+    for part in parts[1:]:
+        acc += part                                               # float32, rank order
+    assert np.array_equal(ordered, acc)
+    assert np.allclose(reduced, acc, atol=1e-6)
+    assert np.abs(_render(0, voices) - ordered).max() <= 1e-6
+    assert per_unit.shape == (voices, 3) and np.array_equal(per_unit[:, 0], np.repeat(np.arange(8, dtype=np.float32), voices // 8))
+    gathered = _run_ranks(_c4_worker, 8, (instances,))
+    full = _render_instances(0, instances)
+    assert gathered.shape == full.shape and np.array_equal(gathered, full)

@@ -9,8 +9,8 @@ for step in "$@"; do
   echo "=== $step"
   case $kind in
     tests) timeout 1500 python -m pytest ${arg:-tests} -m gpu -x -q < /dev/null > $O/pytest_$(echo "$arg" | tr -c 'A-Za-z0-9\n' _ | cut -c1-40).log 2>&1; echo "pytest rc=$?"; tail -n 8 $O/pytest_*.log | cut -c1-400;;
-    bench) timeout 600 python bench.py ${arg:---steps 20 --warmup 5} < /dev/null > $O/bench.out 2> $O/bench.err; echo "rc=$?"; tail -n 1 $O/bench.out | wc -c; tail -n 1 $O/bench.out | cut -c1-3800;;
-    c4)    timeout 600 python bench.py --workload c4 $arg < /dev/null > $O/bench_c4.out 2> $O/bench_c4.err; echo "rc=$?"; tail -n 1 $O/bench_c4.out | cut -c1-2500;;
+    bench) timeout 600 python bench.py --full ${arg:---steps 20 --warmup 5} < /dev/null > $O/bench.out 2> $O/bench.err; echo "rc=$?"; tail -n 1 $O/bench.out | wc -c; tail -n 1 $O/bench.out | cut -c1-3800;;
+    c4)    timeout 600 python bench.py --workload c4 --full $arg < /dev/null > $O/bench_c4.out 2> $O/bench_c4.err; echo "rc=$?"; tail -n 1 $O/bench_c4.out | cut -c1-2500;;
     cfg)   timeout 400 python benchmarks/driver_configs.py $arg < /dev/null > $O/cfg_$(echo "$arg" | tr -c 'A-Za-z0-9\n' _).json 2> $O/cfg_$(echo "$arg" | tr -c 'A-Za-z0-9\n' _).err; echo "rc=$?"; tail -n 1 $O/cfg_$(echo "$arg" | tr -c 'A-Za-z0-9\n' _).json | cut -c1-3000;;
     prof)  timeout 1500 bash profiles/collect_r06.sh $TAG $arg < /dev/null 2>&1 | tail -n 40;;
     py)    timeout 900 python $arg < /dev/null > $O/py_$(echo "$arg" | tr -c 'A-Za-z0-9\n' _ | cut -c1-50).out 2>&1; echo "rc=$?"; tail -n 25 $O/py_$(echo "$arg" | tr -c 'A-Za-z0-9\n' _ | cut -c1-50).out | cut -c1-600;;
