@@ -771,7 +771,7 @@ size_t convolve_batch_scratch_floats(uint32_t maxBatch, uint32_t longHistRows) {
 // `anyShortPath`: some node of the level (or this set's size) still needs the 512-partition kernels.
 void launch_convolve_batch(hipStream_t s, const PlanView& pv, uint32_t* recs, float* hbm, const Globals* g, uint32_t workBegin,
                            uint32_t numNodes, uint32_t batch, uint32_t arenaFloats, float* scratch, uint32_t maxBatch, uint32_t macMode,
-                           bool anyShortIr, bool anyLongIr, uint32_t longHistRows, bool anyShortPath, uint32_t longStateBlocks, uint32_t longMacMode,
+                           bool anyShortIr, bool anyLongIr, uint32_t longHistRows, bool anyShortPath, uint32_t longStateBlocks,
                            const float* inDirect, uint32_t numInCh, float* outDirect, uint32_t numOutCh) {
     const dim3 grid(numNodes, batch), block(256);
     const size_t perNode = convolve_batch_scratch_floats(maxBatch, longHistRows);
@@ -796,14 +796,9 @@ void launch_convolve_batch(hipStream_t s, const PlanView& pv, uint32_t* recs, fl
     if (longSet) {
         const uint32_t chunks = batch / 8u;
         hipLaunchKernelGGL(elemhip_convolve_long_fft, dim3(numNodes, longHistRows + chunks), block, 0, s, pv, recs, hbm, g, workBegin, arenaFloats, scratch, maxBatch, batch, longHistRows, longMode, perNode, inDirect, numInCh);
-        // the partition sums: LDS-tiled (mode 1) while a tile's rows fit 64 KB of LDS (C3: 40 KB), else the register kernel over L2
-        const size_t macLds = long_mac_tile_lds_bytes(longHistRows + 1u);      // (Qp <= histRows + 1)
-        if (macLds <= 64u * 1024u && longMacMode == 1u)
-            hipLaunchKernelGGL(elemhip_convolve_long_mac_lds, dim3(numNodes, lfft::M / kTileBins, (chunks + kTileRun - 1u) / kTileRun), dim3(512), macLds, s, pv, recs, hbm, g, workBegin, arenaFloats, scratch, maxBatch, batch, longHistRows, longMode, perNode);
-        else if (longMacMode == 2u)      // (A/B: runs of 32 chunks per thread — every spectrum row is read by 1.7 workgroups instead of 2.4, at two waves per SIMD)
-        hipLaunchKernelGGL(elemhip_convolve_long_mac<32u>, dim3(numNodes, lfft::M / 256u, (chunks + 31u) / 32u), block, 0, s, pv, recs, hbm, g, workBegin, arenaFloats, scratch, maxBatch, batch, longHistRows, longMode, perNode, 0u);
-        else
-        hipLaunchKernelGGL(elemhip_convolve_long_mac<kLongRun>, dim3(numNodes, lfft::M / 256u, (chunks + kLongRun - 1u) / kLongRun), block, 0, s, pv, recs, hbm, g, workBegin, arenaFloats, scratch, maxBatch, batch, longHistRows, longMode, perNode, longMacMode == 3u ? 1u : 0u);
+        // the partition sums: the register kernel over L2 (an LDS-tiled form and runs of 32 chunks measured no faster:
+        // profiles/r06/c3_long_mac_variants.txt)
+        hipLaunchKernelGGL(elemhip_convolve_long_mac<kLongRun>, dim3(numNodes, lfft::M / 256u, (chunks + kLongRun - 1u) / kLongRun), block, 0, s, pv, recs, hbm, g, workBegin, arenaFloats, scratch, maxBatch, batch, longHistRows, longMode, perNode);
         hipLaunchKernelGGL(elemhip_convolve_long_ifft, dim3(numNodes, chunks), block, 0, s, pv, recs, hbm, g, workBegin, arenaFloats, scratch, maxBatch, batch, longHistRows, longMode, perNode, inDirect, numInCh, outDirect, numOutCh);
         (void)longStateBlocks;      // (the 512-partition state — spectra ring, overlap — is made on demand: launch_convolve_fix_overlap)
     }

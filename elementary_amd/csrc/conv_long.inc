@@ -170,8 +170,7 @@ void elemhip_convolve_long_fft(PlanView pv, uint32_t* recs, float* hbm, const Gl
 template <uint32_t RUN>
 __global__ __launch_bounds__(256, RUN <= 16u ? 4 : 2)
 void elemhip_convolve_long_mac(PlanView pv, uint32_t* recs, float* hbm, const Globals* g, uint32_t workBegin,
-                               uint32_t arenaFloats, float* scratchAll, uint32_t maxBatch, uint32_t batch, uint32_t histRows, uint32_t longMode, size_t perNode,
-                               uint32_t zigzag) {
+                               uint32_t arenaFloats, float* scratchAll, uint32_t maxBatch, uint32_t batch, uint32_t histRows, uint32_t longMode, size_t perNode) {
     const uint32_t convIdx = pv.convWork[workBegin + blockIdx.x] & 0xFFFFu, tid = threadIdx.x;
     const uint32_t k = blockIdx.y * 256u + tid, C0 = blockIdx.z * RUN, chunks = batch / 8u;
     const ConvDesc d = pv.convs[convIdx];
@@ -186,11 +185,13 @@ void elemhip_convolve_long_mac(PlanView pv, uint32_t* recs, float* hbm, const Gl
     c2 acc[RUN];
 #pragma unroll
     for (uint32_t i = 0; i < RUN; ++i) acc[i] = mk(0.0f, 0.0f);
-    // (A/B `zigzag`: odd runs walk the tap groups from the oldest to the newest, so that a run and its successor — which reads, for its
-    //  oldest taps, the very rows this one reads for its newest — ask the L2 for them at the same time)
-    const bool rev = zigzag != 0u && (blockIdx.z & 1u) != 0u;
+    // The two empty asm statements keep the schedule the loop had when its tap order was a run-time choice: l0 in an SGPR before
+    // the loop (else a wait for its scalar load sits in front of every conditional row load) and q0 opaque per group (else the
+    // strength-reduced addresses cost more registers). Without them C3's long MAC took 26.9 us per launch instead of 26.5.
+    asm volatile("" :: "s"(l0));
     for (uint32_t qi = 0; qi < ls.Qp; qi += kLongTaps) {
-        const uint32_t q0 = rev ? ls.Qp - kLongTaps - qi : qi;
+        uint32_t q0 = qi;
+        asm volatile("" : "+s"(q0));
         c2 gq[kLongTaps];
 #pragma unroll
         for (uint32_t t = 0; t < kLongTaps; ++t) gq[t] = Gk[(size_t)(q0 + t) * kRow];
@@ -229,86 +230,6 @@ void elemhip_convolve_long_mac(PlanView pv, uint32_t* recs, float* hbm, const Gl
             a1.x = fmaf(h1.x, x1.x, a1.x); a1.x = fmaf(-h1.y, x1.y, a1.x); a1.y = fmaf(h1.x, x1.y, a1.y); a1.y = fmaf(h1.y, x1.x, a1.y);
         }
         l.Y[(size_t)(C0 + tid) * kRow + lfft::M] = mk(a0.x + a1.x, a0.y + a1.y);
-    }
-}
-
-// K2, LDS-tiled (`conv_long_mac_lds` = 1): (node, 64-bin tile, run of 32 chunks), 512 threads. The register kernel above asks the L2s
-// for 195 MB per C3 launch (every workgroup its own 31 rows per tap group) and runs at their bandwidth (four re-read experiments on the
-// HBM side moved nothing: profiles/r06/c3_long_mac_variants.txt). Here a workgroup brings the Qp - 1 + 32 spectrum rows and the Qp IR
-// rows of its 64 bins into LDS ONCE (C3: 79 rows x 512 B = 40 KB; 82 MB per launch in all) and its eight waves take four chunks each:
-// per tap group of 8 a lane reads 8 IR values and an 11-row window from LDS for 32 complex multiply-adds. Three workgroups per CU, so
-// one workgroup's load phase runs under the others' arithmetic (r05's tiled kernel — 32 bins x ALL chunks, one run per lane group —
-// had a 45 KB load phase in front of every workgroup's arithmetic and measured slower).
-// Same summation order per (bin, chunk) as the register kernel: the two produce identical bits.
-constexpr uint32_t kTileBins = 64, kTileRun = 32, kTileWaveChunks = 4;
-__host__ __device__ __forceinline__ size_t long_mac_tile_lds_bytes(uint32_t Qp) { return (size_t)(2u * Qp - 1u + kTileRun) * kTileBins * sizeof(c2); }
-__global__ __launch_bounds__(512)
-void elemhip_convolve_long_mac_lds(PlanView pv, uint32_t* recs, float* hbm, const Globals* g, uint32_t workBegin,
-                                   uint32_t arenaFloats, float* scratchAll, uint32_t maxBatch, uint32_t batch, uint32_t histRows, uint32_t longMode, size_t perNode) {
-    extern __shared__ __attribute__((aligned(16))) char longLds[];
-    const uint32_t convIdx = pv.convWork[workBegin + blockIdx.x] & 0xFFFFu, tid = threadIdx.x;
-    const uint32_t k0 = blockIdx.y * kTileBins, C0 = blockIdx.z * kTileRun, chunks = batch / 8u;
-    const ConvDesc d = pv.convs[convIdx];
-    if (!root_running((gcup)recs, d.rootRec, g->numOut)) return;
-    BatchCtx c;
-    if (!batch_ctx(d, (gup)recs, g, scratchAll, convIdx, maxBatch, c, perNode) || !conv_use_long(c.st, batch, longMode)) return;
-    if (C0 >= chunks) return;
-    const LongState ls = long_state_of(c.st);
-    const LongCtx l = long_ctx(c, maxBatch, histRows);
-    const uint32_t l0 = ((gcup)c.scratch)[LH_L0], Qp = ls.Qp;
-    const uint32_t rowsU = Qp - 1u + kTileRun, logical0 = histRows + C0 - (Qp - 1u);      // LDS row r = logical row logical0 + r (>= 0: histRows >= Qp - 1)
-    c2 (*Us)[kTileBins] = reinterpret_cast<c2 (*)[kTileBins]>(longLds);
-    c2 (*Gs)[kTileBins] = reinterpret_cast<c2 (*)[kTileBins]>(longLds + (size_t)rowsU * kTileBins * sizeof(c2));
-    {   // 8 rows x 64 bins per pass: 512-byte pieces of consecutive rows; rows behind the set's last chunk feed accumulators that are never stored
-        const uint32_t bin = tid & (kTileBins - 1u), r0 = tid / kTileBins;
-        gcf2p Ub = (gcf2p)l.U + k0 + bin;
-        gcf2p Gb = ls.G + k0 + bin;
-        for (uint32_t r = r0; r < rowsU; r += 512u / kTileBins) {
-            const uint32_t lg = logical0 + r;
-            Us[r][bin] = lg < histRows + chunks ? Ub[(size_t)long_phys(l0, lg, l.Ru) * kRow] : mk(0.0f, 0.0f);
-        }
-        for (uint32_t q = r0; q < Qp; q += 512u / kTileBins) Gs[q][bin] = Gb[(size_t)q * kRow];
-    }
-    __syncthreads();
-    const uint32_t lane = tid & 63u, c0 = (tid >> 6) * kTileWaveChunks;
-    if (C0 + c0 >= chunks) return;
-    c2 acc[kTileWaveChunks];
-#pragma unroll
-    for (uint32_t i = 0; i < kTileWaveChunks; ++i) acc[i] = mk(0.0f, 0.0f);
-    for (uint32_t q0 = 0; q0 < Qp; q0 += kLongTaps) {
-        c2 gq[kLongTaps];
-#pragma unroll
-        for (uint32_t t = 0; t < kLongTaps; ++t) gq[t] = Gs[q0 + t][lane];
-        // LDS row of (chunk c0 + i, tap q0 + t): (Qp - 1) + c0 + i - q0 - t = rb + dd, dd = i - t + kLongTaps - 1
-        const uint32_t rb = Qp - 1u + c0 - q0 - (kLongTaps - 1u);          // >= 0: q0 <= Qp - kLongTaps
-#pragma unroll
-        for (uint32_t dd = 0; dd < kTileWaveChunks + kLongTaps - 1u; ++dd) {
-            const c2 x = Us[rb + dd][lane];
-#pragma unroll
-            for (uint32_t t = 0; t < kLongTaps; ++t) {
-                const int i = (int)dd + (int)t - (int)(kLongTaps - 1u);
-                if (i >= 0 && i < (int)kTileWaveChunks) {
-                    const c2 h = gq[t];
-                    acc[i].x = fmaf(h.x, x.x, acc[i].x); acc[i].x = fmaf(-h.y, x.y, acc[i].x);
-                    acc[i].y = fmaf(h.x, x.y, acc[i].y); acc[i].y = fmaf(h.y, x.x, acc[i].y);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < kTileWaveChunks; ++i) if (C0 + c0 + i < chunks) l.Y[(size_t)(C0 + c0 + i) * kRow + k0 + lane] = acc[i];
-    // bin 4096: the first kTileWaveChunks lanes of tile 0's waves, one chunk each, straight from the rows in memory (as the register kernel's tail)
-    if (blockIdx.y == 0u && lane < kTileWaveChunks && C0 + c0 + lane < chunks) {
-        gcf2p Un = (gcf2p)l.U + lfft::M, Gn = ls.G + lfft::M;
-        const uint32_t top = histRows + C0 + c0 + lane;
-        c2 a0 = mk(0.0f, 0.0f), a1 = mk(0.0f, 0.0f);
-        for (uint32_t q = 0; q < Qp; q += 2u) {
-            const c2 h0 = Gn[(size_t)q * kRow], h1 = Gn[(size_t)(q + 1u) * kRow];
-            const c2 x0 = Un[(size_t)long_phys(l0, top - q, l.Ru) * kRow], x1 = Un[(size_t)long_phys(l0, top - q - 1u, l.Ru) * kRow];
-            a0.x = fmaf(h0.x, x0.x, a0.x); a0.x = fmaf(-h0.y, x0.y, a0.x); a0.y = fmaf(h0.x, x0.y, a0.y); a0.y = fmaf(h0.y, x0.x, a0.y);
-            a1.x = fmaf(h1.x, x1.x, a1.x); a1.x = fmaf(-h1.y, x1.y, a1.x); a1.y = fmaf(h1.x, x1.y, a1.y); a1.y = fmaf(h1.y, x1.x, a1.y);
-        }
-        l.Y[(size_t)(C0 + c0 + lane) * kRow + lfft::M] = mk(a0.x + a1.x, a0.y + a1.y);
     }
 }
 

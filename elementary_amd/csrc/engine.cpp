@@ -91,7 +91,6 @@ ProgHeap::~ProgHeap() { if (dev) (void)hipFree(dev); }
 
 Plan::~Plan() {
     if (graphExec) (void)hipGraphExecDestroy(graphExec);
-    if (specGraphExec) (void)hipGraphExecDestroy(specGraphExec);
     if (dev.ptr) { if (pool) pool->give(dev); else (void)hipFree(dev.ptr); }
 }
 
@@ -136,7 +135,6 @@ Engine::Engine(double sr, int bs, int dev) : sampleRate(sr), blockSize(bs), devi
     }
     if (const char* e = std::getenv("ELEMHIP_SPECIALIZE")) specialize = std::max(0, std::min(2, std::atoi(e)));
     if (const char* e = std::getenv("ELEMHIP_SYNC_POLL")) syncPoll = std::atoi(e) != 0;
-    if (const char* e = std::getenv("ELEMHIP_FUSE_EPILOGUE")) fuseEpilogue = std::atoi(e) != 0;   // (a native host without access to the options)
     if (const char* e = std::getenv("ELEMHIP_RESIDENT")) residentOpt = std::atoi(e) != 0;   // (a native host without access to the options)
     if (const char* e = std::getenv("ELEMHIP_PLAN_CACHE")) planCache = std::max(0, std::min(2, std::atoi(e)));   // 2: verify mode (tests)
     if (bs <= 0 || bs > (int)kMaxBlock) { fail(kBlockTooLarge); return; }
@@ -272,7 +270,6 @@ void Engine::setStream(hipStream_t s) {
 void Engine::dropGraphs() {
     if (!current) return;
     if (current->graphExec) { (void)hipGraphExecDestroy(current->graphExec); current->graphExec = nullptr; }
-    if (current->specGraphExec) { (void)hipGraphExecDestroy(current->specGraphExec); current->specGraphExec = nullptr; }
 }
 
 void Engine::freeDeferred() {   // called right after a synchronize of every stream the engine renders on (`mu` held)
@@ -299,13 +296,12 @@ int Engine::ensureHbm(size_t buffers) {
 // Arena buffers a launch set of `blocks` blocks of plan `p` needs: one slice (host inputs + exports) per block, then the
 // stream ring of the specialised kernels, one slice per buffer set an island may keep in flight.
 size_t Engine::arenaBuffers(const Plan& p, size_t blocks) const {
-    return (size_t)p.numHbmBuffers * blocks + (size_t)p.numStreamBuffers * (streamRing ? (size_t)p.maxCopies : blocks);
+    return (size_t)p.numHbmBuffers * blocks + (size_t)p.numStreamBuffers * (size_t)p.maxCopies;
 }
 // The recurrence loops of the specialised kernels address the whole arena through 32-bit buffer offsets with the top bit
 // reserved as "out of range": a launch set stays under 2 GB of arena (C2: 0.6 MB per block).
 size_t Engine::maxSetBlocks(const Plan& p) const {
     const size_t cap = ((size_t)1 << 29) / (size_t)blockSize;                       // buffers of blockSize floats in 2 GB
-    if (!streamRing) return std::max<size_t>(1, (cap - 2) / std::max<uint32_t>(1u, p.numHbmBuffers + p.numStreamBuffers));
     const size_t ring = (size_t)p.numStreamBuffers * p.maxCopies + 2;
     return cap > ring ? std::max<size_t>(1, (cap - ring) / std::max<uint32_t>(1u, p.numHbmBuffers)) : 1;
 }
@@ -1613,34 +1609,23 @@ int Engine::setOption(const std::string& key, double value) {
     if (key == "resident_after") { residentAfter = (uint32_t)std::max(1.0, std::min(1e6, value)); return kOk; }
     if (key == "host_out_direct") { hostOutDirect = value != 0; return kOk; }   // elemhip_process: epilogue writes the pinned host block itself
     if (key == "conv_direct_io") { convDirectIo = value != 0; return kOk; }
-    if (key == "conv_long_mac_lds") { convLongMacMode = (uint32_t)std::max(0.0, std::min(3.0, value)); return kOk; }   // long-partition sums: 0 the register kernel over L2 (runs of 16 chunks), 1 the LDS-tiled kernel, 2 the register kernel with runs of 32 chunks
     if (key == "conv_long") { convLong = value != 0; return kOk; }   // IRs set from now on get (or do not get) long-partition spectra; sets of older IRs keep theirs
     if (key == "conv_mfma") { convMfma = std::max(0, std::min(1, (int)value)); return kOk; }   // partition MAC of launch sets: 1 matrix cores (default), 0 packed vector FMAs
     if (key == "skip_idle_launches") { skipIdleLaunches = value != 0; dropGraphs(); return kOk; }
-    if (key == "fuse_epilogue") { fuseEpilogue = value != 0; dropGraphs(); return kOk; }
-    if (key == "spec_block_graph") { specBlockGraph = value != 0; dropGraphs(); return kOk; }   // elemhip_process: replay the launch set of one from a hipGraph
     if (key == "spec_blocks") { specBlocks = value != 0; return kOk; }      // elemhip_process through the specialised kernels when it can
     if (key == "batch_blocks") { batchBlocks = std::max(1, std::min(1024, (int)value)); return kOk; }      // blocks per multi-block launch (1 = off)
     if (key == "debug_build_delay_ms") { debugBuildDelayMs = std::max(0, (int)value); return kOk; }   // tests: stretches the unlocked part of a plan build
     if (key == "plan_cache") { planCache = std::max(0, std::min(2, (int)value)); islandCache.clear(); islandShapeCache.clear(); return kOk; }
     if (key == "plan_relocate") { relocatePrograms = value != 0; islandShapeCache.clear(); return kOk; }   // programs of structural twins renamed instead of scheduled again
     if (key == "fuse_svf_coef") { fuseSvfCoef = (uint32_t)std::max(0, std::min(2, (int)value)); planStale = true; return kOk; }
-    if (key == "solo_waves") { soloWaves = (uint32_t)std::max(0, std::min(3, (int)value)); planStale = true; return kOk; }
     if (key == "mixer_split") { const int v = (int)value; mixerSplit = (v == 2 || v == 4 || v == 8) ? (uint32_t)v : 1u; planStale = true; return kOk; }
     if (key == "stateless_rows") { statelessRows = (uint32_t)std::max(1, std::min(64, (int)value)); return kOk; }   // gridDim.y of a multi-block launch: blocks that stateless islands render side by side
-    if (key == "spec_waves_per_eu") { specWavesPerEu = std::max(0, std::min(8, (int)value)); specTextCache.clear(); islandCache.clear(); islandShapeCache.clear(); planStale = true; return kOk; }
     if (key == "pipeline_copies") { pipelineCopies = std::max(1, std::min(6, (int)value)); planStale = true; return kOk; }   // next commit re-plans
-#ifdef ELEMHIP_EXPERIMENTAL
-    if (key == "stream_ring") { streamRing = value != 0.0; return kOk; }   // 0: measurement only, needs kernels built with ELEMHIP_STREAM_PER_BLOCK
-#else
-    if (key == "stream_ring") return value != 0.0 ? kOk : kInvalidPropertyValue;   // (the per-block stream slices exist in EXPERIMENTAL builds only)
-#endif
     if (key == "pack_islands") { packIslands = std::max(0, std::min(16, (int)value)); planStale = true; return kOk; }   // next commit re-plans
     if (key == "prog_heap_dwords") { progHeapCap = (size_t)std::max(0.0, value); progHeap.reset(); islandCache.clear(); planStale = true; return kOk; }   // 0: sized by the engine
     if (key == "pack_roots") { packRoots = value != 0; planStale = true; return kOk; }   // islands of different active roots may share a workgroup (C4: a root per render job)
     if (key == "pack_max") { packMax = std::max(1, std::min(16, (int)value)); planStale = true; return kOk; }
     if (key == "cu_count") { cuCount = std::max(1, (int)value); planStale = true; return kOk; }      // (dry handles / tests: the CU count the auto mode plans for)
-    if (key == "chain_lds_out") { chainLdsOut = value != 0.0; planStale = true; return kOk; }
     if (key == "merge_phases") { mergePhases = value != 0.0; planStale = true; return kOk; }   // next commit re-plans
     if (key == "specialize") { specialize = std::max(0, std::min(2, (int)value)); planStale = true; return kOk; }   // next commit re-plans
     if (key == "profile_launches") {
@@ -1654,9 +1639,6 @@ int Engine::setOption(const std::string& key, double value) {
     if (key == "max_shape_launches") { maxShapeLaunches = std::max(1, std::min(64, (int)value)); dropGraphs(); return kOk; }
     if (key == "spec_lonely_blocks") { lonelyBlocks = std::max(0, (int)value); return kOk; }   // background mode: a one-off shape is queued for compilation once its
     if (key == "spec_lonely_ms") { lonelyMs = std::max(0, (int)value); return kOk; }           // plan has rendered this many blocks and been current this long
-    // run-time compiler tunings (PROCESS-wide; bit-identical samples by construction, island_ops.inc): later plans compile with them
-    if (key == "biquad_form") { if (!Jit::get().setTuning("ELEMHIP_BIQUAD_FORM", (int)value)) return kInvalidPropertyValue; specTextCache.clear(); islandCache.clear(); islandShapeCache.clear(); planStale = true; return kOk; }
-    if (key == "wide_chain_depth") { if (!Jit::get().setTuning("ELEMHIP_WIDE_CHAIN_DEPTH", (int)value)) return kInvalidPropertyValue; specTextCache.clear(); islandCache.clear(); islandShapeCache.clear(); planStale = true; return kOk; }
     if (key == "jit_cache_entries") { Jit::get().setEntryCap((uint32_t)std::max(0.0, value)); return kOk; }   // PROCESS-wide: compiled shapes kept in memory (0: default 256)
     if (key == "time_batch") { timeBatch = std::max(1, std::min(256, (int)value)); return kOk; }
     if (key == "graph_blocks") { graphBlocks = std::max(1, (int)value); dropGraphs(); return kOk; }
@@ -1977,11 +1959,10 @@ int Engine::processSliceLocked(const float* const* in, size_t nIn, float* const*
         }
         outDev = hostOutDirect ? hOutDev : nullptr;
     }
-    // the call ends when the epilogue's word arrives (sync_poll): only when the epilogue writes the host's block itself, nothing is
-    // being profiled and no hipGraph replays the launches (a captured launch would publish a stale value)
-    const bool graphPath = specBlock && specBlockGraph && useGraph && !profileLaunches && !debugSyncOn();
+    // the call ends when the epilogue's word arrives (sync_poll): only when the epilogue writes the host's block itself and nothing is
+    // being profiled
     flagArmed = false; armFlag = nullptr;
-    if (syncPoll && outDev && !graphPath && !profileLaunches && !debugSyncOn() && p.hosts.empty()) {
+    if (syncPoll && outDev && !profileLaunches && !debugSyncOn() && p.hosts.empty()) {
         if (!hDone) {
             HIP_OK(hipHostMalloc((void**)&hDone, 64, hipHostMallocMapped | hipHostMallocCoherent));
             *hDone = 0;
@@ -1989,26 +1970,7 @@ int Engine::processSliceLocked(const float* const* in, size_t nIn, float* const*
         }
         armFlag = dDone; armValue = ++doneSeq;
     }
-    if (specBlock && specBlockGraph && useGraph && !profileLaunches && !debugSyncOn()) {
-        // the launch set of one (level launches, side-stream forks and joins, batch epilogue) replayed from a captured graph
-        float* const target = outDev ? outDev : dOutRing;
-        if (!p.specGraphExec || p.specGraphOut != target || p.specGraphNumOut != (uint32_t)nOut) {   // (which launches are left out depends on the output count)
-            if (p.specGraphExec) { (void)hipGraphExecDestroy(p.specGraphExec); p.specGraphExec = nullptr; }
-            hipGraph_t graph = nullptr;
-            HIP_OK(hipStreamSynchronize(stream));
-            const uint64_t before = st.specLaunches;
-            HIP_OK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-            enqueueBatch(p, 1u, outDev);
-            HIP_OK(hipStreamEndCapture(stream, &graph));
-            HIP_OK(hipGraphInstantiate(&p.specGraphExec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
-            p.specGraphOut = target; p.specGraphNumOut = (uint32_t)nOut; p.specGraphLaunches = (uint32_t)(st.specLaunches - before);
-            st.specLaunches = before;
-            st.graphCaptures++;
-        }
-        HIP_OK(hipGraphLaunch(p.specGraphExec, stream));
-        st.specLaunches += p.specGraphLaunches; st.graphReplays++;
-    } else if (specBlock) enqueueBatch(p, 1u, outDev);
+    if (specBlock) enqueueBatch(p, 1u, outDev);
     else if (specFade) enqueueSpecBlock(p, outDev);
     else { fixConvOverlaps(p); enqueueBlock(p, outDev); }
     if (nOut > 0 && !outDev) HIP_OK(hipMemcpyAsync(hOut, dOutRing, nOut * (size_t)blockSize * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -2365,9 +2327,9 @@ int Engine::launchProfile(double* msOut, size_t cap, uint64_t* launchSets, uint6
 // One launch level of a multi-block launch. When every island shape of the level has its specialised kernel compiled
 // (jit.cpp) the level runs as one launch per shape plus an interpreter launch for the islands no shape covers
 // (stateless mixers and roots); until then the whole level goes through the interpreter kernel.
-bool Engine::launchLevelBatch(const Plan& p, size_t l, uint32_t batch, uint32_t arenaFloats, float* epiOut) {
+void Engine::launchLevelBatch(const Plan& p, size_t l, uint32_t batch, uint32_t arenaFloats) {
     const uint32_t b = p.levelOffsets[l], e = p.levelOffsets[l + 1];
-    if (e <= b) return false;
+    if (e <= b) return;
     bool spec = specialize != 0 && !p.shapes.empty();
     std::vector<std::pair<hipFunction_t, const Plan::SpecShape*>> fns;   // function null: the shape is not compiled (yet)
     struct InterpRun { uint32_t begin, count; };                          // contiguous stretches of specLists the interpreter kernel renders
@@ -2393,16 +2355,15 @@ bool Engine::launchLevelBatch(const Plan& p, size_t l, uint32_t batch, uint32_t 
         }
         if (!any) spec = false;
     }
-    if (!spec) { launch_level(stream, p.view, dRecs, dHbm, dGlobals, dLcg, b, e - b, p.levelLdsBytes[l], batch, arenaFloats, statelessRows); islandBlocksInterp += (uint64_t)(e - b) * batch; debugSync("set: interpreter level", (unsigned)l, batch); return false; }
+    if (!spec) { launch_level(stream, p.view, dRecs, dHbm, dGlobals, dLcg, b, e - b, p.levelLdsBytes[l], batch, arenaFloats, statelessRows); islandBlocksInterp += (uint64_t)(e - b) * batch; debugSync("set: interpreter level", (unsigned)l, batch); return; }
     // The launches of one level are independent of each other (different islands): with more than one they go to side
     // streams forked from / joined to the engine's stream, so two shapes of 64 islands each fill 128 CUs at once
     // instead of 64 CUs twice.
     uint32_t rb = p.restOffsets[l], re = p.restOffsets[l + 1];
     if (re > rb && skipIdleLaunches && l < p.restRoots.size() && !anyRootRuns(p.restRoots[l], hGlobals.numOut)) { re = rb; st.idleLaunchesSkipped++; }
     const size_t launches = fns.size() + interpRuns.size() + (re > rb ? 1 : 0);
-    if (launches == 0) return false;
+    if (launches == 0) return;
     const bool fork = launches > 1;
-    const bool fused = epiOut != nullptr && batch == 1u && launches == 1 && fns.size() == 1 && fns[0].first != nullptr;
     if (fork) {
         while (auxStreams.size() < launches - 1) {
             hipStream_t s2 = nullptr; hipEvent_t ev = nullptr;
@@ -2440,11 +2401,7 @@ bool Engine::launchLevelBatch(const Plan& p, size_t l, uint32_t batch, uint32_t 
         const uint32_t* list = p.dSpecLists + f.second->listBegin;
         // the stream ring sits behind the `batch` block slices of this launch set
         uint32_t bt = batch, af = arenaFloats, sb = batch * arenaFloats, ss = p.numStreamBuffers * (uint32_t)blockSize;
-        uint32_t eg = fused ? f.second->count : 0u;
-        float* eo = fused ? epiOut : nullptr;
-        uint32_t* ef = (fused && armFlag) ? armFlag : nullptr;      // the fused tail publishes elemhip_process' completion word itself
-        uint32_t ev = armValue;
-        void* args[] = {&pv, &recs, &hbm, &g, &lcg, &list, &bt, &af, &sb, &ss, &eg, &eo, &ef, &ev};
+        void* args[] = {&pv, &recs, &hbm, &g, &lcg, &list, &bt, &af, &sb, &ss};
         const uint32_t gy = f.second->stateless ? std::max(1u, std::min(batch, statelessRows)) : 1u;
         HIP_WARN(hipModuleLaunchKernel(f.first, f.second->count, gy, 1, kThreads, 1, 1, 0, st_, args, nullptr));
         st.specLaunches++;
@@ -2464,7 +2421,6 @@ bool Engine::launchLevelBatch(const Plan& p, size_t l, uint32_t batch, uint32_t 
             HIP_WARN(hipStreamWaitEvent(stream, auxDone[i - 1], 0));
         }
     }
-    return fused;
 }
 
 // the convolve nodes of level l over a whole launch set: four launches (fft, mac, ifft, finish: conv.hip, "multi-block launches")
@@ -2500,7 +2456,7 @@ void Engine::launchConvolveBatch(const Plan& p, size_t l, uint32_t batch, uint32
     }
     if (!longSet) fixConvOverlaps(p);
     launch_convolve_batch(stream, p.view, dRecs, dHbm, dGlobals, cb, mains, batch, arenaFloats, dConvScratch, (uint32_t)batchBlocks, (uint32_t)convMfma,
-                          convMinP <= convolve_mfma_max_partitions(), convMaxP > convolve_mfma_max_partitions(), longRows, anyShortPath, stateBlocks, convLongMacMode,
+                          convMinP <= convolve_mfma_max_partitions(), convMaxP > convolve_mfma_max_partitions(), longRows, anyShortPath, stateBlocks,
                           longSet ? setInDirect : nullptr, setNumIn, longSet ? setOutDirect : nullptr, setNumOut);
 }
 
@@ -2547,14 +2503,11 @@ void Engine::enqueueBatch(const Plan& p, uint32_t batch, float* outRing) {
     const uint32_t arenaFloats = p.numHbmBuffers * (uint32_t)blockSize;
     const size_t L = p.levelOffsets.size() - 1;
     const bool prof = profileLaunches && (profSetCounter++ % profileEvery) == 0u;
-    // a launch set of ONE block (elemhip_process): the last level's kernel ends with the epilogue when it can (spec_epilogue_tail)
-    const bool mayFuse = fuseEpilogue && batch == 1u && L > 0 && p.convs.empty() && p.taps.empty() && p.roots.size() <= 32 && !debugSyncOn();
-    bool fused = false;
     for (size_t l = 0; l < L; ++l) {
         const uint32_t b = p.levelOffsets[l], e = p.levelOffsets[l + 1];
         if (e <= b && p.convLevelOffsets[l + 1] <= p.convLevelOffsets[l]) continue;
         if (prof) (void)hipEventRecord(profEvent(), stream);
-        fused = launchLevelBatch(p, l, batch, arenaFloats, (mayFuse && l + 1 == L) ? outRing : nullptr);
+        launchLevelBatch(p, l, batch, arenaFloats);
         launchConvolveBatch(p, l, batch, arenaFloats);
         if (prof) { (void)hipEventRecord(profEvent(), stream); profSlots.push_back((uint32_t)l); }
     }
@@ -2566,10 +2519,10 @@ void Engine::enqueueBatch(const Plan& p, uint32_t batch, float* outRing) {
         //  reader of the clock, and a patch launch per set was 4 us of kernel plus its launch gap in front of every 70 us of work:
         //  flushPending brings the device's clock up to the host's before the first launch that is not another direct set)
         deviceClockBehind = true;
-    } else if (!fused) {
+    } else {
         launch_epilogue_batch(stream, p.view, dRecs, dHbm, dGlobals, outRing, batch, arenaFloats, armFlag, armValue);
         if (armFlag && batch == 1u) flagArmed = true;
-    } else { st.fusedEpilogues++; if (armFlag && batch == 1u) flagArmed = true; }
+    }
     debugSync("set: epilogue", batch);
     if (prof && !setOutDirect) { (void)hipEventRecord(profEvent(), stream); profSlots.push_back((uint32_t)L); }
     if (prof) { profSets++; profBlocks += batch; if (profMs.size() <= L) profMs.resize(L + 1, 0.0); }     // (slot L = the epilogue, 0 for direct sets)
@@ -2581,7 +2534,7 @@ void Engine::enqueueSpecBlock(const Plan& p, float* outRing) {
     if (!outRing) outRing = dOutRing;
     const uint32_t arenaFloats = p.numHbmBuffers * (uint32_t)blockSize;
     const size_t L = p.levelOffsets.size() - 1;
-    for (size_t l = 0; l < L; ++l) (void)launchLevelBatch(p, l, 1u, arenaFloats);
+    for (size_t l = 0; l < L; ++l) launchLevelBatch(p, l, 1u, arenaFloats);
     launch_epilogue(stream, p.view, dRecs, dHbm, dGlobals, outRing, armFlag, armValue);
     if (armFlag) flagArmed = true;
     debugSync("block: specialised levels + epilogue");

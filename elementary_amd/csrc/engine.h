@@ -157,7 +157,6 @@ struct Stats {
     uint64_t graphReplays = 0, graphCaptures = 0, batchLaunches = 0;
     uint64_t specFadeBlocks = 0;         // blocks rendered by the specialised kernels while root fades were running (per-block epilogue)
     uint64_t idleLaunchesSkipped = 0;    // launches left out because no root of their islands ran
-    uint64_t fusedEpilogues = 0;         // launch sets of one whose last level kernel ran the epilogue
     uint64_t progHeaps = 0;              // program heaps started (1 = the first still serves)
     uint64_t planIslandsReused = 0, planIslandsScheduled = 0, planCacheMismatches = 0;   // island program cache (plan.cpp)
     uint64_t planIslandsRelocated = 0, planRelocationMismatches = 0;                      // ... programs taken from a structural twin
@@ -360,7 +359,6 @@ private:
     uint64_t convScratchKey = ~0ull;       // (batch_blocks, long history rows) the scratch headers were zeroed for
     std::set<int32_t> convStaleNodes;      // convolve nodes last rendered by a long-partition set: their `overlap` is made on demand (fixConvOverlaps), per node
     void fixConvOverlaps(const Plan& p);   // ... before the next 512-partition evaluation (block-at-a-time launches, sets that are no multiple of 8 blocks)
-    uint32_t convLongMacMode = 0;          // option "conv_long_mac_lds": 0 the register kernel (ships), 1 the LDS-tiled kernel (r06: 64 bins x 32 chunks; as fast, a third of the L2 traffic), 2 runs of 32, 3 zigzag
     bool convDirectIo = true;              // option "conv_direct_io": a plan of long-partition convolvers only reads the caller's input / writes the caller's output in place
     // the launch set being enqueued (enqueueBlocks -> enqueueBatch -> launchConvolveBatch): where its convolvers read / write directly
     const float* setInDirect = nullptr; float* setOutDirect = nullptr; uint32_t setNumIn = 0, setNumOut = 0;
@@ -370,24 +368,17 @@ private:
     uint32_t convMaxQp = 0;                // most long-partition tap rows of any impulse response set so far (sizes the scratch)
     int convMfma = 1;                      // conv.hip elemhip_convolve_batch_mac: 1 v_mfma_f32_4x4x1_16B_f32 Toeplitz tiles, 0 v_pk_fma_f32 (r03)
     bool skipIdleLaunches = true;          // option "skip_idle_launches": launches of a level whose islands all belong to roots that do not run are left out
-    bool fuseEpilogue = false;             // option "fuse_epilogue": elemhip_process' launch set of one ends in the last level's kernel (no epilogue launch);
-                                           // measured break-even (the ticket's release / acquire costs what the dependent launch did): off
-    bool specBlockGraph = false;           // option "spec_block_graph": replay elemhip_process' launch set of one from a captured hipGraph
     bool specBlocks = true;                // process(): whole blocks of a settled, fully compiled sequence use the specialised kernels
     int  batchBlocks = 64;                 // blocks per multi-block launch in processBlocks (1 = per-block launches)
-    int  specWavesPerEu = 0;               // option "spec_waves_per_eu": amdgpu_waves_per_eu of the specialised kernels (0: the compiler's choice; 4: two workgroups per CU)
     int  pipelineCopies = 6;               // blocks a stateful island keeps in flight inside a multi-block launch
     bool convAligned = true;               // every process call so far rendered whole 512-frame blocks (conv.hip batch path)
     float* dConvScratch = nullptr; size_t convScratchFloats = 0;
     uint32_t fuseSvfCoef = 2;              // plan.cpp: svf coefficient pre-pass inside the scan: 0 never, 1 always, 2 in lane-packed islands
-    uint32_t soloWaves = 0;                // plan.cpp: heaviest recurrence waves that get no SIMD mate
     uint32_t mixerSplit = 2;               // workgroups a mixer island is cut into (plan.cpp; each renders blockSize / split frames on 8 / split waves)
-    bool streamRing = true;                // stream buffers of the specialised kernels live in a ring of `copies` slices (0: one slice per block; measurement)
     int  packIslands = 0;                  // option "pack_islands": same-shape islands merged into one workgroup (0 auto: when a launch level has more
                                            // stateful islands than the device has CUs; 1 never; K: K per island)
     bool packRoots = false;                // option "pack_roots": lane-packing may merge islands of different ACTIVE roots (render jobs with a root each)
     int  packMax = 2, cuCount = 256;       // auto mode: at most packMax per island (measured on C2: 2 per island pays, 3 leaves two buffer sets and loses); CUs of the device
-    bool chainLdsOut = false;              // option "chain_lds_out" (experiment): streamed recurrences write their block to LDS, only their operands come through the arena
     bool mergePhases = true;               // option "merge_phases": constant-frequency phasors and oscillator phases of a stage share one recurrence task (OP_PHASE)
     uint32_t statelessRows = 64;           // gridDim.y of a multi-block launch: blocks that stateless islands render side by side
     int  timeBatch = 1;
@@ -437,9 +428,8 @@ private:
     void enqueueSpecBlock(const Plan& p, float* outRing = nullptr);
     bool specBlockOk(const Plan& p) const;
     void launchConvolveBatch(const Plan& p, size_t l, uint32_t batch, uint32_t arenaFloats);
-    // specialised kernels when ready, else the interpreter. `epiOut` non-null: if the level is one specialised launch, let its last
-    // workgroup run the epilogue into `epiOut` (island_spec.inc spec_epilogue_tail); returns whether it will
-    bool launchLevelBatch(const Plan& p, size_t level, uint32_t batch, uint32_t arenaFloats, float* epiOut = nullptr);
+    // specialised kernels when ready, else the interpreter
+    void launchLevelBatch(const Plan& p, size_t level, uint32_t batch, uint32_t arenaFloats);
     bool batchEligible(const Plan& p, size_t nOut, bool oneBlock = false) const;
     bool specReady(const Plan& p) const;
     // background mode: the one-off shapes of the current plan are queued for compilation (behind everything else) once the plan
@@ -544,11 +534,6 @@ struct Plan {
     hipGraphExec_t graphExec = nullptr;
     int graphBlocks = 0;
     uint32_t blockChunks = 0;               // block-at-a-time chunks rendered before the capture
-    // elemhip_process of a settled, fully compiled sequence: the launch set of ONE (levels + batch epilogue) as a captured graph
-    hipGraphExec_t specGraphExec = nullptr;
-    float* specGraphOut = nullptr;          // the output pointer baked into it
-    uint32_t specGraphNumOut = 0;           // ... and the output count it was captured for
-    uint32_t specGraphLaunches = 0;         // specialised launches it replays (stats)
     ~Plan();
 };
 

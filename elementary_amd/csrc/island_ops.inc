@@ -90,11 +90,8 @@ struct Persist {
     uint32_t s, prev, prevT, lastStage, lastT;   // this slot's stage, the stage it waits on (kNone: none) and its task count, ditto the last stage
     uint32_t slotArea;    // LDS words between the block buffers of consecutive sets
     uint32_t done;        // out: every block rendered and published
-    // specialised kernels (chain_stream): arena geometry of the launch set, in bytes from Ctx::hbm0
-    uint32_t arenaBytes;      // one block's slice (host inputs + exports)
-    uint32_t streamBase;      // first slice of the stream ring
-    uint32_t streamSlice;     // one slice of the stream ring
-    uint32_t ntasks;          // completion-counter increment of the slot
+    // (unused since the specialised kernels' wave-owning loop was retired; kept: the 512-thread kernel holds this struct in scratch)
+    uint32_t arenaBytes, streamBase, streamSlice, ntasks;
 };
 
 #define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
@@ -105,13 +102,7 @@ struct Persist {
 // pair. tools/micro/wakeup_nop.hip measures it in isolation (profiles/r04/micro_s_wakeup_truncates_s_nop.txt: 50 010 of 300 000
 // stores misplaced next to waves that ping, none without the pings, none when the wait states are five `s_nop 0`). It is what
 // made the specialised kernels of tap islands fault and mis-render one block in ~150 in r03 (a tapOut stores through such a pair;
-// profiles/r04/tap_spec_bisect_matrix.txt). Waiting waves therefore poll with a short s_sleep and are never pinged
-// (an EXPERIMENTAL build can bring the pings back, for measurements only).
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_EXP_WAKEUP)
-#define ELEMHIP_WAKE() asm volatile("s_wakeup" ::: "memory")
-#else
-#define ELEMHIP_WAKE() do { } while (0)
-#endif
+// profiles/r04/tap_spec_bisect_matrix.txt). Waiting waves therefore poll with a short s_sleep and are never pinged.
 
 __device__ __forceinline__ float    u2f(uint32_t u) { return __uint_as_float(u); }
 __device__ __forceinline__ uint32_t f2u(float f)    { return __float_as_uint(f); }
@@ -147,7 +138,6 @@ __device__ __forceinline__ void deferred_publish_now(Deferred& d) {   // the cal
     if (opaque_lane() == 0)
         asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3\n\tds_add_u32 %0, %1" : "=&v"(t0_), "=&v"(t1_) : "s"(d.addrBytes), "s"(d.add) : "memory");
     WAVE_SYNC();
-    ELEMHIP_WAKE();
     d.pending = 0u;
 }
 // KEEP = vector memory operations issued after the stores in question that may stay in flight
@@ -1224,15 +1214,6 @@ __device__ __forceinline__ void chain_store_group(const v4f_& a0, const v4f_& a1
                    "i"(OFF), "i"(OFF + 16), "i"(OFF + 32), "i"(OFF + 48)
                  : "memory");
 }
-#ifndef ELEMHIP_WIDE_CHAIN_BARRIER
-#define ELEMHIP_WIDE_CHAIN_BARRIER 0     // measured on the C4 biquad: slower (32 k cycles per block against 28 k)
-#endif
-#ifndef ELEMHIP_WIDE_CHAIN_DEPTH
-#define ELEMHIP_WIDE_CHAIN_DEPTH 4     // prefetch depth (16-frame groups) of one-stream recurrences with more than three operands (C4 biquad: 27.9 k cycles per block at 8, 24.7 k at 4)
-#endif
-#ifndef ELEMHIP_CHAIN_GROUP_WAIT
-#define ELEMHIP_CHAIN_GROUP_WAIT 1      // one wait per 16-frame group of a streamed operand instead of one per 16-byte load
-#endif
 // DEPTH = groups in flight per streamed operand (16 VGPRs each).
 template <int NIN, uint32_t CM, int DEPTH, typename Step>
 __device__ __forceinline__ void chain_loop_d(const SIn (&in)[NIN], const SOut out, uint32_t n, Step&& step) {
@@ -1252,11 +1233,7 @@ __device__ __forceinline__ void chain_loop_d(const SIn (&in)[NIN], const SOut ou
 #pragma unroll
     for (int k = 0; k < NIN; ++k) if (in[k].isG) arena = in[k].arena;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((float*)arena, 0, 0x7FFFFFFF, 0x00020000);
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_CHAIN_OOB_STORES)
-    uint32_t ooff = io ? out.goff : 0x80000000u;
-#else
     uint32_t ooff = out.goff;
-#endif
     uint32_t ioff[NIN];
 #pragma unroll
     for (int k = 0; k < NIN; ++k) ioff[k] = in[k].goff;
@@ -1277,14 +1254,8 @@ __device__ __forceinline__ void chain_loop_d(const SIn (&in)[NIN], const SOut ou
                 for (int q = 0; q < CHG / 4; ++q) {
                     v4f a;
                     // (global loads: the same broadcast access as a buffer load over the arena descriptor came back ~800 cycles
-                    //  per block later on the C2 voice's envelope pole, profiles/r03/ab_chain_loops.txt; the hook keeps that form)
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_EXP_NO_CHAIN_LOADS)      // MEASUREMENT ONLY (wrong samples): the recurrence runs on a constant instead of its streamed operand
-                    if (in[k].isG) { a.x = a.y = a.z = a.w = in[k].cval; }
-#elif defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_CHAIN_BUFFER_LOADS)
-                    if (in[k].isG) a = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, ioff[k] + (uint32_t)((D * CHG + 4 * q) * 4), soff, 0));
-#else
+                    //  per block later on the C2 voice's envelope pole, profiles/r03/ab_chain_loops.txt)
                     if (in[k].isG) a = *(gcv4)((gcfp)((const char __attribute__((address_space(1)))*)arena + ioff[k] + soff) + (D * CHG + 4 * q));
-#endif
                     else a = ld4(in[k].base + (soff >> 2) + (uint32_t)(D * CHG + 4 * q));
                     x[s_][4 * q] = a.x; x[s_][4 * q + 1] = a.y; x[s_][4 * q + 2] = a.z; x[s_][4 * q + 3] = a.w;
                 }
@@ -1296,19 +1267,9 @@ __device__ __forceinline__ void chain_loop_d(const SIn (&in)[NIN], const SOut ou
         constexpr int D = decltype(Dc)::value;
         float y[CHG];
         // one wait per 16-frame group (for its LAST load: vector loads return in order) instead of one per 16-byte load
-        if (ELEMHIP_CHAIN_GROUP_WAIT && NS0 > 0 && NIN <= 3) {   // (the 6-operand biquad sits at the register limit of its kernels: the extra liveness spills)
+        if (NS0 > 0 && NIN <= 3) {   // (the 6-operand biquad sits at the register limit of its kernels: the extra liveness spills)
 #pragma unroll
             for (int k_ = 0; k_ < NS; ++k_) asm volatile("" : "+v"(x[k_][CHG - 4]), "+v"(x[k_][CHG - 3]), "+v"(x[k_][CHG - 2]), "+v"(x[k_][CHG - 1]));
-        }
-        // A step with several state-free products per frame (biquad: b0 x, b1 x, b2 x) invites the scheduler to compute them for
-        // every prefetched group at once: the C4 biquad loop was 256 VGPRs of hoisted products, register moves and scratch traffic
-        // (28 k cycles per block against a 12 k dependency chain). Making a group's operands opaque where the group starts keeps
-        // its arithmetic inside the group; the values are live there anyway, so this costs no register.
-        if (ELEMHIP_WIDE_CHAIN_BARRIER && NS0 > 0 && NIN > 3) {
-#pragma unroll
-            for (int k_ = 0; k_ < NS; ++k_)
-                asm volatile("" : "+v"(x[k_][0]), "+v"(x[k_][1]), "+v"(x[k_][2]), "+v"(x[k_][3]), "+v"(x[k_][4]), "+v"(x[k_][5]), "+v"(x[k_][6]), "+v"(x[k_][7]),
-                                  "+v"(x[k_][8]), "+v"(x[k_][9]), "+v"(x[k_][10]), "+v"(x[k_][11]), "+v"(x[k_][12]), "+v"(x[k_][13]), "+v"(x[k_][14]), "+v"(x[k_][15]));
         }
 #pragma unroll
         for (int j = 0; j < CHG; ++j) {
@@ -1322,19 +1283,11 @@ __device__ __forceinline__ void chain_loop_d(const SIn (&in)[NIN], const SOut ou
             y[j] = step(xs);
         }
         if (out.isG) {
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_CHAIN_OOB_STORES)       // measurement hook: r02's stores (every lane enabled, the extra lanes' offsets out of range)
-#pragma unroll
-            for (int q = 0; q < CHG / 4; ++q) {
-                v4f a; a.x = y[4 * q]; a.y = y[4 * q + 1]; a.z = y[4 * q + 2]; a.w = y[4 * q + 3];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, a), rsrc, ooff + (uint32_t)((D * CHG + 4 * q) * 4), soff, 0);
-            }
-#else
             v4f a[CHG / 4];
 #pragma unroll
             for (int q = 0; q < CHG / 4; ++q) { a[q].x = y[4 * q]; a[q].y = y[4 * q + 1]; a[q].z = y[4 * q + 2]; a[q].w = y[4 * q + 3]; }
             static_assert(CHG == 16, "chain_store_group writes four 16-byte pieces");
             chain_store_group<D * CHG * 4>(a[0], a[1], a[2], a[3], ooff, rsrc, soff, smask);
-#endif
         } else {
             // LDS output: EXEC cut to the member lanes inside one asm statement as well (a branch around the stores would make
             // the compiler's wait counts for the prefetched loads conservative)
@@ -1389,23 +1342,15 @@ __device__ __forceinline__ void chain_loop_d(const SIn (&in)[NIN], const SOut ou
 // A specialised kernel is compiled for ONE engine block size (ELEMHIP_SPEC_BLOCK, jit.cpp): only the prefetch depth that block
 // size uses is instantiated (r04 carried both and chose by `n` at run time — twice the loops for the optimizer to chew through).
 // A block size that is a multiple of 128 frames gets depth 8; a call that asks for fewer frames than the block (n not a
-// multiple of 128) renders its remainder frame by frame here and stays off the streamed loops (chain_stream_ok).
-#if defined(ELEMHIP_SPEC_BLOCK) && (ELEMHIP_SPEC_BLOCK % 128 == 0)
-#define ELEMHIP_ONE_DEPTH 8
-#elif defined(ELEMHIP_SPEC_BLOCK)
-#define ELEMHIP_ONE_DEPTH 4
-#endif
+// multiple of 128) renders its remainder frame by frame here.
+// One-stream recurrences with more than three operands keep depth 4 (C4 biquad: 27.9 k cycles per block at 8, 24.7 k at 4).
 template <int NIN, uint32_t CM, typename Step>
 __device__ __forceinline__ void chain_loop_m(const SIn (&in)[NIN], const SOut out, uint32_t n, Step&& step) {
     constexpr int NS0 = NIN - __builtin_popcount(CM & ((1u << NIN) - 1u));
-    if constexpr (NS0 == 1 && NIN > 3 && ELEMHIP_WIDE_CHAIN_DEPTH != 8) {
-        chain_loop_d<NIN, CM, ELEMHIP_WIDE_CHAIN_DEPTH>(in, out, n, step);
+    if constexpr (NS0 == 1 && NIN > 3) {
+        chain_loop_d<NIN, CM, 4>(in, out, n, step);
     } else if constexpr (NS0 == 1) {
-#ifdef ELEMHIP_ONE_DEPTH
-        chain_loop_d<NIN, CM, ELEMHIP_ONE_DEPTH>(in, out, n, step);
-#else
-        if ((n & 127u) == 0u) chain_loop_d<NIN, CM, 8>(in, out, n, step); else chain_loop_d<NIN, CM, 4>(in, out, n, step);
-#endif
+        chain_loop_d<NIN, CM, ELEMHIP_SPEC_BLOCK % 128 == 0 ? 8 : 4>(in, out, n, step);
     } else if constexpr (NS0 == 0) chain_loop_d<NIN, CM, 4>(in, out, n, step);   // nothing to load: the depth only shapes the unrolling
     else if constexpr (NS0 == 2) chain_loop_d<NIN, CM, 4>(in, out, n, step);
     else chain_loop_d<NIN, CM, 2>(in, out, n, step);
@@ -1533,191 +1478,6 @@ __device__ __forceinline__ void persist_wait(const Persist& ps, uint32_t use, ui
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_PERSISTENT_CHAINS) && defined(ELEMHIP_SPEC)
-// (EXPERIMENTAL builds only: measured slower than the per-block form — 4.86 vs 4.60 us per C2 block, profiles/r03/ab_chain_loops.txt —
-//  and never enabled in a release kernel; r04 still compiled it into every specialised kernel, a quarter of a synth voice's IR)
-// ---- a streamed recurrence that owns its wave: every block of the launch set in ONE loop --------------------------------------
-// (specialised kernels; island_spec.inc spec_wave_persistent sets Ctx::ps up.) The per-block form above pays, for every
-// block: the trip through the slot walk, the member / record / operand set-up, and — the expensive part — an L2 round trip
-// before its first frame, because it only asks for a block's first span once the walk has found the block ready. Here the
-// wave looks at the NEXT block's completion counters while it still has a span of the current block to go; if that block is
-// ready (it usually is: the recurrence is the slowest wave of its island, its producers run ahead), the loads the last span
-// issues are the next block's first span. The state never leaves the registers `step` captures, a block is published under
-// the next block's loads (or, for a recurrence without streamed operands, after the next block's first span of stores),
-// and the wave only sleeps when a block really is not there yet.
-template <int NIN, uint32_t CM, int DEPTH, typename Step>
-__device__ __forceinline__ void chain_stream_d(const Ctx& c, const SIn (&in)[NIN], const SOut out, Step&& step) {
-    Persist& ps = *c.ps;
-    constexpr int NS0 = NIN - __builtin_popcount(CM & ((1u << NIN) - 1u));
-    constexpr int NS = NS0 > 0 ? NS0 : 1;
-    constexpr uint32_t span = (uint32_t)(DEPTH * CHG);
-    const uint32_t spans = c.n / span;                      // per block (chain_stream_m picks a DEPTH that divides the block)
-    const bool io = opaque_lane() < out.cnt;
-    gfp arena = out.arena;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((float*)arena, 0, 0x7FFFFFFF, 0x00020000);
-    unsigned long long smask = out.cnt >= 64u ? ~0ull : ((1ull << out.cnt) - 1ull);
-    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-    typedef const char __attribute__((address_space(1)))* gcbp;
-    const uint32_t D = ps.D;
-    const uint32_t wLast0 = ps.ctr + ps.lastStage * D, wPrev0 = ps.prev == kNone ? wLast0 : ps.ctr + ps.prev * D;
-    const uint32_t wMine0 = ps.ctr + ps.s * D;
-    // is block (use, copy) ready: the stage this slot waits on has completed it, and block b - D has left the buffer set
-    auto ready = [&](uint32_t use, uint32_t copy) -> bool {
-        uint32_t cPrev, cLast;
-        wlds_ld2(wPrev0 + copy, wLast0 + copy, cPrev, cLast);
-        return (ps.prev == kNone || UNI(cPrev) >= (use + 1u) * ps.prevT) && (use == 0u || UNI(cLast) >= use * ps.lastT);
-    };
-    auto publish = [&](uint32_t copy) {      // the caller has waited for the block's stores
-        uint32_t t0_, t1_;
-        if (opaque_lane() == 0)
-            asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3\n\tds_add_u32 %0, %1" : "=&v"(t0_), "=&v"(t1_) : "s"((wMine0 + copy) << 2), "s"(ps.ntasks) : "memory");
-        WAVE_SYNC();
-        ELEMHIP_WAKE();
-    };
-    auto sliceOff = [&](bool isS, uint32_t b, uint32_t copy) { return isS ? ps.streamBase + copy * ps.streamSlice : b * ps.arenaBytes; };
-    auto load = [&](const uint32_t (&ioff)[NIN], uint32_t soff, auto Dc, float (&x)[NS][CHG]) {
-        constexpr int Dg = decltype(Dc)::value;
-        int s_ = 0;
-#pragma unroll
-        for (int k = 0; k < NIN; ++k) {
-            if (!((CM >> k) & 1u)) {
-#pragma unroll
-                for (int q = 0; q < CHG / 4; ++q) {
-                    const v4f a = *(gcv4)((gcfp)((gcbp)arena + ioff[k] + soff) + (Dg * CHG + 4 * q));
-                    x[s_][4 * q] = a.x; x[s_][4 * q + 1] = a.y; x[s_][4 * q + 2] = a.z; x[s_][4 * q + 3] = a.w;
-                }
-                ++s_;
-            }
-        }
-    };
-    auto run = [&](float (&x)[NS][CHG], uint32_t ooff, uint32_t soff, auto Dc) {
-        constexpr int Dg = decltype(Dc)::value;
-        float y[CHG];
-        if (ELEMHIP_CHAIN_GROUP_WAIT && NS0 > 0 && NIN <= 3) {
-#pragma unroll
-            for (int k_ = 0; k_ < NS; ++k_) asm volatile("" : "+v"(x[k_][CHG - 4]), "+v"(x[k_][CHG - 3]), "+v"(x[k_][CHG - 2]), "+v"(x[k_][CHG - 1]));
-        }
-#pragma unroll
-        for (int j = 0; j < CHG; ++j) {
-            float xs[NIN];
-            int s_ = 0;
-#pragma unroll
-            for (int k = 0; k < NIN; ++k) {
-                if ((CM >> k) & 1u) xs[k] = in[k].cval;
-                else xs[k] = x[s_++][j];
-            }
-            y[j] = step(xs);
-        }
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_CHAIN_OOB_STORES)
-#pragma unroll
-        for (int q = 0; q < CHG / 4; ++q) {
-            v4f a; a.x = y[4 * q]; a.y = y[4 * q + 1]; a.z = y[4 * q + 2]; a.w = y[4 * q + 3];
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, a), rsrc, (io ? ooff : 0x80000000u) + (uint32_t)((Dg * CHG + 4 * q) * 4), soff, 0);
-        }
-#else
-        v4f a[CHG / 4];
-#pragma unroll
-        for (int q = 0; q < CHG / 4; ++q) { a[q].x = y[4 * q]; a[q].y = y[4 * q + 1]; a[q].z = y[4 * q + 2]; a[q].w = y[4 * q + 3]; }
-        chain_store_group<Dg * CHG * 4>(a[0], a[1], a[2], a[3], ooff, rsrc, soff, smask);
-#endif
-    };
-    // X holds span `cs` of block `cb` (buffer set ccopy). Every iteration renders that span while it loads the one after it —
-    // the next span of the block or, in a block's last span, the first span of the NEXT block: the wave makes sure that block
-    // is ready (it normally is; otherwise it sleeps right there, with the current span still to render — nothing the
-    // missing block depends on: D >= 2) before it issues those loads. One load site inside the loop, one in front of it.
-    float X[DEPTH][NS][CHG];
-    bool pending = false;
-    uint32_t cb = ps.b, ccopy = cb % D, cuse = cb / D, cs = 0u, pendCopy = 0u;
-    if (cb >= ps.batch) { ps.done = 1u; return; }
-    while (!ready(cuse, ccopy)) __builtin_amdgcn_s_sleep(2);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    uint32_t cioff[NIN], cooff = sliceOff(out.isS, cb, ccopy) + out.boff;
-#pragma unroll
-    for (int k = 0; k < NIN; ++k) cioff[k] = sliceOff(in[k].isS, cb, ccopy) + in[k].boff;
-    if (NS0 > 0) {
-#pragma unroll
-        for (int k_ = 0; k_ < NIN; ++k_) asm volatile("" : "+v"(cioff[k_]));
-        static_for<0, DEPTH>([&](auto Dc) { load(cioff, 0u, Dc, X[decltype(Dc)::value]); });
-    }
-    for (;;) {
-        const bool lastSpan = cs + 1u == spans;
-        uint32_t nb = cb + 1u, ncopy = ccopy + 1u, nuse = cuse;
-        if (ncopy == D) { ncopy = 0u; ++nuse; }
-        const bool more = nb < ps.batch;
-        // the previous block's stores precede this span's loads but for the newest group's: once only those are outstanding, the
-        // block has reached L2 (vector memory completes in issue order)
-        if (pending && NS0 > 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_s_waitcnt((uint32_t)((((NS0 * (CHG / 4)) >> 4) & 3) << 14 | ((NS0 * (CHG / 4)) & 15) | 0x0070));
-            publish(pendCopy); pending = false;
-        }
-        uint32_t lioff[NIN], lsoff;
-        if (lastSpan && more) {
-            if (pending) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_s_waitcnt(0x0070); publish(pendCopy); pending = false; }   // (one-span blocks, no streamed operand)
-            while (!ready(nuse, ncopy)) __builtin_amdgcn_s_sleep(2);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            lsoff = 0u;
-#pragma unroll
-            for (int k = 0; k < NIN; ++k) lioff[k] = sliceOff(in[k].isS, nb, ncopy) + in[k].boff;
-        } else {
-            lsoff = lastSpan ? cs * span * 4u : (cs + 1u) * span * 4u;      // no block left: a harmless re-read of this span
-#pragma unroll
-            for (int k = 0; k < NIN; ++k) lioff[k] = cioff[k];
-        }
-        const uint32_t soff = cs * span * 4u;
-        uint32_t ooff = cooff;
-        asm volatile("" : "+v"(ooff));
-#pragma unroll
-        for (int k_ = 0; k_ < NIN; ++k_) asm volatile("" : "+v"(lioff[k_]));
-        static_for<0, DEPTH>([&](auto Dc) {
-            constexpr int d = decltype(Dc)::value;
-            run(X[d], ooff, soff, Dc);
-            if (NS0 > 0) load(lioff, lsoff, Dc, X[d]);
-            if (NS0 == 0 && d == 0 && pending) {
-                // no streamed operand: the previous block is published once this span's first group of stores has been issued
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_s_waitcnt((uint32_t)(((CHG / 4) & 15) | 0x0070));
-                publish(pendCopy); pending = false;
-            }
-        });
-        if (!lastSpan) { ++cs; continue; }
-        pending = true; pendCopy = ccopy;                    // block cb is complete (its last stores are on their way)
-        if (!more) break;
-        cb = nb; ccopy = ncopy; cuse = nuse; cs = 0u;
-#pragma unroll
-        for (int k = 0; k < NIN; ++k) cioff[k] = lioff[k];
-        cooff = sliceOff(out.isS, cb, ccopy) + out.boff;
-    }
-    if (pending) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_s_waitcnt(0x0070); publish(pendCopy); }
-    (void)io;
-    ps.done = 1u;
-}
-// does the running recurrence own its wave for the whole launch set (and is it all streams: its output and every operand that
-// is not a broadcast cell)?
-template <int NIN>
-__device__ __forceinline__ bool chain_stream_ok(const Ctx& c, const SIn (&in)[NIN], uint32_t cmask, const SOut& out) {
-#if defined(ELEMHIP_ONE_DEPTH) && ELEMHIP_ONE_DEPTH == 8
-    if (c.ps == nullptr || c.ps->on == 0u || !out.isG || (c.n & 127u) != 0u) return false;
-#else
-    if (c.ps == nullptr || c.ps->on == 0u || !out.isG || (c.n & 63u) != 0u) return false;
-#endif
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < NIN; ++k) if (!((cmask >> k) & 1u) && !in[k].isG) ok = false;
-    return ok;
-}
-template <int NIN, uint32_t CM, typename Step>
-__device__ __forceinline__ void chain_stream_m(const Ctx& c, const SIn (&in)[NIN], const SOut out, Step&& step) {
-    constexpr int NS0 = NIN - __builtin_popcount(CM & ((1u << NIN) - 1u));
-#ifdef ELEMHIP_ONE_DEPTH
-    if constexpr (NS0 <= 1) chain_stream_d<NIN, CM, ELEMHIP_ONE_DEPTH>(c, in, out, step);
-#else
-    if constexpr (NS0 <= 1) { if ((c.n & 127u) == 0u) chain_stream_d<NIN, CM, 8>(c, in, out, step); else chain_stream_d<NIN, CM, 4>(c, in, out, step); }
-#endif
-    else if constexpr (NS0 == 2) chain_stream_d<NIN, CM, 4>(c, in, out, step);
-    else chain_stream_d<NIN, CM, 2>(c, in, out, step);
-}
-#endif   // ELEMHIP_SPEC chain_stream
 
 // chain_loop for the recurrence nodes whose whole state lives in the registers `step` captures: when the task owns its wave
 // it goes on with the following blocks of the launch right here — the operands that are block buffers and the output move
@@ -1727,7 +1487,7 @@ template <int NIN, typename Run>
 __device__ __forceinline__ void persist_blocks(const Ctx& c, const SIn (&in)[NIN], uint32_t cmask, const SOut outBase, Run&& run) {
     Persist* ps = c.ps;
 #ifdef ELEMHIP_SPEC
-    const bool own = false;      // (a specialised kernel's wave-owning recurrences go through chain_stream, never through this LDS protocol)
+    const bool own = false;      // (a specialised kernel's recurrences never take this LDS protocol)
 #else
     const bool own = ps != nullptr && ps->on != 0u;
 #endif
@@ -1750,42 +1510,10 @@ __device__ __forceinline__ void persist_blocks(const Ctx& c, const SIn (&in)[NIN
 }
 template <int NIN, typename Step>
 __device__ __forceinline__ void chain_blocks(const Ctx& c, const SIn (&in)[NIN], uint32_t cmask, const SOut outBase, Step&& step) {
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_PERSISTENT_CHAINS) && defined(ELEMHIP_SPEC)
-    if (chain_stream_ok<NIN>(c, in, cmask & ((1u << NIN) - 1u), outBase)) {
-        const uint32_t cm = cmask & ((1u << NIN) - 1u);
-        bool done = true;
-        if constexpr (NIN == 1) { if (cm) chain_stream_m<1, 1u>(c, in, outBase, step); else chain_stream_m<1, 0u>(c, in, outBase, step); }
-        else if constexpr (NIN == 2) {
-            switch (cm) {
-                case 0: chain_stream_m<2, 0u>(c, in, outBase, step); break;
-                case 1: chain_stream_m<2, 1u>(c, in, outBase, step); break;
-                case 2: chain_stream_m<2, 2u>(c, in, outBase, step); break;
-                default: chain_stream_m<2, 3u>(c, in, outBase, step); break;
-            }
-        } else if constexpr (NIN == 3) {
-            switch (cm) {
-                case 0: chain_stream_m<3, 0u>(c, in, outBase, step); break;
-                case 1: chain_stream_m<3, 1u>(c, in, outBase, step); break;
-                case 2: chain_stream_m<3, 2u>(c, in, outBase, step); break;
-                case 3: chain_stream_m<3, 3u>(c, in, outBase, step); break;
-                case 4: chain_stream_m<3, 4u>(c, in, outBase, step); break;
-                case 5: chain_stream_m<3, 5u>(c, in, outBase, step); break;
-                case 6: chain_stream_m<3, 6u>(c, in, outBase, step); break;
-                default: chain_stream_m<3, 7u>(c, in, outBase, step); break;
-            }
-        } else {
-            if (cm == 0x1Fu) chain_stream_m<6, 0x1Fu>(c, in, outBase, step); else done = false;
-        }
-        if (done) return;
-    }
-#endif
     persist_blocks<NIN>(c, in, cmask, outBase, [&](const SIn (&inB)[NIN], const SOut out) { chain_loop<NIN>(inB, cmask, out, c.n, step); });
 }
 template <int NIN, uint32_t CM, typename Step>
 __device__ __forceinline__ void chain_blocks_m(const Ctx& c, const SIn (&in)[NIN], const SOut outBase, Step&& step) {
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_PERSISTENT_CHAINS) && defined(ELEMHIP_SPEC)
-    if (chain_stream_ok<NIN>(c, in, CM, outBase)) { chain_stream_m<NIN, CM>(c, in, outBase, step); return; }
-#endif
     persist_blocks<NIN>(c, in, CM, outBase, [&](const SIn (&inB)[NIN], const SOut out) { chain_loop_m<NIN, CM>(inB, out, c.n, step); });
 }
 // CMT >= 0: the task's cell mask is a compile-time constant (a specialised kernel's task descriptor): only that variant of the
@@ -1890,67 +1618,12 @@ __device__ __forceinline__ void ser_biquad(const Ctx& c, const Member& m, uint32
     in[0] = sin_of(c, opnd_lane(c, m, 0)); in[1] = sin_of(c, opnd_lane(c, m, 1)); in[2] = sin_of(c, opnd_lane(c, m, 2));
     in[3] = sin_of(c, opnd_lane(c, m, 3)); in[4] = sin_of(c, opnd_lane(c, m, 4)); in[5] = sin_of(c, opnd_lane(c, m, 5));
     float z1 = u2f(r[rec::S0]), z2 = u2f(r[rec::S1]);
-    // (written as 2-vectors so that the products and differences issue as v_pk_mul_f32 / v_pk_add_f32 — six slots per frame
-    //  instead of nine — the loop was not faster: 24-28 k cycles per block either way, the packed operations' latency sits on
-    //  the loop-carried path; tools/c4_variants.sh)
-    // ELEMHIP_BIQUAD_FORM (engine option "biquad_form", a run-time compiler tuning: every form performs the reference's nine IEEE
-    // operations on the same operands — Filters.h:103-105, no contraction — only their packing into instructions differs):
-    //   0  nine scalar VALU slots per frame;
-    //   1  the OFF-chain pair (b1 x, b2 x) as one v_pk_mul_f32, everything on the loop-carried path scalar: eight slots (VERDICT r04 #5c);
-    //   2  (b1 x, b2 x), (a1 y, a2 y) and the two differences packed: six slots, packed latency on the chain (measured no faster in r04).
-#ifndef ELEMHIP_BIQUAD_FORM
-#define ELEMHIP_BIQUAD_FORM 4      // (r06; per C4 set of 1024 blocks: form 0 11.0 ms, 3 13.3, 4 10.25, 5 11.1 — profiles/r06/c4_biquad_forms.txt)
-#endif
-    typedef float bq2 __attribute__((ext_vector_type(2)));
+    // The nine scalar operations of Filters.h:103-105 (no contraction) with the compiler's pairing switched off (an empty asm on
+    // one twin of each pair): left alone, its SLP pass packs (b1 x, b2 x), (a1 y, a2 y) and the two differences with a v_mov_b32
+    // per broadcast ON the loop-carried path (y -> (y, y) -> product), five dependent operations per frame instead of four.
+    // Packed forms were measured slower or no faster (profiles/r06/c4_biquad_forms.txt; DESIGN.md §8).
     chain_blocks_c<CMT, 6>(c, in, cm, sout_of(c, m), [&](const float (&x)[6]) {
         const float xx = x[5];
-#if ELEMHIP_BIQUAD_FORM == 1
-        bq2 b12; b12.x = x[1]; b12.y = x[2];
-        bq2 xv; xv.x = xx; xv.y = xx;
-        const bq2 p = b12 * xv;
-        const float y = x[0] * xx + z1;
-        z1 = p.x - x[3] * y + z2;
-        z2 = p.y - x[4] * y;
-#elif ELEMHIP_BIQUAD_FORM == 3
-        // r06: six slots WITHOUT the register moves the compiler's own packing (SLP) puts around packed operations — it builds
-        // (x, x) and (y, y) with two v_mov_b32 per frame, on the loop-carried path (form 0 as compiled in r05: 6 float + 4 move
-        // slots per frame, 49 cycles; the ISA is in profiles/r06/c4_biquad_isa.txt). Here the packed operations take the broadcast
-        // from the LOW half of a register pair (op_sel_hi), so y goes from the add that makes it straight into the product.
-        // The same nine IEEE operations on the same operands (a packed operation rounds each half like the scalar one; the
-        // difference is a sum with the subtrahend's sign flipped).
-        bq2 b12; b12.x = x[1]; b12.y = x[2];
-        bq2 a12; a12.x = x[3]; a12.y = x[4];
-        // (xv / yv: the HIGH halves are deliberately left unassigned — the packed products read the low half twice, and any value
-        //  given to the high half would be a v_mov_b32 per frame again)
-        bq2 xv; xv.x = xx;
-        bq2 p, t, d;
-        asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(p) : "v"(b12), "v"(xv));
-        const float y = x[0] * xx + z1;
-        bq2 yv; yv.x = y;
-        asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t) : "v"(a12), "v"(yv));
-        asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(p), "v"(t));
-        z1 = d.x + z2;
-        z2 = d.y;
-#elif ELEMHIP_BIQUAD_FORM == 5
-        // form 4 with the two differences kept apart as well: nine scalar slots, NO packed operation anywhere on the loop-carried
-        // path y -> a1 y -> b1 x - a1 y -> + z2 -> y' (a packed operation there costs more than the slot it saves: form 3, all
-        // packed, 13.3 ms per C4 set; form 0 as the compiler packs it, 11.0; form 4, one packed difference left, 10.3).
-        const float s0 = x[0] * xx, p1 = x[1] * xx;
-        float p2 = x[2] * xx;
-        asm("" : "+v"(p2));
-        const float y = s0 + z1;
-        const float t1 = x[3] * y;
-        float t2 = x[4] * y;
-        asm("" : "+v"(t2));
-        const float d1 = p1 - t1;
-        float d2 = p2 - t2;
-        asm("" : "+v"(d2));
-        z1 = d1 + z2;
-        z2 = d2;
-#elif ELEMHIP_BIQUAD_FORM == 4
-        // r06: the nine scalar operations with the compiler's pairing switched off (an empty asm on one twin of each pair): what
-        // form 0 was meant to be — its (b1 x, b2 x), (a1 y, a2 y) and the two differences were packed by the SLP pass with a
-        // v_mov_b32 per broadcast ON the loop-carried path (y -> (y, y) -> product), five dependent operations per frame instead of four.
         const float s0 = x[0] * xx, p1 = x[1] * xx;
         float p2 = x[2] * xx;
         asm("" : "+v"(p2));
@@ -1960,21 +1633,6 @@ __device__ __forceinline__ void ser_biquad(const Ctx& c, const Member& m, uint32
         asm("" : "+v"(t2));
         z1 = p1 - t1 + z2;
         z2 = p2 - t2;
-#elif ELEMHIP_BIQUAD_FORM == 2
-        bq2 b12; b12.x = x[1]; b12.y = x[2];
-        bq2 a12; a12.x = x[3]; a12.y = x[4];
-        bq2 xv; xv.x = xx; xv.y = xx;
-        const bq2 p = b12 * xv;
-        const float y = x[0] * xx + z1;
-        bq2 yv; yv.x = y; yv.y = y;
-        const bq2 d = p - a12 * yv;
-        z1 = d.x + z2;
-        z2 = d.y;
-#else
-        const float y = x[0] * xx + z1;
-        z1 = x[1] * xx - x[3] * y + z2;
-        z2 = x[2] * xx - x[4] * y;
-#endif
         return y;
     });
     r[rec::S0] = f2u(z1); r[rec::S1] = f2u(z2);

@@ -207,9 +207,6 @@ __device__ __forceinline__ void spec_stateful(const Ctx& c, uint32_t off) {
 template <class T>
 __device__ __forceinline__ void spec_task(const Ctx& c, uint32_t off) {
     constexpr uint32_t op = T::opcode, count = T::count;
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_EXP_SOLO)   // MEASUREMENT ONLY: only the float recurrences run, every other task is skipped (timing without contention)
-    if constexpr (!(op == OP_PHASOR || op == OP_POLE || op == OP_BLEPSAW)) return;
-#endif
     if constexpr (op == OP_RAND || op == OP_Z || op == OP_SDELAY || op == OP_DELAY || op == OP_SAMPLESEQ ||
                   op == OP_METER || op == OP_SNAPSHOT || op == OP_SCOPE || op == OP_CAPTURE) {
         static_for<0, (int)count>([&](auto K) {
@@ -259,48 +256,11 @@ __device__ __forceinline__ void spec_task_at(const Ctx& c, uint32_t delta) {
     });
 }
 
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_PERSISTENT_CHAINS)
-// ---- a wave whose only slot is one streamed recurrence task: the task renders the whole launch set itself -----------
-// (island_ops.inc chain_stream: next block's first span prefetched under the current block's last, state in registers)
-template <class P, int W>
-__device__ __forceinline__ void spec_wave_persistent(Ctx& c, float* hbm, uint32_t batch, uint32_t arenaFloats, uint32_t streamBase, uint32_t streamSlice,
-                                                     int64_t sampleTime0, unsigned long long* trace) {
-    using S = typename gen::template Slot<W, 0>;
-    Persist ps;
-    ps.on = 1u; ps.done = 0u; ps.b = 0u; ps.batch = batch; ps.D = P::D; ps.ctr = P::ldsCounters;
-    ps.s = S::stage; ps.prev = S::prev; ps.prevT = S::prevT; ps.lastStage = P::lastStage; ps.lastT = P::lastT; ps.slotArea = P::slotArea;
-    ps.arenaBytes = arenaFloats * 4u; ps.streamBase = streamBase * 4u; ps.streamSlice = streamSlice * 4u; ps.ntasks = S::ntasks;
-    c.ps = &ps; c.defer = nullptr;
-    c.hbm = (gfp)hbm; c.offE = 0u; c.hbmS = (gfp)hbm + streamBase; c.offS = streamBase * 4u; c.bset = 0u;
-    c.sampleTime = sampleTime0;
-    const unsigned long long t0 = trace ? clock64() : 0ull;
-    if (batch > 0u) S::run(c, 0u);
-    if (batch > 0u && __builtin_amdgcn_ballot_w64(ps.done != 0u) == 0ull) __builtin_trap();   // the generator only marks slots persistent whose task takes the streaming path
-    c.ps = nullptr;
-    if (trace && c.lane == 0) {
-        typedef __attribute__((address_space(1))) unsigned long long* gtp;
-        gtp w = (gtp)(trace + (size_t)W * 192);
-        w[0] = 1ull; w[4] = clock64() - t0; w[5] = batch;
-    }
-}
-
-#endif   // EXPERIMENTAL persistent chains
 // ---- the block pipeline of one wave -----------------------------------------------------------------------------
 template <class P, int W>
 __device__ __forceinline__ void spec_wave(Ctx& c, float* hbm, uint32_t batch, uint32_t arenaFloats, uint32_t streamBase, uint32_t streamSlice,
                                           int64_t sampleTime0, unsigned long long* trace) {
     constexpr int K = P::waveSlots[W];
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_EXP_KEEP_WAVES)   // MEASUREMENT ONLY: the other waves leave at once, no slot waits for anything
-    if (!((ELEMHIP_EXP_KEEP_WAVES >> W) & 1)) return;
-#endif
-    if constexpr (K == 1) {
-        if constexpr (gen::template Slot<W, 0>::persistent) {
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_PERSISTENT_CHAINS)   // (opt-in: as written the cross-block loop costs more in register copies and spills than it saves; profiles/r03/ab_chain_loops.txt)
-            spec_wave_persistent<P, W>(c, hbm, batch, arenaFloats, streamBase, streamSlice, sampleTime0, trace);
-            return;
-#endif
-        }
-    }
     if constexpr (K > 0) {
         constexpr uint32_t D = P::D;
         uint32_t nb[K], cp[K], us[K];              // per slot: next block, its buffer set (b % D) and use number (b / D)
@@ -323,28 +283,15 @@ __device__ __forceinline__ void spec_wave(Ctx& c, float* hbm, uint32_t batch, ui
                 uint32_t cPrev, cLast;
                 wlds_ld2(wPrev, wLast, cPrev, cLast);
                 bool ready = (S::prev == kNone || UNI(cPrev) >= (use + 1u) * S::prevT) && (use == 0u || UNI(cLast) >= use * P::lastT);
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_EXP_KEEP_WAVES)
-                ready = true;
-#endif
                 if (!ready) return;
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 const uint32_t b = nb[j];
                 // the block's arena slice (host inputs, exports) and its slice of the stream ring (set b % D, like the LDS buffers)
                 c.hbm = (gfp)hbm + (size_t)b * arenaFloats; c.offE = b * arenaFloats * 4u; c.bset = b;
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_STREAM_PER_BLOCK)   // measurement hook (with engine option "stream_ring" = 0): a stream slice per block of the launch set, as in r02
-                c.hbmS = (gfp)hbm + (size_t)(streamBase + b * streamSlice); c.offS = (streamBase + b * streamSlice) * 4u;
-#else
                 c.hbmS = (gfp)hbm + (size_t)(streamBase + copy * streamSlice); c.offS = (streamBase + copy * streamSlice) * 4u;
-#endif
                 c.sampleTime = sampleTime0 + (int64_t)b * (int64_t)c.n;
                 const unsigned long long t0 = trace ? clock64() : 0ull;
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_CHAIN_PRIO)                      // tuning hook (ELEMHIP_JIT_DEFINES): issue priority of a recurrence slot over its SIMD mate
-                if constexpr (S::deferPublish) __builtin_amdgcn_s_setprio(ELEMHIP_CHAIN_PRIO);
-#endif
                 S::run(c, copy * P::slotArea);
-#if defined(ELEMHIP_EXPERIMENTAL) && defined(ELEMHIP_CHAIN_PRIO)
-                if constexpr (S::deferPublish) __builtin_amdgcn_s_setprio(0);
-#endif
                 if (trace) busy[j] += clock64() - t0;
                 // publish: what other waves read from this one goes through LDS only; LDS operations of a wave complete in
                 // issue order, so the counter update is ordered behind the block's samples
@@ -366,20 +313,16 @@ __device__ __forceinline__ void spec_wave(Ctx& c, float* hbm, uint32_t batch, ui
                     WAVE_SYNC();
                     // waiting waves sleep between polls (a poll is two LDS reads, and seven back-to-back pollers keep the LDS
                     // instruction queue busy enough to slow the recurrence waves' own loads and stores by a third); they are NOT
-                    // pinged awake: s_wakeup breaks other waves' hazard wait states (island_ops.inc, ELEMHIP_WAKE)
-                    ELEMHIP_WAKE();
+                    // pinged awake: s_wakeup breaks other waves' hazard wait states (island_ops.inc)
                 }
                 nb[j] = b + 1u;
                 if (++cp[j] == D) { cp[j] = 0u; ++us[j]; }
                 if (b + 1u == batch) --remaining;
                 ran = true;
             });
-#ifndef ELEMHIP_SPEC_SLEEP
-#define ELEMHIP_SPEC_SLEEP 1
-#endif
             if (!ran) {
                 if (dq.pending) { __builtin_amdgcn_s_waitcnt(0x0070); deferred_publish_now(dq); }   // nothing to hand it to: publish now
-                else __builtin_amdgcn_s_sleep(ELEMHIP_SPEC_SLEEP);   // ~64 * N cycles between two polls
+                else __builtin_amdgcn_s_sleep(1);   // ~64 * N cycles between two polls
             }
         }
         if (dq.pending) { __builtin_amdgcn_s_waitcnt(0x0070); deferred_publish_now(dq); }
@@ -427,53 +370,6 @@ __device__ __forceinline__ void spec_stateless_blocks(Ctx& c, float* hbm, uint32
             }
             __syncthreads();     // the next stage (or the next block's first) reads / rewrites what this one produced
         });
-    }
-}
-
-// ---- fused epilogue of a launch set of ONE (elemhip_process) -------------------------------------------------------------------
-// A synchronous one-block call is three dependent launches on a 256-voice graph (voices, mixers, epilogue) and every dependent
-// launch costs ~6 us of dispatch latency, more than the mixer level's work. When the last level is a single launch the host
-// passes its workgroup count: each workgroup takes a ticket once its exports are out, and the one that draws the last ticket
-// does what elemhip_epilogue_batch_kernel does for block 0 of a set of one — the output bus (running roots summed per channel
-// in render-sequence order, GraphRenderSequence.h:214-219) and the sample clock. Same adds in the same order: same bits.
-// (Host side: only plans with a handful of roots and no taps — the tail keeps no tables in LDS and promotes no tap buffers.)
-// `doneFlag` (r06): when the output block is the host's mapped block, the last workgroup also publishes the call's completion word
-// behind it (what elemhip_epilogue_batch_kernel's publish_done does, island.inc) — elemhip_process then ends on that word with ONE
-// launch per level and no epilogue launch at all.
-__device__ __forceinline__ void spec_epilogue_tail(const PlanView& pv, const uint32_t* recs_, const float* hbm_, const Globals* gc,
-                                                   uint32_t groups, float* out_, uint32_t* doneFlag, uint32_t doneValue) {
-    if (groups == 0u) return;
-    Globals* g = const_cast<Globals*>(gc);
-    gcup recs = (gcup)recs_; gcfp hbm = (gcfp)hbm_; gfp out = (gfp)out_;
-    const uint32_t n = UNI(g->numSamples), numOut = UNI(g->numOut), stride = UNI(g->blockStride);   // (the host refuses more than kMaxOutBus channels)
-    const uint32_t nr = min(UNI(pv.numRoots), 32u);
-    __syncthreads();                         // every wave of this workgroup has issued its exports; the island's LDS is free
-    uint32_t* box = reinterpret_cast<uint32_t*>(lds);      // [0] ticket, [1..32] channel of root r (or none), [33..64] its arena buffer
-    if (threadIdx.x < nr) {                  // what does not depend on the other workgroups is looked up before the ticket
-        const RootEntry re = pv.roots[threadIdx.x];
-        box[1u + threadIdx.x] = spec_root_running(recs, re.rec, numOut) ? recs[re.rec * kRecDwords + rec::ROOT_CHANNEL] : 0xFFFFFFFFu;
-        box[33u + threadIdx.x] = re.hbm;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");     // exports visible device-wide before the ticket is
-    if (threadIdx.x == 0u) box[0] = atomicAdd(&g->epiTicket, 1u);
-    __syncthreads();
-    const uint32_t ticket = UNI(box[0]);
-    if (ticket != groups - 1u) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // the last one in: everybody else's exports are behind this fence
-    for (uint32_t idx = threadIdx.x; idx < numOut * n; idx += 512u) {
-        const uint32_t ch = idx / n, i = idx - ch * n;
-        float acc = 0.0f;
-        for (uint32_t r = 0; r < nr; ++r)
-            if (box[1u + r] == ch) acc += hbm[(size_t)box[33u + r] * stride + i];
-        out[(size_t)ch * stride + i] = acc;
-    }
-    if (threadIdx.x == 0u) { g->epiTicket = 0u; g->sampleTime += (int64_t)n; g->blockSlot = 0u; }
-    if (doneFlag) {
-        __syncthreads();                                            // every thread's stores of the output block have completed ...
-        if (threadIdx.x == 0u) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");         // ... and are in host memory
-            __hip_atomic_store(doneFlag, doneValue, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
     }
 }
 

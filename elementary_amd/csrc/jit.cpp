@@ -99,22 +99,6 @@ static std::string libraryDir() {
     return ".";
 }
 
-// tuning experiments ("NAME=VALUE NAME2=VALUE2" -> #define lines in front of the node library, part of the cache key) exist only
-// in a `make EXPERIMENTAL=1` build: several of the hooks they reach render wrong samples by design (measurement only)
-// whitelisted tunings (Jit::setTuning): "#define NAME VALUE" lines in front of the node library
-static std::mutex gTuningMu;
-static std::string gTuning;
-static std::string tuningDefines() { std::lock_guard<std::mutex> l(gTuningMu); return gTuning; }
-
-static std::string experimentalDefines() {
-#ifdef ELEMHIP_EXPERIMENTAL
-    const char* d = std::getenv("ELEMHIP_JIT_DEFINES");
-    return d ? d : "";
-#else
-    return "";
-#endif
-}
-
 struct Jit::Impl {
     std::mutex mu;
     std::condition_variable cv;
@@ -122,7 +106,6 @@ struct Jit::Impl {
     std::deque<std::shared_ptr<SpecEntry>> queue;                          // wanted by a plan now (newest served first when backed up)
     std::deque<std::shared_ptr<SpecEntry>> lowQueue;                       // promoted one-off shapes
     std::unordered_map<uint64_t, std::pair<uint64_t, uint64_t>> prefixHash; // (LDS words, block) -> key hash state behind the fixed part of the source
-    std::string prefixDefs;                                                 // ... under these experimental defines
     std::unordered_map<std::string, uint32_t> sightings;                    // one-island shapes a background-mode plan left to the interpreter
     std::unordered_set<std::string> notOnDisk;                             // keys the disk cache was asked about in vain
     std::vector<std::thread> workers;
@@ -153,9 +136,6 @@ struct Jit::Impl {
         int maj = 0, min = 0;
         (void)hiprtcVersion(&maj, &min);
         versionTag = "hiprtc" + std::to_string(maj) + "." + std::to_string(min) + ";gfx950;-O3;-ffp-contract=off;v2";
-#ifdef ELEMHIP_EXPERIMENTAL
-        versionTag += ";experimental";
-#endif
         unsigned n = std::min(8u, std::max(2u, std::thread::hardware_concurrency() / 4u));   // a plan of a new graph brings several shapes at once
         if (const char* t = std::getenv("ELEMHIP_JIT_THREADS")) n = (unsigned)std::max(1, std::atoi(t));
         // hiprtc serialises compilations inside a process (jitc_main.cpp): the workers hand their shapes to a helper process each
@@ -416,25 +396,11 @@ void Jit::setEntryCap(uint32_t cap) {
     impl->evict();
 }
 
-// everything in front of the generated text (a function of the LDS size, the engine's block size and the experimental defines)
+// everything in front of the generated text (a function of the LDS size and the engine's block size)
 static std::string sourcePrefix(uint32_t ldsWords, uint32_t block, size_t reserveExtra) {
     std::string s;
     s.reserve(sizeof(kSpecDeviceH) + sizeof(kSpecOpsInc) + sizeof(kSpecInc) + reserveExtra + 256);
     s += "#define ELEMHIP_SPEC 1\n#define ELEMHIP_SPEC_LDS_WORDS " + std::to_string(ldsWords) + "\n#define ELEMHIP_SPEC_BLOCK " + std::to_string(block) + "\n";
-#ifdef ELEMHIP_EXPERIMENTAL
-    s += "#define ELEMHIP_EXPERIMENTAL 1\n";
-#endif
-    s += tuningDefines();
-    const std::string defs = experimentalDefines();
-    if (!defs.empty()) {
-        std::string tok;
-        for (size_t i = 0; i <= defs.size(); ++i) {
-            if (i == defs.size() || defs[i] == ' ') {
-                if (!tok.empty()) { const size_t eq = tok.find('='); s += "#define " + (eq == std::string::npos ? tok + " 1" : tok.substr(0, eq) + " " + tok.substr(eq + 1)) + "\n"; }
-                tok.clear();
-            } else tok += defs[i];
-        }
-    }
     // hiprtc has no host headers: the fixed-width names the sources use (same underlying types as <stdint.h> on this target)
     s += "typedef unsigned char uint8_t; typedef unsigned short uint16_t; typedef unsigned int uint32_t; typedef unsigned long uint64_t;\n"
          "typedef signed char int8_t; typedef short int16_t; typedef int int32_t; typedef long int64_t; typedef unsigned long uintptr_t;\n";
@@ -450,34 +416,20 @@ std::string Jit::fullSource(const std::string& generated, uint32_t ldsWords, uin
 
 // The key is a hash of the whole translation unit; its first ~300 KB are the same for every shape of one LDS size, so the hash
 // state behind them is kept (FNV-1a runs front to back: same keys as hashing the full source, a tenth of the time).
-bool Jit::setTuning(const std::string& name, int value) {
-    const bool ok = (name == "ELEMHIP_BIQUAD_FORM" && value >= 0 && value <= 5) ||
-                    (name == "ELEMHIP_WIDE_CHAIN_DEPTH" && (value == 2 || value == 4 || value == 8));
-    if (!ok) return false;
-    std::lock_guard<std::mutex> l(gTuningMu);
-    // replace an earlier line of the same name
-    const std::string head = "#define " + name + " ";
-    size_t at = gTuning.find(head);
-    if (at != std::string::npos) gTuning.erase(at, gTuning.find('\n', at) - at + 1);
-    gTuning += head + std::to_string(value) + "\n";
-    return true;
-}
-
 std::string Jit::keyFor(const std::string& generated, uint32_t ldsWords, uint32_t block) {
-    const std::string defs = experimentalDefines() + "|" + tuningDefines();
     const uint64_t pk = ((uint64_t)block << 32) | ldsWords;
     uint64_t h1 = 0, h2 = 0;
     bool have = false;
     {
         std::lock_guard<std::mutex> l(impl->mu);
-        if (impl->prefixDefs == defs) { auto it = impl->prefixHash.find(pk); if (it != impl->prefixHash.end()) { h1 = it->second.first; h2 = it->second.second; have = true; } }
+        auto it = impl->prefixHash.find(pk);
+        if (it != impl->prefixHash.end()) { h1 = it->second.first; h2 = it->second.second; have = true; }
     }
     if (!have) {
         const std::string pre = sourcePrefix(ldsWords, block, 0);
         h1 = fnv1a(pre, fnv1a(impl->versionTag, 1469598103934665603ull));
         h2 = fnv1a(pre, fnv1a(impl->versionTag, 0x9E3779B97F4A7C15ull) ^ 0xA5A5A5A5ull);
         std::lock_guard<std::mutex> l(impl->mu);
-        if (impl->prefixDefs != defs) { impl->prefixHash.clear(); impl->prefixDefs = defs; }
         if (impl->prefixHash.size() > 256) impl->prefixHash.clear();
         impl->prefixHash[pk] = {h1, h2};
     }

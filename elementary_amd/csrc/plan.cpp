@@ -81,7 +81,7 @@ uint32_t leafArityOfOp(uint16_t op);
 } // namespace
 uint32_t leafArityForCodegen(uint16_t op) { return leafArityOfOp(op); }
 std::string emitSpecSource(const Island& I, const std::vector<Task>& tasks, const SpecProgram& sp,
-                           const std::vector<uint32_t>& stageTab, uint32_t blockSize, uint32_t wavesPerEu);   // codegen.cpp
+                           const std::vector<uint32_t>& stageTab, uint32_t blockSize);   // codegen.cpp
 namespace {
 uint32_t leafArityOfOp(uint16_t op) {
     if (op == OP_SAW_SHAPE || op == OP_SQUARE_SHAPE || op == OP_PHASE) return 1;
@@ -701,8 +701,8 @@ std::shared_ptr<Plan> PlanBuilder::build(uint32_t maxIslandNodes, uint32_t maxCo
         if (e.planCache != 0) {
             uint64_t h = 1469598103934665603ull;
             auto mix = [&](uint64_t v) { h ^= v; h *= 1099511628211ull; h ^= h >> 29; };
-            mix(bs); mix(maxCopies); mix(splitCoefStage); mix(wantSpec); mix(e.fuseSvfCoef); mix(e.mergePhases); mix(e.soloWaves);
-            mix(e.mixerSplit); mix(e.chainLdsOut); mix(packCount[ii]); mix((uint32_t)islandPairsTaps[ii]); mix(streamStart);
+            mix(bs); mix(maxCopies); mix(splitCoefStage); mix(wantSpec); mix(e.fuseSvfCoef); mix(e.mergePhases);
+            mix(e.mixerSplit); mix(packCount[ii]); mix((uint32_t)islandPairsTaps[ii]); mix(streamStart);
             mix(B.nodes.size());       // (the owning root's record is not an input of the schedule: Island::rootRec is re-made per plan)
             for (int k : B.nodes) {
                 const NI& x = ni[k];
@@ -742,8 +742,8 @@ std::shared_ptr<Plan> PlanBuilder::build(uint32_t maxIslandNodes, uint32_t maxCo
                     auto f = std::lower_bound(B.nodes.begin(), B.nodes.end(), niIndex);
                     return (f != B.nodes.end() && *f == niIndex) ? (uint32_t)(f - B.nodes.begin()) : 0xFFFFu;
                 };
-                smix(bs); smix(maxCopies); smix(splitCoefStage); smix(wantSpec); smix(e.fuseSvfCoef); smix(e.mergePhases); smix(e.soloWaves);
-                smix(e.mixerSplit); smix(e.chainLdsOut); smix(packCount[ii]); smix((uint32_t)islandPairsTaps[ii]);
+                smix(bs); smix(maxCopies); smix(splitCoefStage); smix(wantSpec); smix(e.fuseSvfCoef); smix(e.mergePhases);
+                smix(e.mixerSplit); smix(packCount[ii]); smix((uint32_t)islandPairsTaps[ii]);
                 smix(B.nodes.size());
                 for (int k : B.nodes) {
                     const NI& x = ni[k];
@@ -1311,21 +1311,6 @@ std::shared_ptr<Plan> PlanBuilder::build(uint32_t maxIslandNodes, uint32_t maxCo
                     for (size_t k = 0; k < ser.size(); ++k) { taken[k] = true; if (k < par.size()) taken[k + 4] = true; }
                     for (int w = 0; w < (int)kWaves; ++w) if (!taken[w]) freeIdx[nf++] = w;
                     for (int f = 0; pi < par.size() && f < nf; ++f) renum[par[pi++]] = freeIdx[f];
-                    // `solo_waves` = n: the n heaviest recurrence waves keep their SIMD to themselves — the mate's tasks move
-                    // to the lightest sample-parallel wave that is not such a mate (it then owns two slots per block)
-                    const size_t solo = std::min<size_t>({(size_t)e.soloWaves, ser.size(), par.size() > 1 ? par.size() - 1 : 0});
-                    if (solo > 0) {
-                        uint32_t ld[kWaves] = {};
-                        for (int w = 0; w < (int)kWaves; ++w) ld[renum[w]] = load[w];
-                        for (size_t k = 0; k < solo; ++k) {
-                            const int mate = renum[par[k]];
-                            int best = -1;
-                            for (size_t j = solo; j < par.size(); ++j) { const int w = renum[par[j]]; if (best < 0 || ld[w] < ld[best]) best = w; }
-                            if (best < 0) break;
-                            for (int w = 0; w < (int)kWaves; ++w) if (renum[w] == mate) renum[w] = best;
-                            ld[best] += ld[mate]; ld[mate] = 0;
-                        }
-                    }
                     for (size_t q = 0; q < tasks.size(); ++q) taskWave[q] = renum[taskWave[q]];
                 }
             }
@@ -1512,18 +1497,15 @@ std::shared_ptr<Plan> PlanBuilder::build(uint32_t maxIslandNodes, uint32_t maxCo
                     if (m.nin == kNone || m.nin < leafArityOfOp(t.opcode) || memberNode[t.first + k] < 0) ok = false;
                 }
                 if (!ok) continue;
-                // (option "chain_lds_out": only the operands stream through the arena; the output block stays in its LDS slot)
-                sp.gdirect[q] = e.chainLdsOut ? 0 : 1;
+                sp.gdirect[q] = 1;
                 for (uint32_t k = 0; k < t.count; ++k) {
                     const uint32_t mi = t.first + k;
                     const int x = memberNode[mi];
                     const bool osc = blepSplit(ni[x].n->op);            // (an OP_PHASE task carries both kinds)
-                    if (!e.chainLdsOut) {
-                        uint32_t b;
-                        if (osc) { b = kOpStream | p.numStreamBuffers++; phaseStream.emplace(x, b); }
-                        else { b = stream(x); streamed.insert(x); }
-                        sp.members[mi].outHbm = b;
-                    }
+                    uint32_t b;
+                    if (osc) { b = kOpStream | p.numStreamBuffers++; phaseStream.emplace(x, b); }
+                    else { b = stream(x); streamed.insert(x); }
+                    sp.members[mi].outHbm = b;
                     for (uint32_t j = 0; j < members[mi].nin; ++j) {
                         const uint32_t oi = members[mi].opnd + j;
                         if ((operands[oi] & kOpKindMask) != kOpLds) continue;
@@ -1633,11 +1615,11 @@ std::shared_ptr<Plan> PlanBuilder::build(uint32_t maxIslandNodes, uint32_t maxCo
             for (uint32_t o : sp.phaseOp) mix((o & kOpKindMask) == kOpHbm ? (kOpHbm | arenaPos(o & kOpValMask)) : o);
             for (uint8_t g : sp.gdirect) mix(g);
             for (uint32_t k = 0; k < 2 * S; ++k) mix(stageTab[k]);
-            mix(bs); mix((uint32_t)sp.hbmTab.size()); mix((uint32_t)e.specWavesPerEu);
+            mix(bs); mix((uint32_t)sp.hbmTab.size());
             auto it = e.specTextCache.find(h);
             if (it == e.specTextCache.end()) {
                 auto txt = std::make_shared<SpecText>();
-                txt->text = emitSpecSource(I, tasks, sp, stageTab, bs, (uint32_t)e.specWavesPerEu);
+                txt->text = emitSpecSource(I, tasks, sp, stageTab, bs);
                 it = e.specTextCache.emplace(h, std::move(txt)).first;
             }
             p.specText[ii] = it->second;
@@ -1951,7 +1933,7 @@ std::string Engine::describePlan() {
     kv("num_islands", p.islands.size()); kv("num_levels", p.levelOffsets.size() - 1); kv("num_tasks", p.numTasks);
     kv("num_members", p.numMembers); kv("num_operands", p.numOperands); kv("num_nodes", p.nodeIds.size());
     kv("plan_islands_relocated", st.planIslandsRelocated); kv("plan_relocation_mismatches", st.planRelocationMismatches);
-    kv("plan_spec_texts", specTextCache.size()); kv("plan_spec_fade_blocks", st.specFadeBlocks); kv("plan_idle_launches_skipped", st.idleLaunchesSkipped); kv("plan_fused_epilogues", st.fusedEpilogues); kv("plan_prog_heaps", st.progHeaps); kv("plan_prog_heap_used_dwords", p.progHeap ? p.progHeap->usedDwords : 0);
+    kv("plan_spec_texts", specTextCache.size()); kv("plan_spec_fade_blocks", st.specFadeBlocks); kv("plan_idle_launches_skipped", st.idleLaunchesSkipped); kv("plan_prog_heaps", st.progHeaps); kv("plan_prog_heap_used_dwords", p.progHeap ? p.progHeap->usedDwords : 0);
     kv("plan_islands_reused", st.planIslandsReused); kv("plan_islands_scheduled", st.planIslandsScheduled); kv("plan_cache_mismatches", st.planCacheMismatches);
     kv("num_hbm_buffers", p.numHbmBuffers); kv("num_stream_buffers", p.numStreamBuffers); kv("pack_k", p.packK);
     kv("max_lds_bytes", p.maxLdsBytes); kv("num_roots", p.roots.size());

@@ -193,8 +193,8 @@ int  elemhip_sum_buses(int deviceOrdinal, void* hipStream, float* dst, const flo
  * "specialize" (0 interpreter kernels only, 1 per-island-shape kernels compiled in the background and used once ready, 2 commit
  * waits for them), "spec_blocks" / "host_out_direct" (elemhip_process through the specialised kernels / output written straight
  * into pinned host memory), "use_graph" / "graph_blocks" (per-block launch path replayed from a hipGraph), "stateless_rows",
- * "mixer_split", "pipeline_copies", "merge_phases", "stream_ring", "pack_islands" / "pack_max" / "cu_count" (lane-packing of
- * isomorphic islands), "profile_launches", "time_batch", "chain_lds_out" (measurement). Unknown keys return code 6. */
+ * "mixer_split", "pipeline_copies", "merge_phases", "pack_islands" / "pack_max" / "cu_count" (lane-packing of isomorphic
+ * islands), "profile_launches", "time_batch". Unknown keys return code 6. */
 int  elemhip_set_option(elemhip_t*, const char* key, double value);
 
 #ifdef __cplusplus

@@ -357,36 +357,23 @@ def test_relocated_programs_in_verify_mode():
     assert total >= 16 + 48 + 100
 
 
-def test_release_library_carries_no_measurement_hooks():
+def test_release_library_has_no_measurement_hooks_and_refuses_retired_options():
     """the wrong-sample hooks (ELEMHIP_EXP_*, the out-of-range chain stores, the persistent chains) and the
-    ELEMHIP_JIT_DEFINES back door exist only in a `make EXPERIMENTAL=1` build: a release library's embedded node-library text
-    (what its run-time compiler sees) has the blocks removed (tools/strip_experimental.py), jit.cpp does not read the variable,
-    `conv_mfma` takes 0 / 1, and the only tunings the compiler accepts are the whitelisted bit-identical ones."""
+    ELEMHIP_JIT_DEFINES back door are gone from the library and from the node-library text its run-time compiler sees,
+    `conv_mfma` takes 0 / 1, and the options of the retired kernel variants are refused like any unknown key."""
     from elementary_amd.runtime import LIB_PATH, ElemHipError
     data = open(LIB_PATH, "rb").read()
-    for needle in (b"ELEMHIP_EXP_", b"ELEMHIP_JIT_DEFINES", b"ELEMHIP_CHAIN_OOB_STORES", b"ELEMHIP_PERSISTENT_CHAINS", b"ELEMHIP_STREAM_PER_BLOCK"):
+    for needle in (b"ELEMHIP_EXPERIMENTAL", b"ELEMHIP_EXP_", b"ELEMHIP_JIT_DEFINES", b"ELEMHIP_CHAIN_OOB_STORES", b"ELEMHIP_PERSISTENT_CHAINS",
+                   b"ELEMHIP_STREAM_PER_BLOCK"):
         assert needle not in data, needle
     assert b"ELEMHIP_SPEC_BLOCK" in data            # (the embedded text is there)
     rt = Runtime(48000.0, 512, device=-1)
     rt.set_option("conv_mfma", 2)                    # clamped to 1: the operand-swapped bring-up probe is gone
-    rt.set_option("biquad_form", 1)
-    rt.set_option("biquad_form", 5)                  # (r06: forms 0-5, every one the reference's nine IEEE operations on the same operands)
-    rt.set_option("biquad_form", 4)                  # ... back to the default
-    with pytest.raises(ElemHipError):
-        rt.set_option("biquad_form", 6)
-    with pytest.raises(ElemHipError):
-        rt.set_option("stream_ring", 0)
-    # and the stripper itself: nested, #elif chains, #else branches
-    import subprocess, sys, tempfile
-    src = "a\n#if defined(ELEMHIP_EXPERIMENTAL) && defined(X)\nbad1\n#elif defined(ELEMHIP_EXPERIMENTAL) && defined(Y)\nbad2\n#else\nkeep1\n#endif\n" \
-          "#ifdef OTHER\nkeep2\n#if defined(ELEMHIP_EXPERIMENTAL) && defined(Z)\nbad3\n#endif\n#else\nkeep3\n#endif\n" \
-          "#if defined(ELEMHIP_EXPERIMENTAL) && defined(A)\nbad4\n#elif FOO\nkeep4\n#else\nkeep5\n#endif\nz\n"
-    with tempfile.NamedTemporaryFile("w", suffix=".inc", delete=False) as f:
-        f.write(src)
-    out = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "strip_experimental.py"), f.name],
-                         capture_output=True, text=True, check=True).stdout
-    os.unlink(f.name)
-    assert out == "a\nkeep1\n#ifdef OTHER\nkeep2\n#else\nkeep3\n#endif\n#if FOO\nkeep4\n#else\nkeep5\n#endif\nz\n", out
+    for key in ("biquad_form", "wide_chain_depth", "stream_ring", "conv_long_mac_lds", "spec_block_graph", "chain_lds_out", "solo_waves",
+                "spec_waves_per_eu", "fuse_epilogue"):
+        for val in (0, 1):
+            with pytest.raises(ElemHipError):
+                rt.set_option(key, val)
 
 
 def test_kernel_cache_is_bounded_and_one_off_shapes_are_deferred():
@@ -530,16 +517,16 @@ def test_rccl_exchange_snippet_compiles_and_links():
         assert os.path.getsize(os.path.join(d, "rccl_bus_sum")) > 1000
 
 
-def test_round5_call_path_options_on_a_dry_handle():
+def test_call_path_options_on_a_dry_handle():
     """`sync_poll` (elemhip_process ends on the epilogue's word in mapped host memory), `resident` / `resident_idle_us` / `resident_after`
-    (the opt-in resident kernel) and `spec_waves_per_eu` (register cap of the generated kernels) are options every handle takes, and
+    (the opt-in resident kernel) are options every handle takes, and
     `elemhip_describe_plan` says which way a handle waits; unknown keys are still refused; the stats struct carries the resident counters."""
     from elementary_amd.runtime import ElemHipError
     rt = dry(48000.0)
     assert rt.render(el.mul(0.5, el.cycle(220.0)))["result"] == 0
     d = rt.describe_plan()
     assert d["sync_poll"] == 1 and d["resident"] == 0 and d["sync_polls"] == 0 and d["resident_blocks"] == 0
-    for key, val in (("sync_poll", 0), ("resident", 1), ("resident_idle_us", 500), ("resident_after", 5), ("spec_waves_per_eu", 4)):
+    for key, val in (("sync_poll", 0), ("resident", 1), ("resident_idle_us", 500), ("resident_after", 5)):
         rt.set_option(key, val)
     d = rt.describe_plan()
     assert d["sync_poll"] == 0 and d["resident"] == 1
@@ -547,12 +534,8 @@ def test_round5_call_path_options_on_a_dry_handle():
     assert st["resident_launches"] == 0 and st["resident_blocks"] == 0
     with pytest.raises(ElemHipError):
         rt.set_option("resident_kernel", 1)
-    # the register cap is part of a generated kernel's text (and so of its cache key), nothing else changes
+    # a generated kernel carries no register cap: the compiler chooses
     rt2 = dry(48000.0)
     rt2.set_option("specialize", 2)
     assert rt2.render(el.mul(0.5, el.cycle(220.0)))["result"] == 0
-    plain = rt2.spec_info(0)["source"]
-    rt2.set_option("spec_waves_per_eu", 4)
-    assert rt2.render(el.mul(0.25, el.cycle(221.0)))["result"] == 0
-    capped = rt2.spec_info(0)["source"]
-    assert "amdgpu_waves_per_eu(4, 4)" in capped and "amdgpu_waves_per_eu" not in plain
+    assert "amdgpu_waves_per_eu" not in rt2.spec_info(0)["source"]
