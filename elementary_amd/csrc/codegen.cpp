@@ -10,11 +10,9 @@
 #include <string>
 #include <vector>
 
-#include "engine.h"
+#include "plan_build.h"
 
 namespace elemhip {
-
-uint32_t leafArityForCodegen(uint16_t op);   // plan.cpp
 
 static std::string u(uint32_t v) {
     if (v == kNone) return "kNone";
@@ -63,7 +61,7 @@ std::string emitSpecSource(const Island& I, const std::vector<Task>& tasks, cons
         for (uint32_t k = 0; k < t.count; ++k) {
             const uint32_t mi = t.first + k;
             const Member& m = members[mi];
-            const uint32_t nops = m.nin == kNone ? std::min<uint32_t>(leafArityForCodegen(t.opcode), kMaxHostIn) : m.nin;
+            const uint32_t nops = m.nin == kNone ? std::min<uint32_t>(leafArityOfOp(t.opcode), kMaxHostIn) : m.nin;
             o << "        " << (k ? "else " : "") << "if constexpr (K == " << k << ") {\n";
             o << "            m.rec = " << u(m.rec) << "; m.opnd = " << u(m.opnd) << "; m.nin = " << u(m.nin) << ";\n";
             o << "            m.outLds = " << (m.outLds == kNone ? std::string("kNone") : u(m.outLds) + " + off") << ";\n";

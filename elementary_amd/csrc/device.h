@@ -1,4 +1,4 @@
-// device.h — plan encoding shared by the host graph compiler (plan.cpp) and the HIP
+// device.h — plan encoding shared by the host graph compiler (plan.cpp, plan_island.cpp) and the HIP
 // block-render kernels (kernels.hip).
 //
 // Vocabulary

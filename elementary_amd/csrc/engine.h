@@ -73,7 +73,7 @@ struct Outlet { int32_t dest; uint32_t channel; };
 
 struct Node {
     int32_t id = 0;
-    uint32_t planVisited = 0, planOnStack = 0;   // plan-build scratch (PlanBuilder::traverse): epoch marks instead of hash sets
+    uint32_t planVisited = 0, planOnStack = 0;   // plan-build scratch (PlanBuilder::traverse, plan.cpp): epoch marks instead of hash sets
     int32_t planIdx = -1;                        // ... planner entry of output channel 0 in the build whose epoch is planVisited
     uint32_t planChans = 0;                      // ... and how many channel entries follow it
     uint16_t op = OP_INVALID;
@@ -109,7 +109,7 @@ struct SpecText {
     uint32_t keyLdsWords = 0; // the LDS footprint the key was computed for
 };
 
-// One island's scheduled program as the planner left it (plan.cpp "island program cache"): an island whose nodes, edges,
+// One island's scheduled program as the planner left it (plan_island.cpp "island program cache"): an island whose nodes, edges,
 // arena positions and options are unchanged at the next build takes these instead of being scheduled again.
 // Table buffers of retired plans, kept for the next plan (a live graph re-plans dozens of times a second; hipMalloc / hipFree
 // cost more than the upload, and hipFree synchronises the device). A buffer comes back when its plan dies, which is after the
@@ -136,7 +136,7 @@ struct IslandProgram {
     Island I;                            // progBegin / rootRec are re-made per plan
     std::vector<uint32_t> blob;          // host copy of the program (16-byte padded): describePlan, plan_cache = 2
     std::vector<uint32_t> members;       // (node id, opcode, record, arena buffer) of every member in render order: checked on a cache hit (the key is a hash)
-    // relocation (plan.cpp, "same island, other nodes"): the records and arena buffers the program names, in the order a canonical
+    // relocation (plan_island.cpp, "same structure, other nodes"): the records and arena buffers the program names, in the order a canonical
     // walk of the island meets them, and the first stream buffer it was given — an island of the same STRUCTURE (another voice of
     // the patch) takes this program with the i-th record / buffer replaced by its own i-th
     std::vector<uint32_t> canonRecs, canonHbms;
@@ -230,6 +230,7 @@ public:
 
 private:
     friend struct PlanBuilder;
+    friend struct IslandSchedule;
     int initErr = 0;
     bool dry = false;                      // device == -1: host logic only, cannot render
     double sampleRate;
@@ -262,7 +263,7 @@ private:
     // generated text per island-program signature: 256 voices (and every re-plan of a live graph) format their text once
     // (the kernel cache key of a text lives NEXT TO the text, in the same shared object: nothing is keyed by an address)
     std::unordered_map<uint64_t, std::shared_ptr<SpecText>> specTextCache;
-    // per-island programs of earlier builds (plan.cpp "island program cache"); same locking as specTextCache
+    // per-island programs of earlier builds (plan_island.cpp "island program cache"); same locking as specTextCache
     std::unordered_map<uint64_t, std::shared_ptr<IslandProgram>> islandCache;
     int planCache = 1;                     // 0 off, 1 reuse unchanged islands' programs, 2 schedule anyway and compare (tests)
     uint32_t planEpoch = 0;                // PlanBuilder::traverse marks
@@ -447,7 +448,7 @@ private:
     int debugBuildDelayMs = 0;
 };
 
-// The specialised-kernel variant of one island's program (plan.cpp builds it, codegen.cpp turns it into text).
+// The specialised-kernel variant of one island's program (plan_island.cpp builds it, codegen.cpp turns it into text).
 struct SpecProgram {
     std::vector<Member> members;           // same indexing as the interpreter's tables
     std::vector<uint32_t> operands;

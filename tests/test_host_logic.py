@@ -357,6 +357,17 @@ def test_relocated_programs_in_verify_mode():
     assert total >= 16 + 48 + 100
 
 
+def test_planner_output_is_pinned():
+    """tests/plan_corpus.py: the `program_digest` of every plan of the corpus (island headers, program blobs, level / convolve /
+    root / tap tables, specialised-kernel texts) equals the one recorded in tests/golden/plan_digests.json. A planner change
+    that moves plans on purpose re-records the file (`python tests/plan_corpus.py`); the diff names the graphs that moved."""
+    import plan_corpus
+    got, want = plan_corpus.digests(), plan_corpus.recorded()
+    assert sorted(got) == sorted(want)
+    moved = sorted(k for k in want if got[k] != want[k])
+    assert not moved, moved
+
+
 def test_release_library_has_no_measurement_hooks_and_refuses_retired_options():
     """the wrong-sample hooks (ELEMHIP_EXP_*, the out-of-range chain stores, the persistent chains) and the
     ELEMHIP_JIT_DEFINES back door are gone from the library and from the node-library text its run-time compiler sees,
