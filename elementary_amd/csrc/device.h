@@ -83,6 +83,8 @@ enum Op : uint16_t {
                       // first (Task::s0 of them: step = f * (1 / sr), Core.h:85-136), then the phase halves of blepsaw / blepsquare
                       // (inc = f / sr, Oscillators.h:60-66). Same loop for every lane — phase' = fract(phase + inc) — so a synth
                       // voice's gate phasor and its two oscillators cost one recurrence wave instead of two.
+    // (appended behind the pseudo-ops: every earlier opcode keeps its number, and with it every recorded plan digest)
+    OP_FFT,           // wasm/FFT.h: pass-through + a one-channel 8192-frame ring; the relay transforms `size` frames of it (fft_frames.hip)
     OP_COUNT_
 };
 
@@ -270,6 +272,7 @@ enum : uint32_t {
     // after EVERY block (offline-renderer/index.ts:112-120); the log lets a host that rendered a whole launch set do the same afterwards.
     EVT_LOG = P0, EVT_LOGMASK = P2, EVT_BLK = 11, EVT_LOGN = 12,
     // scope: device ring [4 channels][8192] (MultiChannelRingBuffer.h), write / read positions shared with the host relay
+    // (fft: the same three dwords, one channel)
     SCP_RING = P0, SCP_WRITE = 8, SCP_READ = 9,
     // sample (Sample.h:22-231): buffer, length, new-buffer flag, mode (0 trigger, 1 gate, 2 loop), offsets, gain smoothing alpha;
     // state: change detector, current reader, two readers {target gain, gain, pos (double)}

@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "launch.h"
+#include "fft_frames.h"
 
 namespace elemhip {
 
@@ -68,6 +69,7 @@ static const std::unordered_map<std::string, uint16_t>& opTable() {
         {"tapIn", OP_TAPIN}, {"tapOut", OP_TAPOUT},
         {"blepsaw", OP_BLEPSAW}, {"blepsquare", OP_BLEPSQUARE}, {"bleptriangle", OP_BLEPTRIANGLE},
         {"mc.table", OP_TABLE}, {"mc.sample", OP_MCSAMPLE}, {"mc.sampleseq", OP_SAMPLESEQ}, {"time", OP_TIME}, {"metro", OP_METRO}, {"sampleseq", OP_SAMPLESEQ}, {"convolve", OP_CONVOLVE}, {"table", OP_TABLE}, {"seq2", OP_SEQ2}, {"sparseq2", OP_SPARSEQ2}, {"sparseq", OP_SPARSEQ}, {"capture", OP_CAPTURE}, {"mc.capture", OP_CAPTURE}, {"sample", OP_SAMPLE}, {"meter", OP_METER}, {"snapshot", OP_SNAPSHOT}, {"scope", OP_SCOPE},
+        {"fft", OP_FFT},
     };
     return t;
 }
@@ -248,6 +250,9 @@ Engine::~Engine() {
     if (evRelay) (void)hipEventDestroy(evRelay);
     if (dRelay) (void)hipFree(dRelay);
     if (hRelay) (void)hipHostFree(hRelay);
+    if (dFft) (void)hipFree(dFft);
+    if (hFft) (void)hipHostFree(hFft);
+    for (void* t : dFftTables) if (t) (void)hipFree(t);
     if (ownStream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -431,6 +436,22 @@ int Engine::allocRing(Node& n, size_t floats) {
     return kOk;
 }
 
+// The fft node's tables of one size (fft_frames.h): Blackman-Harris window and transform twiddles, made in double, uploaded once.
+int Engine::ensureFftTables(uint32_t size) {
+    if (dry || !ffr::size_ok(size)) return kOk;          // (8192 is accepted and never fires: no transform, no tables)
+    uint32_t lg = 0;
+    while ((1u << lg) < size) ++lg;
+    if (dFftTables[lg]) return kOk;
+    std::vector<double> host((size_t)size * 3u);
+    ffr::make_window(size, host.data());
+    ffr::make_twiddles(size, reinterpret_cast<ffr::c2*>(host.data() + size));
+    void* d = nullptr;
+    HIP_OK(hipMalloc(&d, host.size() * sizeof(double)));
+    HIP_OK(hipMemcpy(d, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
+    dFftTables[lg] = d;
+    return kOk;
+}
+
 // A new impulse response = a new convolver starting from silence (Convolve.h:47-51: a fresh
 // TwoStageFFTConvolver per `path` assignment). Builds the conv:: state: header + IR partition spectra.
 int Engine::setConvolverIr(Node& n, const ResourcePtr& res) {
@@ -599,6 +620,9 @@ int Engine::createNode(int32_t id, const std::string& type) {   // Runtime.h:293
         case OP_SCOPE:   // Analyzers.h:142-149: ringBuffer(4) of 8192 frames, channels = 1, size = 512
             n.props["channels"] = Value::number(1.0); n.props["size"] = Value::number(512.0);
             break;
+        case OP_FFT:     // wasm/FFT.h:18-25: ringBuffer(1) of 8192 frames, size = 1024
+            n.props["size"] = Value::number(1024.0);
+            break;
         case OP_SAMPLE:  // VariablePitchLerpReader(float sampleRate, ...): gainSmoothAlpha(1.0 - exp(-1.0 / (0.01 * sampleRate))), Sample.h:163
             r[rec::SMP_ALPHA] = fbits((float)(1.0 - std::exp(-1.0 / (0.01 * (double)(float)sampleRate)))); break;
         case OP_RAND:    r[rec::S0] = (uint32_t)std::rand(); break;               // Noise.h:42
@@ -643,6 +667,10 @@ int Engine::createNode(int32_t id, const std::string& type) {   // Runtime.h:293
     } else if (nn.op == OP_SCOPE) {                                               // Analyzers.h:145: MultiChannelRingBuffer(4) x 8192
         rc = allocRing(nn, 4u * 8192u);
         if (rc == kOk) writeParamPtr(nn, rec::SCP_RING, nn.ring.ptr);
+    } else if (nn.op == OP_FFT) {                                                 // wasm/FFT.h:20: MultiChannelRingBuffer(1) x 8192
+        rc = allocRing(nn, 8192u);
+        if (rc == kOk) writeParamPtr(nn, rec::SCP_RING, nn.ring.ptr);
+        if (rc == kOk) rc = ensureFftTables(1024u);
     } else if (nn.op == OP_CAPTURE && !nn.mc) {                                   // Capture.h:17: ringBuffer(1, bitceil(sr)); (mc.capture: at commit)
         const size_t cap = (size_t)bitceil((int)(size_t)sampleRate);
         rc = allocRing(nn, cap);
@@ -880,6 +908,16 @@ int Engine::setProperty(int32_t id, const std::string& key, const Value& v) {   
         case OP_SCOPE:                                             // Analyzers.h:151-173
             if (key == "size") { if (!v.isNumber()) return kInvalidPropertyType; if (v.num < 256 || v.num > 8192) return kInvalidPropertyValue; }
             if (key == "channels") { if (!v.isNumber()) return kInvalidPropertyType; if (v.num < 0 || v.num > 4) return kInvalidPropertyValue; }
+            if (key == "name") { if (!v.isString()) return kInvalidPropertyType; }
+            break;
+        case OP_FFT:                                               // wasm/FFT.h:31-72 (a rejected value leaves the node as it was)
+            if (key == "size") {
+                if (!v.isNumber()) return kInvalidPropertyType;
+                const int size = (int)v.num;
+                if (size <= 0 || (size & (size - 1)) != 0 || size < 256 || size > 8192) return kInvalidPropertyValue;
+                const int rc = ensureFftTables((uint32_t)size);
+                if (rc != kOk) return rc;
+            }
             if (key == "name") { if (!v.isString()) return kInvalidPropertyType; }
             break;
         case OP_TABLE:                                             // Table.h:20-33
@@ -1274,9 +1312,85 @@ int Engine::processQueuedEvents(void (*cb)(const char*, const char*, void*), voi
     const uint64_t hostBlocks = sliced ? hostEnds.size() : windowBlocks;            // host blocks in the window
     const uint64_t lastBlock = hostBlocks ? hostBlocks - 1 : 0;
     const uint32_t hostFrames = (uint32_t)hostBlockSize;
+    // ---- fft nodes (wasm/FFT.h:92-132): what every node hands on in this window, then ONE launch for all frames ----
+    // A relay emits at most one frame per node (`ringBuffer.size() >= size`, where scope has `>`); the blockwise relay replays that
+    // comparison after every host block of the window, as the scope branch below does. The kernel reads the rings where the snapshot
+    // says they are readable and writes into the relay's own buffer, on the relay's stream: the render thread is not involved.
+    struct FftEmit { uint64_t block; size_t outFloat; };
+    std::vector<std::vector<FftEmit>> fftEmits(items.size());
+    {
+        std::vector<FftFrame> frames;
+        size_t outFloats = 0;
+        for (size_t ix = 0; ix < items.size(); ++ix) {
+            Node& n = *items[ix].n;
+            if (n.op != OP_FFT) continue;
+            const uint32_t* rc_ = reinterpret_cast<const uint32_t*>(hRelay + items[ix].recOff);
+            auto q = n.props.find("size");
+            const uint32_t size = (q != n.props.end() && q->second.isNumber()) ? (uint32_t)q->second.num : 1024u;
+            const uint32_t cap = 8192u, mask = cap - 1u;
+            uint32_t lg = 0;
+            while ((1u << lg) < size) ++lg;
+            // (the ring never holds more than cap - 1 frames: size 8192 never fires, FFT.h:96 with MultiChannelRingBuffer.h:99-110)
+            if (!n.ring.ptr || !ffr::size_ok(size) || !dFftTables[lg]) continue;
+            const uint32_t wEnd = rc_[rec::SCP_WRITE];
+            uint32_t r = rc_[rec::SCP_READ];
+            const uint64_t steps = blockwise ? std::max<uint64_t>(1, std::min<uint64_t>(hostBlocks, (cap - 1) / hostFrames)) : 1;
+            bool any = false;
+            for (uint64_t s_ = 0; s_ < steps; ++s_) {
+                const uint32_t w = (wEnd - (uint32_t)((steps - 1 - s_) * (uint64_t)hostFrames)) & mask;
+                const uint32_t full = w > r ? w - r : ((cap - (r - w)) & mask);
+                if (!(full >= size)) continue;
+                const double* tab = static_cast<const double*>(dFftTables[lg]);
+                frames.push_back(FftFrame{static_cast<const float*>(n.ring.ptr), tab, tab + size, nullptr, r, size});
+                fftEmits[ix].push_back({lastBlock - std::min<uint64_t>(lastBlock, steps - 1 - s_), outFloats});
+                outFloats += (size_t)size + 2u;
+                r = (r + size) & mask;
+                any = true;
+            }
+            if (any) writeBack.push_back({&n, rec::SCP_READ, r});
+        }
+        if (!frames.empty()) {
+            const size_t descBytes = (frames.size() * sizeof(FftFrame) + 255u) & ~(size_t)255u, need = descBytes + outFloats * 4u;
+            if (need > fftBytes) {                                   // (only this relay and its stream, idle here, ever touch the pair)
+                const size_t capB = std::max<size_t>(need * 2, 65536);
+                uint8_t* d = nullptr; uint8_t* h = nullptr;
+                HIP_OK(hipMalloc(reinterpret_cast<void**>(&d), capB));
+                HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&h), capB, hipHostMallocDefault));
+                if (dFft) (void)hipFree(dFft);
+                if (hFft) (void)hipHostFree(hFft);
+                dFft = d; hFft = h; fftBytes = capB;
+            }
+            size_t at = 0;
+            for (FftFrame& f : frames) { f.out = reinterpret_cast<float*>(dFft + descBytes) + at; at += (size_t)f.size + 2u; }
+            std::memcpy(hFft, frames.data(), frames.size() * sizeof(FftFrame));
+            HIP_OK(hipMemcpyAsync(dFft, hFft, frames.size() * sizeof(FftFrame), hipMemcpyHostToDevice, relayStream));
+            HIP_OK(launch_fft_frames(relayStream, reinterpret_cast<const FftFrame*>(dFft), (uint32_t)frames.size()));
+            HIP_OK(hipMemcpyAsync(hFft + descBytes, dFft + descBytes, outFloats * 4u, hipMemcpyDeviceToHost, relayStream));
+            HIP_OK(hipStreamSynchronize(relayStream));
+            fftLaunches++; fftFrames += frames.size();
+            for (auto& v : fftEmits) for (FftEmit& e : v) e.outFloat += descBytes / 4u;
+        }
+    }
     for (const Item& it : items) {
         Node& n = *it.n;
         const uint32_t* rc_ = reinterpret_cast<const uint32_t*>(hRelay + it.recOff);
+        if (n.op == OP_FFT) {
+            const std::vector<FftEmit>& em = fftEmits[(size_t)(&it - items.data())];
+            if (em.empty()) continue;
+            auto q = n.props.find("size");
+            const size_t bins = ((q != n.props.end() && q->second.isNumber()) ? (size_t)q->second.num : 1024u) / 2u + 1u;
+            const std::string src = srcOf(n);
+            for (const FftEmit& e : em) {
+                const float* sp = reinterpret_cast<const float*>(hFft) + e.outFloat;
+                std::string j = "{\"source\": " + src + ", \"data\": {\"real\": [";
+                for (size_t i = 0; i < bins; ++i) { if (i) j += ", "; j += numStr(sp[i]); }
+                j += "], \"imag\": [";
+                for (size_t i = 0; i < bins; ++i) { if (i) j += ", "; j += numStr(sp[bins + i]); }
+                j += "]}}";
+                evs.push_back({e.block, it.order, "fft", std::move(j)});
+            }
+            continue;
+        }
         if (n.op == OP_SCOPE) {                                           // Analyzers.h:192-245, MultiChannelRingBuffer.h:61-86
             auto numOr = [&](const char* k, double dflt) { auto q = n.props.find(k); return (q != n.props.end() && q->second.isNumber()) ? q->second.num : dflt; };
             const size_t size = (size_t)numOr("size", 512.0), channels = std::min<size_t>(4, (size_t)numOr("channels", 1.0));
@@ -1413,7 +1527,7 @@ int Engine::processQueuedEvents(void (*cb)(const char*, const char*, void*), voi
 }
 
 // How many blocks may pass between two blockwise relays for their result to be exactly the per-block relay's: the per-block
-// readout logs hold 1024 blocks; a scope ring (8192 frames, `size` of them per event) must not overrun inside a window; a
+// readout logs hold 1024 blocks; a scope or fft ring (8192 frames, `size` of them per event) must not overrun inside a window; a
 // capture node's take is placed by the relay that sees its gate fall, so it wants a relay per block.
 uint32_t Engine::eventWindowBlocks() {
     std::lock_guard<std::mutex> control(ctl);
@@ -1436,6 +1550,14 @@ uint32_t Engine::eventWindowBlocks() {
             if (size < (double)hostBlockSize) return 1u;
             const double room = 8192.0 - 1.0 - std::max(1.0, size);
             w = std::min<uint32_t>(w, (uint32_t)std::max(1.0, std::floor(room / (double)hostBlockSize)));
+        }
+        if (n.op == OP_FFT) {
+            auto q = n.props.find("size");
+            const double size = (q != n.props.end() && q->second.isNumber()) ? q->second.num : 1024.0;
+            // as the scope, with `>=` where the scope compares with `>`: under a per-block relay the ring holds at most size - 1 frames
+            // when a window begins, so w blocks fit without an overrun while size - 1 + w * block <= 8191
+            if (size < (double)hostBlockSize) return 1u;
+            w = std::min<uint32_t>(w, (uint32_t)std::max(1.0, std::floor((8192.0 - size) / (double)hostBlockSize)));
         }
     }
     return w;

@@ -302,6 +302,12 @@ private:
     // the event relay's snapshot (processQueuedEvents): records copied device-side in stream order, fetched on a stream of its own
     hipStream_t relayStream = nullptr; hipEvent_t evRelay = nullptr;
     uint8_t* dRelay = nullptr; uint8_t* hRelay = nullptr; size_t relayBytes = 0;
+    // the `fft` node's relay (fft_frames.hip): per size the window + twiddle tables on the device (made at the first setProperty that
+    // names the size, never freed before the engine), and the relay's frame descriptors + spectra, device side and pinned host side
+    void* dFftTables[13] = {};             // [log2 size]: `size` doubles of window, then `size` (re, im) double pairs
+    int  ensureFftTables(uint32_t size);
+    uint8_t* dFft = nullptr; uint8_t* hFft = nullptr; size_t fftBytes = 0;
+    uint64_t fftLaunches = 0, fftFrames = 0;   // relay launches / frames transformed since the handle was made (describe_plan)
     uint64_t relayBlocksMark = 0;          // Stats::blocksRendered at the last relay: a blockwise relay's window starts here
     // A host block longer than the engine's is k slices = k engine blocks, and the reference's nodes queue their readouts per HOST block
     // (one meter readout over all its frames, Analyzers.h:38-39): Stats::blocksRendered at the end of every host block rendered since the

@@ -269,6 +269,7 @@ __device__ __forceinline__ void run_task(const Ctx& c, const TaskU& t, uint32_t 
         case OP_METER:    for_members(c, t, [&](const Member& m) { run_meter(c, m, 0, c.n); }); return;
         case OP_SNAPSHOT: for_members(c, t, [&](const Member& m) { run_snapshot(c, m, 0, c.n); }); return;
         case OP_SCOPE:    for_members(c, t, [&](const Member& m) { run_scope(c, m, 0, c.n); }); return;
+        case OP_FFT:      for_members(c, t, [&](const Member& m) { run_fft(c, m, 0, c.n); }); return;
         case OP_CAPTURE:  for_members(c, t, [&](const Member& m) { run_capture(c, m, 0, c.n); }); return;
         case OP_PHASOR: case OP_SPHASOR: case OP_COUNTER: case OP_ACCUM: case OP_LATCH: case OP_MAXHOLD: case OP_ONCE:
         case OP_SEQ: case OP_SEQ2: case OP_SPARSEQ: case OP_SAMPLE: case OP_MCSAMPLE: case OP_POLE: case OP_ENV: case OP_BIQUAD: case OP_MM1P: case OP_SVF: case OP_SVFSHELF:

@@ -985,6 +985,7 @@ __device__ __forceinline__ void run_snapshot(const Ctx& c, const Member& m, uint
 
 // ScopeNode (Analyzers.h:175-190) + MultiChannelRingBuffer::write (:34-59): pass-through of input 0, up to four
 // inputs appended to the node's device ring; an overrun nudges the read position past the write position.
+template <uint32_t MaxCh = 4u>
 __device__ __forceinline__ void run_scope(const Ctx& c, const Member& m, uint32_t s0, uint32_t s1) {
     const uint32_t nin = member_nin(c, m);
     if (nin < 1) return zero_fill(c, m, s0, s1);
@@ -992,7 +993,7 @@ __device__ __forceinline__ void run_scope(const Ctx& c, const Member& m, uint32_
     gfp ring = rec_ptr(r, rec::SCP_RING);
     const uint32_t cap = 8192u, mask = cap - 1u, n = s1 - s0;
     const uint32_t w = r[rec::SCP_WRITE], rd = r[rec::SCP_READ];
-    const uint32_t chans = min(nin, 4u);
+    const uint32_t chans = min(nin, MaxCh);
     for (uint32_t ch = 0; ch < chans; ++ch) {
         const uint32_t o = opnd_uniform(c, m, ch);
         for (uint32_t i = s0 + c.lane; i < s1; i += 64) {
@@ -1008,6 +1009,10 @@ __device__ __forceinline__ void run_scope(const Ctx& c, const Member& m, uint32_
         r[rec::SCP_READ] = n >= freeSlots ? ((nw + 1u) & mask) : rd;
     }
 }
+
+// FFTNode::process (wasm/FFT.h:74-90): pass-through of input 0, which is also appended to the node's ONE-channel ring — the scope's
+// ring write at one channel (no input: zeros out, nothing written). The transform happens at the relay (fft_frames.hip).
+__device__ __forceinline__ void run_fft(const Ctx& c, const Member& m, uint32_t s0, uint32_t s1) { run_scope<1u>(c, m, s0, s1); }
 
 // CaptureNode (Capture.h:21-58): pass-through of input 1; while the gate (input 0) is non-zero its samples are recorded. The
 // reference collects them in a 128-frame scratch it appends to its ring when full or when the gate falls (MultiChannelRingBuffer

@@ -208,7 +208,7 @@ template <class T>
 __device__ __forceinline__ void spec_task(const Ctx& c, uint32_t off) {
     constexpr uint32_t op = T::opcode, count = T::count;
     if constexpr (op == OP_RAND || op == OP_Z || op == OP_SDELAY || op == OP_DELAY || op == OP_SAMPLESEQ ||
-                  op == OP_METER || op == OP_SNAPSHOT || op == OP_SCOPE || op == OP_CAPTURE) {
+                  op == OP_METER || op == OP_SNAPSHOT || op == OP_SCOPE || op == OP_CAPTURE || op == OP_FFT) {
         static_for<0, (int)count>([&](auto K) {
             const Member m = T::template member<K.value>(c, off);
             if constexpr (op == OP_RAND) run_rand(c, m, 0, c.n);
@@ -219,6 +219,7 @@ __device__ __forceinline__ void spec_task(const Ctx& c, uint32_t off) {
             else if constexpr (op == OP_METER) run_meter(c, m, 0, c.n);
             else if constexpr (op == OP_SNAPSHOT) run_snapshot(c, m, 0, c.n);
             else if constexpr (op == OP_CAPTURE) run_capture(c, m, 0, c.n);
+            else if constexpr (op == OP_FFT) run_fft(c, m, 0, c.n);
             else run_scope(c, m, 0, c.n);
         });
     } else if constexpr (op == OP_PHASOR || op == OP_SPHASOR || op == OP_COUNTER || op == OP_ACCUM || op == OP_LATCH || op == OP_MAXHOLD ||

@@ -533,7 +533,7 @@ bool PlanBuilder::levelTables() {
         p.roots.push_back(RootEntry{r->rec, x.hbm});
         p.rootIds.push_back(r->id);
         for (int k : seqNodes[s]) if (ni[k].n->op == OP_TAPOUT) p.taps.push_back(TapEntry{ni[k].n->rec, r->rec});
-        for (int k : seqNodes[s]) if (ni[k].n->op == OP_METER || ni[k].n->op == OP_SNAPSHOT || ni[k].n->op == OP_SCOPE || ni[k].n->op == OP_CAPTURE) p.eventNodes.push_back({ni[k].n->id, r->id});
+        for (int k : seqNodes[s]) if (ni[k].n->op == OP_METER || ni[k].n->op == OP_SNAPSHOT || ni[k].n->op == OP_SCOPE || ni[k].n->op == OP_CAPTURE || ni[k].n->op == OP_FFT) p.eventNodes.push_back({ni[k].n->id, r->id});
     }
     return true;
 }
@@ -845,6 +845,7 @@ std::string Engine::describePlan() {
         s += b;
     }
     kv("sync_poll", syncPoll ? 1 : 0); kv("sync_polls", syncPolls); kv("sync_poll_fallbacks", syncPollFallbacks);
+    kv("fft_launches", fftLaunches); kv("fft_frames", fftFrames);
     kv("resident", residentOpt ? 1 : 0); kv("resident_launches", st.residentLaunches); kv("resident_blocks", st.residentBlocks);
     kv("conv_direct_io_sets", convDirectSets); kv("conv_long_sets", convLongSets); kv("conv_long", convLong ? 1 : 0); kv("conv_max_long_tap_rows", convMaxQp);
     kv("num_taps", p.taps.size()); kv("taps_in_sets", p.tapsInSets ? 1 : 0); kv("num_tap_nodes", p.taps.size() + p.tapPairs.size()); kv("num_convs", p.convs.size()); kv("conv_workgroups", p.convWork.size());

@@ -91,6 +91,10 @@ def scope(props: Dict[str, Any], *args: ElemNode) -> NodeRepr:
     return _n("scope", props, *args)
 
 
+def fft(props: Dict[str, Any], x: ElemNode) -> NodeRepr:
+    return _n("fft", props, x)
+
+
 def snapshot(props: Dict[str, Any], trigger: ElemNode, x: ElemNode) -> NodeRepr:
     return _n("snapshot", props, trigger, x)
 

@@ -166,8 +166,10 @@ int  elemhip_process_queued_events(elemhip_t*, elemhip_event_cb cb, void* user);
  * last relay, in block order, nodes in render order inside a block — reconstructed from per-block readout logs the kernels keep
  * (builtins/Analyzers.h:23-62, 83-131: `meter` queues one readout per block, `snapshot` one per latch; a per-block relay hands on the
  * newest of each block). Exact while no more than elemhip_event_window_blocks() blocks pass between two relays (1024 for meter /
- * snapshot; less with a `scope` — its 8192-frame ring must not overrun inside a window — and 1 with a `capture` node, whose take
- * belongs to the block in which the gate fell). Neither relay holds up a render thread: the readouts are snapshotted in stream order
+ * snapshot; less with a `scope` or an `fft` — their 8192-frame rings must not overrun inside a window: floor((8191 - size) / block)
+ * blocks for a scope, floor((8192 - size) / block) for an fft, 1 when `size` is below the block — and 1 with a `capture` node, whose
+ * take belongs to the block in which the gate fell). An `fft` node's frames are transformed on the GPU, all frames of a relay in one
+ * launch on the relay's stream, and arrive as ("fft", {"source":name|null,"data":{"real":[size/2+1],"imag":[size/2+1]}}). Neither relay holds up a render thread: the readouts are snapshotted in stream order
  * and fetched on a stream of their own (runtime/elem/Runtime.h:437-446 drains lock-free queues). */
 int  elemhip_process_queued_events_blockwise(elemhip_t*, elemhip_event_cb cb, void* user);
 uint32_t elemhip_event_window_blocks(elemhip_t*);
