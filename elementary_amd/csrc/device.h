@@ -272,8 +272,10 @@ enum : uint32_t {
     // after EVERY block (offline-renderer/index.ts:112-120); the log lets a host that rendered a whole launch set do the same afterwards.
     EVT_LOG = P0, EVT_LOGMASK = P2, EVT_BLK = 11, EVT_LOGN = 12,
     // scope: device ring [4 channels][8192] (MultiChannelRingBuffer.h), write / read positions shared with the host relay
-    // (fft: the same three dwords, one channel)
-    SCP_RING = P0, SCP_WRITE = 8, SCP_READ = 9,
+    // (fft: the same dwords, one channel). The ring's capacity is SCP_MASK + 1 frames per channel: 8192, or — option
+    // "event_history_blocks" — enough for a whole relay window; sample k of a block lands at (SCP_ABS + k) & SCP_MASK, SCP_ABS = frames
+    // written so far (mod 2^32). SCP_WRITE / SCP_READ stay the reference's positions mod 8192 (at mask 8191 SCP_ABS & 8191 == SCP_WRITE).
+    SCP_RING = P0, SCP_MASK = P2, SCP_WRITE = 8, SCP_READ = 9, SCP_ABS = 10,
     // sample (Sample.h:22-231): buffer, length, new-buffer flag, mode (0 trigger, 1 gate, 2 loop), offsets, gain smoothing alpha;
     // state: change detector, current reader, two readers {target gain, gain, pos (double)}
     SMP_BUF = P0, SMP_LEN = P2, SMP_PENDING = P3, SMP_MODE = P4, SMP_START = P5, SMP_STOP = P6, SMP_ALPHA = P7,

@@ -12,9 +12,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 
 #include "launch.h"
 #include "fft_frames.h"
+#include "event_replay.h"
 
 namespace elemhip {
 
@@ -664,13 +666,16 @@ int Engine::createNode(int32_t id, const std::string& type) {   // Runtime.h:293
     } else if (nn.op == OP_METER || nn.op == OP_SNAPSHOT) {                       // per-block readout log (device.h EVT_LOG): 1024 entries of 4 dwords
         rc = allocRing(nn, (size_t)kEventLogEntries * 4u);
         if (rc == kOk) { writeParamPtr(nn, rec::EVT_LOG, nn.ring.ptr); writeParam(nn, rec::EVT_LOGMASK, kEventLogEntries - 1u); }
-    } else if (nn.op == OP_SCOPE) {                                               // Analyzers.h:145: MultiChannelRingBuffer(4) x 8192
-        rc = allocRing(nn, 4u * 8192u);
-        if (rc == kOk) writeParamPtr(nn, rec::SCP_RING, nn.ring.ptr);
-    } else if (nn.op == OP_FFT) {                                                 // wasm/FFT.h:20: MultiChannelRingBuffer(1) x 8192
-        rc = allocRing(nn, 8192u);
-        if (rc == kOk) writeParamPtr(nn, rec::SCP_RING, nn.ring.ptr);
-        if (rc == kOk) rc = ensureFftTables(1024u);
+    } else if (nn.op == OP_SCOPE || nn.op == OP_FFT) {   // Analyzers.h:145: MultiChannelRingBuffer(4) x 8192; wasm/FFT.h:20: MultiChannelRingBuffer(1) x 8192
+        // Option "event_history_blocks" = W: the device ring keeps W host blocks + 8192 frames. An event of the last block of a W-block
+        // relay window reaches back at most 8191 frames before the window's first frame (event_replay.h), so every frame a per-block
+        // relay would have handed on is still there after the window. The reference's positions stay mod 8192 (device.h SCP_MASK).
+        // (a ring is kept to 2^24 frames per channel, 64 MB: a host block so long that fewer than W fit gets the window that does)
+        nn.historyBlocks = (uint32_t)std::min<size_t>(eventHistoryBlocks, (((size_t)1 << 24) - evr::kRefRing) / (size_t)std::max(1, hostBlockSize));
+        nn.ringFrames = nn.historyBlocks ? (uint32_t)bitceil((int)((size_t)nn.historyBlocks * (size_t)hostBlockSize + evr::kRefRing)) : evr::kRefRing;
+        rc = allocRing(nn, (size_t)(nn.op == OP_SCOPE ? 4u : 1u) * nn.ringFrames);
+        if (rc == kOk) { writeParamPtr(nn, rec::SCP_RING, nn.ring.ptr); writeParam(nn, rec::SCP_MASK, nn.ringFrames - 1u); }
+        if (rc == kOk && nn.op == OP_FFT) rc = ensureFftTables(1024u);
     } else if (nn.op == OP_CAPTURE && !nn.mc) {                                   // Capture.h:17: ringBuffer(1, bitceil(sr)); (mc.capture: at commit)
         const size_t cap = (size_t)bitceil((int)(size_t)sampleRate);
         rc = allocRing(nn, cap);
@@ -1291,13 +1296,17 @@ int Engine::processQueuedEvents(void (*cb)(const char*, const char*, void*), voi
         return src;
     };
     // a stretch [from, from + count) of a device ring of `cap` entries of `entryFloats` floats each, wrapped, into `dst`
-    auto fetchRing = [&](const float* base, uint32_t cap, uint32_t from, uint32_t count, uint32_t entryFloats, float* dst) -> bool {
+    // (Async: queued on the relay's stream, the caller synchronises once behind all its stretches)
+    auto fetchRingAsync = [&](const float* base, uint32_t cap, uint32_t from, uint32_t count, uint32_t entryFloats, float* dst) -> bool {
         if (!count) return true;
         from %= cap;
         const uint32_t first = std::min(count, cap - from);
         if (hipMemcpyAsync(dst, base + (size_t)from * entryFloats, (size_t)first * entryFloats * 4, hipMemcpyDeviceToHost, relayStream) != hipSuccess) return false;
         if (count > first && hipMemcpyAsync(dst + (size_t)first * entryFloats, base, (size_t)(count - first) * entryFloats * 4, hipMemcpyDeviceToHost, relayStream) != hipSuccess) return false;
-        return hipStreamSynchronize(relayStream) == hipSuccess;
+        return true;
+    };
+    auto fetchRing = [&](const float* base, uint32_t cap, uint32_t from, uint32_t count, uint32_t entryFloats, float* dst) -> bool {
+        return fetchRingAsync(base, cap, from, count, entryFloats, dst) && hipStreamSynchronize(relayStream) == hipSuccess;
     };
     struct Ev { uint64_t block; uint32_t order; const char* type; std::string json; };
     std::vector<Ev> evs;
@@ -1312,42 +1321,64 @@ int Engine::processQueuedEvents(void (*cb)(const char*, const char*, void*), voi
     const uint64_t hostBlocks = sliced ? hostEnds.size() : windowBlocks;            // host blocks in the window
     const uint64_t lastBlock = hostBlocks ? hostBlocks - 1 : 0;
     const uint32_t hostFrames = (uint32_t)hostBlockSize;
+    // ---- scope / fft rings: the reads of this relay (event_replay.h). emit(host block of the window, absolute index of the frame's
+    // first sample); the frame's samples sit at that index, wrapped, in the device ring of n.ringFrames frames per channel. ----
+    // plain relay: ONE read at the positions the device kept — no relay came in between, so its overrun nudges are the reference's.
+    // blockwise:   the device's read position is NOT what a relay after every block would have left (the kernel never saw the reads in
+    //   between): the window is replayed from the positions the previous relay established, kept on the host per node — write rule,
+    //   then the read comparison, per HOST block — and the final read position goes back to the device. A frame the device ring no
+    //   longer holds (a window longer than eventWindowBlocks()) is dropped rather than handed on with newer samples in it.
+    auto ringReads = [&](Node& n, const uint32_t* rc_, uint32_t size, evr::Cmp cmp, const std::function<void(uint64_t, uint64_t)>& emit) {
+        const uint32_t fresh = rc_[rec::SCP_ABS] - (uint32_t)n.ringWritten;      // frames written since the last relay
+        const uint64_t writtenEnd = n.ringWritten + fresh;
+        evr::Pos p;
+        if (!blockwise) {
+            p.written = writtenEnd; p.read = rc_[rec::SCP_READ];
+            uint64_t first;
+            if (evr::read_frame(p, size, cmp, first) && emit) emit(lastBlock, first);
+        } else {
+            p.written = n.ringWritten; p.read = n.ringRead;
+            // whole host blocks; what does not fit the window's count (blocks rendered while the node's root was off, a short first
+            // call) was written with no relay behind it
+            uint64_t blocks = fresh / hostFrames;
+            if (fresh % hostFrames) evr::write_block(p, fresh % hostFrames);
+            for (; blocks > std::max<uint64_t>(1, hostBlocks); --blocks) evr::write_block(p, hostFrames);
+            const uint64_t firstBlock = lastBlock + 1 >= blocks ? lastBlock + 1 - blocks : 0;
+            p = evr::replay(p, hostFrames, size, cmp, (uint32_t)blocks, [&](uint32_t b, uint64_t first) {
+                if (emit && writtenEnd - first <= (uint64_t)n.ringFrames) emit(std::min<uint64_t>(lastBlock, firstBlock + b), first);
+            });
+        }
+        n.ringWritten = p.written; n.ringRead = p.read;
+        if (p.read != rc_[rec::SCP_READ]) writeBack.push_back({&n, rec::SCP_READ, p.read});
+    };
     // ---- fft nodes (wasm/FFT.h:92-132): what every node hands on in this window, then ONE launch for all frames ----
     // A relay emits at most one frame per node (`ringBuffer.size() >= size`, where scope has `>`); the blockwise relay replays that
-    // comparison after every host block of the window, as the scope branch below does. The kernel reads the rings where the snapshot
-    // says they are readable and writes into the relay's own buffer, on the relay's stream: the render thread is not involved.
+    // comparison after every host block of the window (ringReads), as the scope branch below does: up to a frame per node and block,
+    // all of them in ONE launch. The kernel reads the rings where the replay says the frames are and writes into the relay's own
+    // buffer, on the relay's stream: the render thread is not involved.
     struct FftEmit { uint64_t block; size_t outFloat; };
     std::vector<std::vector<FftEmit>> fftEmits(items.size());
     {
         std::vector<FftFrame> frames;
         size_t outFloats = 0;
+        uint32_t maxSize = 0;
         for (size_t ix = 0; ix < items.size(); ++ix) {
             Node& n = *items[ix].n;
             if (n.op != OP_FFT) continue;
             const uint32_t* rc_ = reinterpret_cast<const uint32_t*>(hRelay + items[ix].recOff);
             auto q = n.props.find("size");
             const uint32_t size = (q != n.props.end() && q->second.isNumber()) ? (uint32_t)q->second.num : 1024u;
-            const uint32_t cap = 8192u, mask = cap - 1u;
             uint32_t lg = 0;
             while ((1u << lg) < size) ++lg;
-            // (the ring never holds more than cap - 1 frames: size 8192 never fires, FFT.h:96 with MultiChannelRingBuffer.h:99-110)
-            if (!n.ring.ptr || !ffr::size_ok(size) || !dFftTables[lg]) continue;
-            const uint32_t wEnd = rc_[rec::SCP_WRITE];
-            uint32_t r = rc_[rec::SCP_READ];
-            const uint64_t steps = blockwise ? std::max<uint64_t>(1, std::min<uint64_t>(hostBlocks, (cap - 1) / hostFrames)) : 1;
-            bool any = false;
-            for (uint64_t s_ = 0; s_ < steps; ++s_) {
-                const uint32_t w = (wEnd - (uint32_t)((steps - 1 - s_) * (uint64_t)hostFrames)) & mask;
-                const uint32_t full = w > r ? w - r : ((cap - (r - w)) & mask);
-                if (!(full >= size)) continue;
-                const double* tab = static_cast<const double*>(dFftTables[lg]);
-                frames.push_back(FftFrame{static_cast<const float*>(n.ring.ptr), tab, tab + size, nullptr, r, size});
-                fftEmits[ix].push_back({lastBlock - std::min<uint64_t>(lastBlock, steps - 1 - s_), outFloats});
+            // (the ring never holds more than 8191 frames: size 8192 never fires, FFT.h:96 with MultiChannelRingBuffer.h:99-110)
+            if (!n.ring.ptr || !ffr::size_ok(size) || !dFftTables[lg]) { ringReads(n, rc_, size, evr::kAtLeast, nullptr); continue; }
+            const double* tab = static_cast<const double*>(dFftTables[lg]);
+            ringReads(n, rc_, size, evr::kAtLeast, [&](uint64_t block, uint64_t first) {
+                frames.push_back(FftFrame{static_cast<const float*>(n.ring.ptr), tab, tab + size, nullptr, (uint32_t)(first & (n.ringFrames - 1u)), size, n.ringFrames - 1u, 0u});
+                fftEmits[ix].push_back({block, outFloats});
                 outFloats += (size_t)size + 2u;
-                r = (r + size) & mask;
-                any = true;
-            }
-            if (any) writeBack.push_back({&n, rec::SCP_READ, r});
+                maxSize = std::max(maxSize, size);
+            });
         }
         if (!frames.empty()) {
             const size_t descBytes = (frames.size() * sizeof(FftFrame) + 255u) & ~(size_t)255u, need = descBytes + outFloats * 4u;
@@ -1364,7 +1395,7 @@ int Engine::processQueuedEvents(void (*cb)(const char*, const char*, void*), voi
             for (FftFrame& f : frames) { f.out = reinterpret_cast<float*>(dFft + descBytes) + at; at += (size_t)f.size + 2u; }
             std::memcpy(hFft, frames.data(), frames.size() * sizeof(FftFrame));
             HIP_OK(hipMemcpyAsync(dFft, hFft, frames.size() * sizeof(FftFrame), hipMemcpyHostToDevice, relayStream));
-            HIP_OK(launch_fft_frames(relayStream, reinterpret_cast<const FftFrame*>(dFft), (uint32_t)frames.size()));
+            HIP_OK(launch_fft_frames(relayStream, reinterpret_cast<const FftFrame*>(dFft), (uint32_t)frames.size(), maxSize));
             HIP_OK(hipMemcpyAsync(hFft + descBytes, dFft + descBytes, outFloats * 4u, hipMemcpyDeviceToHost, relayStream));
             HIP_OK(hipStreamSynchronize(relayStream));
             fftLaunches++; fftFrames += frames.size();
@@ -1394,38 +1425,43 @@ int Engine::processQueuedEvents(void (*cb)(const char*, const char*, void*), voi
         if (n.op == OP_SCOPE) {                                           // Analyzers.h:192-245, MultiChannelRingBuffer.h:61-86
             auto numOr = [&](const char* k, double dflt) { auto q = n.props.find(k); return (q != n.props.end() && q->second.isNumber()) ? q->second.num : dflt; };
             const size_t size = (size_t)numOr("size", 512.0), channels = std::min<size_t>(4, (size_t)numOr("channels", 1.0));
-            const uint32_t cap = 8192u, mask = cap - 1u;
-            const uint32_t wEnd = rc_[rec::SCP_WRITE];
-            uint32_t r = rc_[rec::SCP_READ];
-            if (!n.ring.ptr || size == 0 || size >= cap) continue;
-            // blockwise: the write position after each block of the window (whole blocks of blockSize frames), oldest first
-            const uint64_t steps = blockwise ? std::max<uint64_t>(1, std::min<uint64_t>(hostBlocks, (cap - 1) / hostFrames)) : 1;
-            std::vector<std::pair<uint64_t, uint32_t>> emits;            // (host block, read position of the emitted frame)
-            for (uint64_t s_ = 0; s_ < steps; ++s_) {
-                const uint32_t w = (wEnd - (uint32_t)((steps - 1 - s_) * (uint64_t)hostFrames)) & mask;
-                const uint32_t full = w > r ? w - r : ((cap - (r - w)) & mask);
-                if (!(full > size)) continue;
-                emits.emplace_back(lastBlock - std::min<uint64_t>(lastBlock, steps - 1 - s_), r);
-                r = (uint32_t)((r + size) & mask);
-            }
+            if (!n.ring.ptr || size == 0) continue;
+            if (size >= evr::kRefRing) { ringReads(n, rc_, (uint32_t)size, evr::kMoreThan, nullptr); continue; }   // (never fires: the ring holds 8191 at most)
+            struct Emit { uint64_t block, first; size_t run; };
+            std::vector<Emit> emits;
+            // the frames to fetch, as runs of absolute frame indices: consecutive emits are contiguous until an overrun skips frames; a
+            // gap shorter than a copy is worth (kGap frames = 16 KB per channel) is fetched along rather than split off
+            struct Run { uint64_t first, frames; size_t at; };
+            std::vector<Run> runs;
+            constexpr uint64_t kGap = 4096;
+            ringReads(n, rc_, (uint32_t)size, evr::kMoreThan, [&](uint64_t block, uint64_t first) {
+                if (runs.empty() || first < runs.back().first || first > runs.back().first + runs.back().frames + kGap) runs.push_back({first, 0, 0});
+                Run& run = runs.back();
+                run.frames = std::max<uint64_t>(run.frames, first + size - run.first);
+                emits.push_back({block, first, runs.size() - 1});
+            });
             if (emits.empty()) continue;
-            const uint32_t r0 = emits.front().second, span = (uint32_t)(emits.size() * size);
+            size_t span = 0;
+            for (Run& run : runs) { run.at = span; span += (size_t)run.frames; }
             std::vector<float> host((size_t)channels * span);
+            const uint32_t cap = n.ringFrames;
             bool ok = true;
-            for (size_t ch = 0; ch < channels && ok; ++ch) ok = fetchRing((const float*)n.ring.ptr + ch * cap, cap, r0, span, 1, host.data() + ch * span);
-            if (!ok) return kHipError;
+            for (size_t ch = 0; ch < channels && ok; ++ch)
+                for (const Run& run : runs)
+                    if (!(ok = fetchRingAsync((const float*)n.ring.ptr + ch * cap, cap, (uint32_t)(run.first & (cap - 1u)), (uint32_t)run.frames, 1, host.data() + ch * span + run.at))) break;
+            if (!ok || hipStreamSynchronize(relayStream) != hipSuccess) return kHipError;
             const std::string src = srcOf(n);
-            for (size_t e = 0; e < emits.size(); ++e) {
+            for (const Emit& e : emits) {
+                const size_t at = runs[e.run].at + (size_t)(e.first - runs[e.run].first);
                 std::string j = "{\"source\": " + src + ", \"data\": [";
                 for (size_t ch = 0; ch < channels; ++ch) {
                     j += ch ? ", [" : "[";
-                    for (size_t i = 0; i < size; ++i) { if (i) j += ", "; j += numStr(host[ch * span + e * size + i]); }
+                    for (size_t i = 0; i < size; ++i) { if (i) j += ", "; j += numStr(host[ch * span + at + i]); }
                     j += "]";
                 }
                 j += "]}";
-                evs.push_back({emits[e].first, it.order, "scope", std::move(j)});
+                evs.push_back({e.block, it.order, "scope", std::move(j)});
             }
-            writeBack.push_back({&n, rec::SCP_READ, r});
             continue;
         }
         if (n.op == OP_CAPTURE) {                                         // Capture.h:60-95 / mc/Capture.h:107-146: drain the ring(s) into the relay, emit once the gate fell
@@ -1527,8 +1563,9 @@ int Engine::processQueuedEvents(void (*cb)(const char*, const char*, void*), voi
 }
 
 // How many blocks may pass between two blockwise relays for their result to be exactly the per-block relay's: the per-block
-// readout logs hold 1024 blocks; a scope or fft ring (8192 frames, `size` of them per event) must not overrun inside a window; a
-// capture node's take is placed by the relay that sees its gate fall, so it wants a relay per block.
+// readout logs hold 1024 blocks; a scope or fft ring of 8192 frames (`size` of them per event) must not overrun inside a window — one
+// made with history (option "event_history_blocks" = W) serves W blocks; a capture node's take is placed by the relay that sees its
+// gate fall, so it wants a relay per block.
 uint32_t Engine::eventWindowBlocks() {
     std::lock_guard<std::mutex> control(ctl);
     RenderGuard lock(*this);
@@ -1542,6 +1579,9 @@ uint32_t Engine::eventWindowBlocks() {
         if (nit == nodes.end()) continue;
         const Node& n = nit->second;
         if (n.op == OP_CAPTURE) return 1u;
+        // a ring with history (option "event_history_blocks") holds every frame a per-block relay hands on over that many blocks, and
+        // the relay replays the reads: whatever `size`, overruns included
+        if ((n.op == OP_SCOPE || n.op == OP_FFT) && n.historyBlocks) { w = std::min(w, n.historyBlocks); continue; }
         if (n.op == OP_SCOPE) {
             auto q = n.props.find("size");
             const double size = (q != n.props.end() && q->second.isNumber()) ? q->second.num : 512.0;
@@ -1735,6 +1775,9 @@ int Engine::setOption(const std::string& key, double value) {
     if (key == "conv_mfma") { convMfma = std::max(0, std::min(1, (int)value)); return kOk; }   // partition MAC of launch sets: 1 matrix cores (default), 0 packed vector FMAs
     if (key == "skip_idle_launches") { skipIdleLaunches = value != 0; dropGraphs(); return kOk; }
     if (key == "spec_blocks") { specBlocks = value != 0; return kOk; }      // elemhip_process through the specialised kernels when it can
+    // relay window (host blocks) the device rings of scope / fft nodes made FROM NOW ON keep: their blockwise relay stays exact over that
+    // many blocks, ring overruns included (0: the reference's 8192 frames, windows as short as one block). Older nodes keep their ring.
+    if (key == "event_history_blocks") { eventHistoryBlocks = (uint32_t)std::max(0, std::min((int)kEventLogEntries, (int)value)); return kOk; }
     if (key == "batch_blocks") { batchBlocks = std::max(1, std::min(1024, (int)value)); return kOk; }      // blocks per multi-block launch (1 = off)
     if (key == "debug_build_delay_ms") { debugBuildDelayMs = std::max(0, (int)value); return kOk; }   // tests: stretches the unlocked part of a plan build
     if (key == "plan_cache") { planCache = std::max(0, std::min(2, (int)value)); islandCache.clear(); islandShapeCache.clear(); return kOk; }

@@ -89,6 +89,11 @@ struct Node {
     ResourcePtr res;            // tap buffer / sample data held by the node
     uint32_t eventCount = 0;    // meter / snapshot: readouts already relayed by processQueuedEvents
     uint32_t logRelayed = 0;    // snapshot: entries of the per-block readout log already relayed
+    // scope / fft: the reference's ring positions as the last relay left them (event_replay.h: frames written, read position) — a
+    // blockwise relay replays the window's per-block reads from here; frames of the device ring per channel; the relay window
+    // (host blocks) the ring was sized for by option "event_history_blocks" when the node was made (0: the plain 8192-frame ring)
+    uint64_t ringWritten = 0;
+    uint32_t ringRead = 0, ringFrames = 8192, historyBlocks = 0;
     uint32_t convSlices = 1;    // convolve: helper slices its current impulse response wants (conv.hip)
     uint32_t convQp = 0, convHistBlocks = 0, convP = 0;   // convolve: long-partition tap rows (0: none), blocks of its input ring, 512-partitions (conv_long.inc)
     bool mc = false;            // multi-output node (mc.*): one record per output channel, planned as one entry per channel
@@ -216,6 +221,8 @@ public:
     uint32_t eventWindowBlocks();          // blocks a blockwise relay window may span and still be exact for the newest plan's event nodes
     void setStream(hipStream_t s);
     const Stats& stats() const { return st; }
+    uint64_t fftLaunchCount() const { return fftLaunches; }     // launches of the fft relay kernel / frames they transformed
+    uint64_t fftFrameCount() const { return fftFrames; }
     // dry-engine introspection for host-logic tests: adopt the pending plan and describe it as JSON
     std::string describePlan();
     int setOption(const std::string& key, double value);
@@ -307,6 +314,7 @@ private:
     void* dFftTables[13] = {};             // [log2 size]: `size` doubles of window, then `size` (re, im) double pairs
     int  ensureFftTables(uint32_t size);
     uint8_t* dFft = nullptr; uint8_t* hFft = nullptr; size_t fftBytes = 0;
+    uint32_t eventHistoryBlocks = 0;   // option "event_history_blocks": relay window (host blocks) the rings of NEW scope / fft nodes keep (0: off)
     uint64_t fftLaunches = 0, fftFrames = 0;   // relay launches / frames transformed since the handle was made (describe_plan)
     uint64_t relayBlocksMark = 0;          // Stats::blocksRendered at the last relay: a blockwise relay's window starts here
     // A host block longer than the engine's is k slices = k engine blocks, and the reference's nodes queue their readouts per HOST block

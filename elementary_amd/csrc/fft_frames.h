@@ -5,8 +5,8 @@
 // The arithmetic is DOUBLE, the result rounded to float once, at the store. The reference's transform (audiofft, Ooura backend)
 // works in double and rounds to float as well: its recorded spectra sit within half a float ulp of the exact DFT, and the event
 // tolerance is twice that. The first build of this core ran fft4096.h's float butterflies and missed it by 3.5x (size 256:
-// 8.2e-7 against a float64 DFT where the reference has 2.4e-7). A relay transforms at most 31 frames per node, and the MI355X's
-// fp64 vector rate is half its fp32 rate: the cost is LDS (16 bytes per point), not time.
+// 8.2e-7 against a float64 DFT where the reference has 2.4e-7). The MI355X's fp64 vector rate is half its fp32 rate: the cost is
+// LDS (16 bytes per point), not time — and a launch asks for the LDS of its LARGEST frame only (fft_frames.hip).
 //
 // Written against plain pointers, as fft4096.h is, so that the same code runs on the device (buffers = LDS, one call per thread,
 // __syncthreads between the phases) and on the host (tests/native/fft_frames_host.cpp emulates the kThreads threads phase by
@@ -58,7 +58,8 @@ LFFT_FD void dft16(c2 (&v)[16]) {
 constexpr uint32_t kThreads = 128;                // M / 16 butterflies of the largest transform
 constexpr uint32_t kMaxM = 2048;
 constexpr uint32_t kBuf = kMaxM + kMaxM / 16;     // one padded buffer (c2 elements of 16 bytes); the transform uses two: 68 KB of LDS
-constexpr uint32_t kRing = 8192;                  // frames of the node's ring (MultiChannelRingBuffer.h:17)
+LFFT_FD constexpr uint32_t buf_stride(uint32_t size) { return size / 2u + size / 32u; }   // ... of a size-`size` frame: pad(M - 1) < M + M / 16
+constexpr uint32_t kRing = 8192;                  // frames of the reference's ring (MultiChannelRingBuffer.h:17), the default capacity
 
 LFFT_FD bool size_ok(uint32_t size) { return size == 256u || size == 512u || size == 1024u || size == 2048u || size == 4096u; }
 
@@ -77,12 +78,13 @@ template <> LFFT_FD void dft<8>(c2 (&v)[8]) {
 }
 template <> LFFT_FD void dft<16>(c2 (&v)[16]) { dft16(v); }
 
-// ---- load: frame samples [read, read + 2 M) of the ring (wrapped), times the window in double, rounded to FLOAT as the reference
-// hands them to its transform (FFT.h:114-120 with FloatType = double), packed as z[n] = x[2n] + i x[2n + 1] ----
+// ---- load: frame samples [read, read + 2 M) of the ring (wrapped at `mask` + 1 frames: 8192, or the longer history ring of a node
+// made under "event_history_blocks"), times the window in double, rounded to FLOAT as the reference hands them to its transform
+// (FFT.h:114-120 with FloatType = double), packed as z[n] = x[2n] + i x[2n + 1] ----
 template <uint32_t M>
-LFFT_FD void load_frame(const float* ring, uint32_t read, const double* win, c2* a, uint32_t tid) {
+LFFT_FD void load_frame(const float* ring, uint32_t read, const double* win, c2* a, uint32_t tid, uint32_t mask = kRing - 1u) {
     for (uint32_t n = tid; n < M; n += kThreads) {
-        const float x0 = ring[(read + 2u * n) & (kRing - 1u)], x1 = ring[(read + 2u * n + 1u) & (kRing - 1u)];
+        const float x0 = ring[(read + 2u * n) & mask], x1 = ring[(read + 2u * n + 1u) & mask];
         a[pad(n)] = mk((double)(float)((double)x0 * win[2u * n]), (double)(float)((double)x1 * win[2u * n + 1u]));
     }
 }

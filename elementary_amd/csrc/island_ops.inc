@@ -991,15 +991,19 @@ __device__ __forceinline__ void run_scope(const Ctx& c, const Member& m, uint32_
     if (nin < 1) return zero_fill(c, m, s0, s1);
     rup r = c.recs + m.rec * kRecDwords;
     gfp ring = rec_ptr(r, rec::SCP_RING);
+    // the reference's ring positions (mod 8192); the device ring holds SCP_MASK + 1 frames per channel — the same 8192, or a whole
+    // relay window's history (engine.cpp, event_replay.h) — and is addressed by the count of frames written so far
     const uint32_t cap = 8192u, mask = cap - 1u, n = s1 - s0;
     const uint32_t w = r[rec::SCP_WRITE], rd = r[rec::SCP_READ];
+    const uint32_t hmask = UNI(r[rec::SCP_MASK]), abs0 = UNI(r[rec::SCP_ABS]);
+    const size_t hcap = (size_t)hmask + 1u;
     const uint32_t chans = min(nin, MaxCh);
     for (uint32_t ch = 0; ch < chans; ++ch) {
         const uint32_t o = opnd_uniform(c, m, ch);
         for (uint32_t i = s0 + c.lane; i < s1; i += 64) {
             const float x = fetch(c, o, i);
             if (ch == 0u) put(c, m, i, x);
-            if (ring) ring[ch * cap + ((w + i - s0) & mask)] = x;
+            if (ring) ring[ch * hcap + ((abs0 + i - s0) & hmask)] = x;
         }
     }
     if (c.lane == 0 && n > 0) {
@@ -1007,6 +1011,7 @@ __device__ __forceinline__ void run_scope(const Ctx& c, const Member& m, uint32_
         const uint32_t nw = (w + n) & mask;
         r[rec::SCP_WRITE] = nw;
         r[rec::SCP_READ] = n >= freeSlots ? ((nw + 1u) & mask) : rd;
+        r[rec::SCP_ABS] = abs0 + n;
     }
 }
 

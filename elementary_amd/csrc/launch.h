@@ -56,14 +56,17 @@ hipError_t upload_convolve_tables(const float* twiddleReIm, const float* twiddle
 void launch_patches(hipStream_t s, const Patch* patches, uint32_t count, uint32_t* recs, uint32_t* globals);
 // ---- the `fft` node's relay kernel (fft_frames.hip): one workgroup per frame ----
 struct FftFrame {
-    const float*  ring;        // the node's ring: 8192 floats
+    const float*  ring;        // the node's ring: mask + 1 floats
     const double* window;      // Blackman-Harris table of `size` doubles
     const double* twiddles;    // exp(-2 pi i q / size), q < size, as (re, im) pairs
     float*        out;         // receives real[size/2 + 1] | imag[size/2 + 1]
     uint32_t      read;        // ring position of the frame's first sample
     uint32_t      size;        // 256, 512, 1024, 2048 or 4096
+    uint32_t      mask;        // ring frames - 1 (8191, or the history ring of "event_history_blocks")
+    uint32_t      pad_;
 };
-hipError_t launch_fft_frames(hipStream_t s, const FftFrame* framesDev, uint32_t count);
+// `maxSize`: the largest `size` among the frames — the launch's LDS is sized by it
+hipError_t launch_fft_frames(hipStream_t s, const FftFrame* framesDev, uint32_t count, uint32_t maxSize);
 hipError_t launch_bus_sum(hipStream_t s, float* dst, const float* const* partials, uint32_t count, size_t n);   // dst = ((p0 + p1) + p2) + ... (rank order)
 
 } // namespace elemhip

@@ -20,12 +20,18 @@ class OfflineRenderer:
         self._listeners: Dict[str, list] = {}
 
     def initialize(self, num_input_channels: int = 0, num_output_channels: int = 2, sample_rate: float = 44100,
-                   block_size: int = 512, virtual_file_system: Optional[Dict[str, np.ndarray]] = None) -> None:
+                   block_size: int = 512, virtual_file_system: Optional[Dict[str, np.ndarray]] = None,
+                   event_history_blocks: int = 0) -> None:
+        """``event_history_blocks`` (no counterpart in the reference; 0 = off): engine option of the same name — `scope` and `fft`
+        nodes keep a device ring long enough for a relay window of that many blocks, so ``process`` still renders launch sets of
+        that size with such a listener attached (engines without ``set_option`` relay after every block anyway)."""
         self.num_in = int(num_input_channels)
         self.num_out = int(num_output_channels)
         self.block_size = int(block_size)
         self.sample_rate = float(sample_rate)
         self._rt = self._factory(self.sample_rate, self.block_size)
+        if event_history_blocks and hasattr(self._rt, "set_option"):
+            self._rt.set_option("event_history_blocks", int(event_history_blocks))
         self._time = 0
         for k, v in (virtual_file_system or {}).items():
             self._rt.add_shared_resource(k, v)

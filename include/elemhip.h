@@ -56,6 +56,7 @@ typedef struct elemhip_stats {
     double   last_jit_wait_ms;    /* time the last commit waited for kernel compilation (option "specialize" = 2) */
     double   last_graph_capture_ms; /* hipGraph capture + instantiate of the current plan's per-block launch sequence */
     uint64_t resident_launches, resident_blocks;   /* option "resident": launches of the resident kernel / blocks it rendered */
+    uint64_t fft_launches, fft_frames;             /* `fft` nodes: launches of the relay's transform kernel / frames they transformed */
 } elemhip_stats;
 
 /* Runtime(double sampleRate, int blockSize)                      runtime/elem/Runtime.h:44,157-166
@@ -173,6 +174,11 @@ int  elemhip_process_queued_events(elemhip_t*, elemhip_event_cb cb, void* user);
  * and fetched on a stream of their own (runtime/elem/Runtime.h:437-446 drains lock-free queues). */
 int  elemhip_process_queued_events_blockwise(elemhip_t*, elemhip_event_cb cb, void* user);
 uint32_t elemhip_event_window_blocks(elemhip_t*);
+/* elemhip_set_option(h, "event_history_blocks", W), W = 0 ... 1024 (clamped; 0 = off, the default): `scope` and `fft` nodes created
+ * AFTERWARDS keep a device ring of bitceil(W * blockSize + 8192) frames per channel instead of 8192 (4 MB per channel at W = 1024 and
+ * 512 frames), and the blockwise relay replays the reference ring's per-block reads and overrun nudges on the host: for such nodes
+ * elemhip_event_window_blocks() is min(W, 1024 / slices per block) whatever their `size` — overruns included, the events are the
+ * per-block relay's. Nodes that already exist keep their 8192-frame ring and the rule above; `capture` stays at 1. */
 
 int  elemhip_trace_level(elemhip_t*, size_t nOut, uint32_t level, unsigned long long* out, size_t cap);
 /* Debug/test hook: JSON description of the current render plan (islands, launch levels, LDS).
@@ -196,7 +202,7 @@ int  elemhip_sum_buses(int deviceOrdinal, void* hipStream, float* dst, const flo
  * waits for them), "spec_blocks" / "host_out_direct" (elemhip_process through the specialised kernels / output written straight
  * into pinned host memory), "use_graph" / "graph_blocks" (per-block launch path replayed from a hipGraph), "stateless_rows",
  * "mixer_split", "pipeline_copies", "merge_phases", "pack_islands" / "pack_max" / "cu_count" (lane-packing of isomorphic
- * islands), "profile_launches", "time_batch". Unknown keys return code 6. */
+ * islands), "event_history_blocks" (above, at elemhip_event_window_blocks), "profile_launches", "time_batch". Unknown keys return code 6. */
 int  elemhip_set_option(elemhip_t*, const char* key, double value);
 
 #ifdef __cplusplus
