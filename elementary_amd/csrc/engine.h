@@ -173,7 +173,8 @@ struct Stats {
 };
 
 struct ResidentCtl;     // launch.h
-struct RenderGuard;     // engine.cpp
+struct RenderGuard;     // engine_impl.h
+struct RelayCtx;        // engine_relay.cpp
 
 class Engine {
     friend struct RenderGuard;
@@ -316,6 +317,14 @@ private:
     uint8_t* dFft = nullptr; uint8_t* hFft = nullptr; size_t fftBytes = 0;
     uint32_t eventHistoryBlocks = 0;   // option "event_history_blocks": relay window (host blocks) the rings of NEW scope / fft nodes keep (0: off)
     uint64_t fftLaunches = 0, fftFrames = 0;   // relay launches / frames transformed since the handle was made (describe_plan)
+    // the relay's readers, one per node kind, over the context of one relay (engine_relay.cpp): they fetch off the render lock and
+    // leave events and read-position write-backs in the context
+    int  relayFftFrames(RelayCtx& c);                     // every fft node's frames of the window: collect, ONE launch ...
+    void relayFft(RelayCtx& c, size_t item);              // ... and the events of one node from its spectra
+    int  relayScope(RelayCtx& c, Node& n, const uint32_t* rec, uint32_t order);
+    int  relayCapture(RelayCtx& c, Node& n, const uint32_t* rec, uint32_t order);
+    int  relayMeter(RelayCtx& c, Node& n, const uint32_t* rec, uint32_t order);
+    int  relaySnapshot(RelayCtx& c, Node& n, const uint32_t* rec, uint32_t order);
     uint64_t relayBlocksMark = 0;          // Stats::blocksRendered at the last relay: a blockwise relay's window starts here
     // A host block longer than the engine's is k slices = k engine blocks, and the reference's nodes queue their readouts per HOST block
     // (one meter readout over all its frames, Analyzers.h:38-39): Stats::blocksRendered at the end of every host block rendered since the
@@ -421,7 +430,14 @@ private:
     int  ensureResourceChannelOnDevice(const ResourcePtr& r, uint32_t ch, const void** ptr, uint32_t* len);
     void writeParam(Node& n, uint32_t dword, uint32_t value);
     void writeParamF(Node& n, uint32_t dword, float value) { uint32_t u; memcpy(&u, &value, 4); writeParam(n, dword, u); }
-    void writeParamPtr(Node& n, uint32_t dword, const void* p);
+    void writeParamI64(Node& n, uint32_t dword, int64_t value) { writeParam(n, dword, (uint32_t)((uint64_t)value & 0xFFFFFFFFu)); writeParam(n, dword + 1, (uint32_t)((uint64_t)value >> 32)); }   // two dwords, low first
+    void writeParamF64(Node& n, uint32_t dword, double value) { int64_t i; memcpy(&i, &value, 8); writeParamI64(n, dword, i); }
+    void writeParamPtr(Node& n, uint32_t dword, const void* p) { writeParamI64(n, dword, (int64_t)reinterpret_cast<uintptr_t>(p)); }
+    void writeChannelBuffers(Node& n) { for (size_t c = 0; c < n.chanRecs.size(); ++c) writeChannelBuffer(n, (uint32_t)c + 1u, n.chanRecs[c]); }   // mc.*: channels >= 1
+    int  findResource(const Value& v, ResourcePtr& out);  // engine_nodes.cpp: a `path` property -> the shared resource it names
+    int  bindResource(Node& n, const Value& v);            // ... held by the node, channel 0 on the device
+    int  uploadRing(Node& n, const void* words, size_t count);
+    void freeRec(uint32_t rec);                            // gc: the record back to the free list, queued writes to it dropped
     int  allocRing(Node& n, size_t floats);
     int  ensureResourceOnDevice(const ResourcePtr& r);
     int  setConvolverIr(Node& n, const ResourcePtr& res);
@@ -551,5 +567,23 @@ struct Plan {
     uint32_t blockChunks = 0;               // block-at-a-time chunks rendered before the capture
     ~Plan();
 };
+
+// The record writers both the render path (setTapSlice) and the control plane call: inline, so that neither pays a call across units.
+inline void Engine::writeRec(uint32_t rec, uint32_t dword, uint32_t value) {
+    const uint32_t idx = rec * kRecDwords + dword;
+    shadow[idx] = value;
+    if (!freshFlag[rec]) patches.push_back(Patch{0u, idx, value, 0u});
+}
+
+inline void Engine::writeParam(Node& n, uint32_t dword, uint32_t value) {
+    const uint32_t idx = n.rec * kRecDwords + dword;
+    shadow[idx] = value;
+    // a record that has not been uploaded yet travels whole; otherwise patch the one dword
+    if (!freshFlag[n.rec])
+        patches.push_back(Patch{0u, idx, value, 0u});
+    // a multi-output node: every channel's record — except the buffer slots (P0..P2: pointer, length), which differ per
+    // channel and are written by writeChannelBuffer only (two patches for one dword in one flush have no order)
+    if (dword > rec::P2) for (uint32_t cr : n.chanRecs) writeRec(cr, dword, value);
+}
 
 } // namespace elemhip

@@ -1,0 +1,1288 @@
+// engine_render.cpp — the per-block launch sequence (process), launch sets (processBlocks / processBlocksHost), the resident
+// kernel's host side and the measurement calls. Everything a render call reaches lives in this unit or inline in engine.h.
+#include "engine_impl.h"
+#include <thread>
+
+namespace elemhip {
+
+// ---- block rendering ----------------------------------------------------------------------------------
+void Engine::dropGraphs() {
+    if (!current) return;
+    if (current->graphExec) { (void)hipGraphExecDestroy(current->graphExec); current->graphExec = nullptr; }
+}
+
+void Engine::freeDeferred() {   // called right after a synchronize of every stream the engine renders on (`mu` held)
+    patchCursor = 0;
+    for (void* p : deferredFree) (void)hipFree(p);
+    deferredFree.clear();
+    retiredPlans.clear();         // plans replaced since the last synchronize: their tables / hipGraphs are idle now (~Plan frees them)
+}
+
+int Engine::ensureHbm(size_t buffers) {
+    if (buffers <= hbmBuffers) return kOk;
+    size_t want = std::max(buffers, hbmBuffers * 2);
+    float* nb = nullptr;
+    // + slack: vector loads of a 64*V-frame task may read (never write) past a short block's buffer
+    const size_t floats = want * blockSize + 1024;
+    HIP_OK(hipMalloc(&nb, floats * sizeof(float)));
+    HIP_OK(hipMemsetAsync(nb, 0, floats * sizeof(float), stream));   // ordered with the kernels: they run on `stream` (non-blocking w.r.t. the null stream)
+    if (dHbm) deferredFree.push_back(dHbm);
+    dHbm = nb; hbmBuffers = want;
+    dropGraphs();
+    return kOk;
+}
+
+// Arena buffers a launch set of `blocks` blocks of plan `p` needs: one slice (host inputs + exports) per block, then the
+// stream ring of the specialised kernels, one slice per buffer set an island may keep in flight.
+size_t Engine::arenaBuffers(const Plan& p, size_t blocks) const {
+    return (size_t)p.numHbmBuffers * blocks + (size_t)p.numStreamBuffers * (size_t)p.maxCopies;
+}
+// The recurrence loops of the specialised kernels address the whole arena through 32-bit buffer offsets with the top bit
+// reserved as "out of range": a launch set stays under 2 GB of arena (C2: 0.6 MB per block).
+size_t Engine::maxSetBlocks(const Plan& p) const {
+    const size_t cap = ((size_t)1 << 29) / (size_t)blockSize;                       // buffers of blockSize floats in 2 GB
+    const size_t ring = (size_t)p.numStreamBuffers * p.maxCopies + 2;
+    return cap > ring ? std::max<size_t>(1, (cap - ring) / std::max<uint32_t>(1u, p.numHbmBuffers)) : 1;
+}
+
+int Engine::ensureOutRing(size_t floats) {
+    if (floats <= outRingFloats) return kOk;
+    float* nb = nullptr;
+    HIP_OK(hipMalloc(&nb, floats * sizeof(float)));
+    HIP_OK(hipMemsetAsync(nb, 0, floats * sizeof(float), stream));
+    if (dOutRing) deferredFree.push_back(dOutRing);
+    dOutRing = nb; outRingFloats = floats;
+    dropGraphs();
+    return kOk;
+}
+
+int Engine::flushPending() {
+    residentStop();
+    if (nextRec > recCapacity) {   // grow the record arena (device idle: we hold `mu` and sync every call)
+        uint32_t cap = recCapacity;
+        while (cap < nextRec) cap *= 2;
+        uint32_t* nr = nullptr;
+        HIP_OK(hipStreamSynchronize(stream));
+        HIP_OK(hipMalloc(&nr, (size_t)cap * kRecDwords * 4));
+        HIP_OK(hipMemsetAsync(nr, 0, (size_t)cap * kRecDwords * 4, stream));
+        HIP_OK(hipMemcpyAsync(nr, dRecs, (size_t)recCapacity * kRecDwords * 4, hipMemcpyDeviceToDevice, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        (void)hipFree(dRecs);
+        dRecs = nr; recCapacity = cap;
+        dropGraphs();
+    }
+    if (!freshRecs.empty()) {
+        std::sort(freshRecs.begin(), freshRecs.end());
+        size_t i = 0;
+        while (i < freshRecs.size()) {
+            size_t j = i + 1;
+            while (j < freshRecs.size() && freshRecs[j] == freshRecs[j - 1] + 1) ++j;
+            const uint32_t first = freshRecs[i];
+            const size_t count = j - i;
+            // through the pinned staging area the patches use (`shadow` is pageable and changes under the copy otherwise): a new
+            // voice's records reach the device without waiting for the blocks that are still rendering
+            constexpr size_t slotsPerRec = (kRecDwords * 4 + sizeof(Patch) - 1) / sizeof(Patch);
+            size_t done = 0;
+            while (done < count) {
+                if (patchCursor + slotsPerRec > patchCap) { HIP_WARN(hipStreamSynchronize(stream)); patchCursor = 0; }
+                const size_t fit = std::min(count - done, (patchCap - patchCursor) / slotsPerRec);
+                std::memcpy(hPatches + patchCursor, shadow.data() + ((size_t)first + done) * kRecDwords, fit * kRecDwords * 4);
+                HIP_WARN(hipMemcpyAsync(dRecs + ((size_t)first + done) * kRecDwords, hPatches + patchCursor, fit * kRecDwords * 4, hipMemcpyHostToDevice, stream));
+                patchCursor += fit * slotsPerRec;
+                done += fit;
+            }
+            i = j;
+        }
+        for (uint32_t r : freshRecs) freshFlag[r] = 0;
+        freshRecs.clear();
+    }
+    if (deviceClockBehind && !nextSetDirect) {      // (enqueueBatch: direct-I/O convolver sets leave the device's sample clock to be caught up here)
+        const uint64_t t = (uint64_t)hGlobals.sampleTime;
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, sampleTime) / 4), (uint32_t)(t & 0xFFFFFFFFu), 0u});
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, sampleTime) / 4 + 1), (uint32_t)(t >> 32), 0u});
+        deviceClockBehind = false;
+    }
+    size_t off = 0;
+    while (off < patches.size()) {
+        // the patch kernel reads the pinned staging area when it RUNS: hand every launch its own
+        // stretch of it and only rewind once the stream has drained
+        if (patchCursor >= patchCap) { HIP_WARN(hipStreamSynchronize(stream)); patchCursor = 0; }
+        const size_t cnt = std::min<size_t>(patchCap - patchCursor, patches.size() - off);
+        std::memcpy(hPatches + patchCursor, patches.data() + off, cnt * sizeof(Patch));
+        launch_patches(stream, hPatches + patchCursor, (uint32_t)cnt, dRecs, reinterpret_cast<uint32_t*>(dGlobals));
+        debugSync("patches", (unsigned)cnt);
+        patchCursor += cnt;
+        off += cnt;
+    }
+    patches.clear();
+    // new channel records of multi-output nodes that are already rendering: everything but the buffer slots, AFTER the
+    // patches (a pending-buffer flag the host has just queued for channel 0 reaches the new channel with this copy)
+    for (auto& cl : recClones)
+        HIP_WARN(hipMemcpyAsync(dRecs + (size_t)cl.second * kRecDwords + rec::P3, dRecs + (size_t)cl.first * kRecDwords + rec::P3,
+                                (kRecDwords - rec::P3) * 4, hipMemcpyDeviceToDevice, stream));
+    recClones.clear();
+    return kOk;
+}
+
+int Engine::setGlobalsFor(size_t nIn, size_t nOut, size_t n, int64_t sampleTime) {
+    auto patchG = [&](size_t byteOff, uint32_t v) { patches.push_back(Patch{2u, (uint32_t)(byteOff / 4), v, 0u}); };
+    if (hGlobals.numSamples != (uint32_t)n) { hGlobals.numSamples = (uint32_t)n; patchG(offsetof(Globals, numSamples), (uint32_t)n); }
+    if (hGlobals.numIn != (uint32_t)nIn) { hGlobals.numIn = (uint32_t)nIn; patchG(offsetof(Globals, numIn), (uint32_t)nIn); }
+    if (hGlobals.numOut != (uint32_t)nOut) { hGlobals.numOut = (uint32_t)nOut; patchG(offsetof(Globals, numOut), (uint32_t)nOut); }
+    if (hGlobals.sampleTime != sampleTime) {
+        hGlobals.sampleTime = sampleTime;
+        patchG(offsetof(Globals, sampleTime), (uint32_t)((uint64_t)sampleTime & 0xFFFFFFFFu));
+        patchG(offsetof(Globals, sampleTime) + 4, (uint32_t)((uint64_t)sampleTime >> 32));
+    }
+    return kOk;
+}
+
+void Engine::setInRing(const float* ring, uint32_t blocks) {
+    const uint64_t v = (uint64_t)(uintptr_t)ring;
+    if (hGlobals.inRing != v) {
+        hGlobals.inRing = v;
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, inRing) / 4), (uint32_t)(v & 0xFFFFFFFFu), 0u});
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, inRing) / 4 + 1), (uint32_t)(v >> 32), 0u});
+    }
+    if (hGlobals.inBlocks != blocks) {
+        hGlobals.inBlocks = blocks;
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, inBlocks) / 4), blocks, 0u});
+    }
+}
+
+int Engine::swapInPending() {   // Runtime.h:277-285: newest sequence wins
+    if (pending) {
+        if (current && !dry) retiredPlans.push_back(std::move(current));   // its kernels may still be queued (host path): freed after the next synchronize
+        current = pending;
+        pending.reset();
+        current->blocksAtAdoption = st.blocksRendered;
+        current->adopted = std::chrono::steady_clock::now();
+        st.numIslands = (uint32_t)current->islands.size();
+        st.numLevels = (uint32_t)current->levelOffsets.size() - 1;
+        st.numTasks = current->numTasks;
+        st.numNodesInPlan = (uint32_t)current->nodeIds.size();
+        st.maxLdsBytes = current->maxLdsBytes;
+        st.numHbmBuffers = current->numHbmBuffers;
+    }
+    if (!current) return kOk;
+    int rc = ensureHbm(arenaBuffers(*current, 1));
+    if (rc != kOk) return rc;
+    if (current->maxLdsBytes > maxLdsConfigured) {
+        HIP_OK(configure_kernels(current->maxLdsBytes));
+        maxLdsConfigured = current->maxLdsBytes;
+    }
+    return kOk;
+}
+
+void Engine::enqueueBlock(const Plan& p, float* outRing) {
+    if (!outRing) outRing = dOutRing;
+    const size_t L = p.levelOffsets.size() - 1;
+    for (size_t l = 0; l < L; ++l) {
+        const uint32_t b = p.levelOffsets[l], e = p.levelOffsets[l + 1];
+        if (e > b) { launch_level(stream, p.view, dRecs, dHbm, dGlobals, dLcg, b, e - b, p.levelLdsBytes[l]); islandBlocksInterp += e - b; }
+        debugSync("block: interpreter level", (unsigned)l, e - b);
+        const uint32_t cb = p.convLevelOffsets[l], ce = p.convLevelOffsets[l + 1];
+        if (ce > cb) launch_convolve(stream, p.view, dRecs, dHbm, dGlobals, cb, ce - cb);
+        if (!p.hosts.empty()) (void)renderHostNodes(p, l);
+    }
+    launch_epilogue(stream, p.view, dRecs, dHbm, dGlobals, outRing, armFlag, armValue);
+    if (armFlag) flagArmed = true;
+    debugSync("block: epilogue");
+}
+
+// Call-out nodes of launch level `l` (GraphNode::process on the CPU, GraphNode.h:72): drain the stream, bring each node's
+// input buffers to the host, run the user's process(), put its output block back into the arena. Slow by construction
+// (two PCIe round trips and a pipeline drain per node and block) — the price of keeping custom CPU nodes usable.
+int Engine::renderHostNodes(const Plan& p, size_t l) {
+    bool any = false;
+    for (const Plan::HostDesc& h : p.hosts) if (h.level == (uint32_t)l) { any = true; break; }
+    if (!any) return kOk;
+    HIP_OK(hipStreamSynchronize(stream));
+    const size_t bs = (size_t)blockSize, n = hGlobals.numSamples, nInHost = hGlobals.numIn;
+    for (const Plan::HostDesc& h : p.hosts) {
+        if (h.level != (uint32_t)l) continue;
+        auto nit = nodes.find(h.nodeId), rit = nodes.find(h.rootId);
+        if (nit == nodes.end() || rit == nodes.end() || !nit->second.hostVt) continue;
+        const Node& r = rit->second;
+        const bool on = r.target > 0.5f, settled = std::fabs(r.target - r.gain) <= 1e-6f;
+        if (!((on || !settled) && r.channel >= 0 && (uint32_t)r.channel < hGlobals.numOut)) continue;   // GraphRenderSequence.h:214-219
+        const size_t k = h.leaf ? nInHost : h.inputs.size();
+        hostIn.assign(std::max<size_t>(k, 1) * bs, 0.0f);
+        hostOut.assign(bs, 0.0f);
+        for (size_t j = 0; j < k; ++j) {
+            float* dst = hostIn.data() + j * bs;
+            if (h.leaf) { HIP_OK(hipMemcpyAsync(dst, dHbm + j * bs, n * sizeof(float), hipMemcpyDeviceToHost, stream)); continue; }
+            const Plan::HostDesc::In& in = h.inputs[j];
+            if (in.kind == 1) HIP_OK(hipMemcpyAsync(dst, dHbm + (size_t)in.idx * bs, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+            else if (in.kind == 2) { float v; std::memcpy(&v, &shadow[(size_t)in.idx * kRecDwords + rec::P0], 4); std::fill(dst, dst + n, v); }
+            else if (in.kind == 3) {
+                const uint32_t ch = shadow[(size_t)in.idx * kRecDwords + rec::P0];
+                if (ch < nInHost) HIP_OK(hipMemcpyAsync(dst, dHbm + (size_t)ch * bs, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+            }
+        }
+        HIP_OK(hipStreamSynchronize(stream));
+        std::vector<const float*> ptrs(std::max<size_t>(k, 1));
+        for (size_t j = 0; j < k; ++j) ptrs[j] = hostIn.data() + j * bs;
+        const Node& hn = nit->second;
+        hn.hostVt->process(hn.hostInst, ptrs.data(), k, hostOut.data(), n, curBlockTime, h.active ? 1 : 0, hn.hostVt->user);
+        HIP_OK(hipMemcpyAsync(dHbm + (size_t)h.outHbm * bs, hostOut.data(), n * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+    }
+    return kOk;
+}
+
+// Host mirror of what the epilogue kernel does to each root's fade (GainFade.h:56-72), so that
+// activateRoots()/gc() can evaluate stillRunning() without a device read-back.
+void Engine::mirrorRootFades(const Plan& p, uint32_t n, uint32_t nOut, uint32_t nIn) {
+    for (int32_t id : p.rootIds) {
+        auto it = nodes.find(id);
+        if (it == nodes.end()) continue;
+        Node& r = it->second;
+        const bool on = r.target > 0.5f;
+        const bool settled = std::fabs(r.target - r.gain) <= 1e-6f;
+        if (!((on || !settled) && r.channel >= 0 && (uint32_t)r.channel < nOut)) continue;
+        if (r.gain != r.target && (!r.inlets.empty() || nIn > 0))
+            r.gain = clampf(r.gain + r.step * (float)(int)n, 0.0f, 1.0f);
+    }
+}
+
+// A host block longer than the engine's: slice `off / blockSize` of it renders the frames [off, off + blockSize) — and a tap's delay
+// is the HOST's block (TapOutNode::promoteTapBuffers copies numSamples frames of its delay buffer to the shared one, TapInNode copies
+// numSamples frames back out: Feedback.h:88-109, 40-54), so the slice reads and promotes ITS stretch of the shared buffers: the tap
+// records' shared-buffer pointers move with the slice (parameter patches, applied in front of the slice's kernels).
+void Engine::setTapSlice(size_t off) {
+    if (off == tapSliceOff) return;
+    tapSliceOff = off;
+    if (dry) return;
+    for (int32_t id : tapNodeIds) {
+        auto it = nodes.find(id);
+        if (it == nodes.end() || !it->second.res || !it->second.res->dev.ptr) continue;
+        writeParamPtr(it->second, rec::TAP_SHARED, reinterpret_cast<const float*>(it->second.res->dev.ptr) + off);
+    }
+}
+
+int Engine::process(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t n, int64_t sampleTime) {
+    if (hostBlockSize == blockSize) return processSlice(in, nIn, out, nOut, n, sampleTime);
+    if (n > (size_t)hostBlockSize) return kBlockTooLarge;
+    if (nIn > kMaxHostIn || nOut > kMaxOutBus) return kTooManyChannels;
+    // a host block longer than the engine's: slice by slice (each slice is a block of its own to the kernels), the render lock held
+    // and the newest sequence adopted ONCE for the whole host block — a commit, gc or event relay from another thread lands between
+    // two host blocks, never inside one
+    std::vector<const float*> ip(nIn);
+    std::vector<float*> op(nOut);
+    std::lock_guard<std::mutex> lock(mu);
+    for (size_t off = 0; off < n || off == 0; off += (size_t)blockSize) {
+        for (size_t c = 0; c < nIn; ++c) ip[c] = in[c] + off;
+        for (size_t c = 0; c < nOut; ++c) op[c] = out[c] + off;
+        if (!tapNodeIds.empty()) setTapSlice(off);
+        const int rc = processSliceLocked(ip.data(), nIn, op.data(), nOut, std::min((size_t)blockSize, n - off), sampleTime + (int64_t)off, off == 0);
+        if (rc != kOk) return rc;
+    }
+    noteHostBlockEnd();
+    return kOk;
+}
+
+int Engine::processSlice(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t n, int64_t sampleTime) {
+    std::lock_guard<std::mutex> lock(mu);
+    return processSliceLocked(in, nIn, out, nOut, n, sampleTime, true);
+}
+
+// (`mu` held.) `adopt`: take the newest render sequence — once per HOST block (Runtime.h:277-285): the later slices of a host block
+// longer than the engine's render the sequence its first slice adopted, under the same hold of the lock.
+int Engine::processSliceLocked(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t n, int64_t sampleTime, bool adopt) {
+    if (dry) return kNoDevice;
+    if (hipSetDevice(device) != hipSuccess) return kHipError;
+    if (n > (size_t)blockSize) return kBlockTooLarge;
+    if (nIn > kMaxHostIn || nOut > kMaxOutBus) return kTooManyChannels;
+    if (n != conv::kBlock) convAligned = false;   // a convolver's input block may now be partly filled at a call boundary
+    if (residentLive && (pending || !residentOpt)) residentStop();
+    int rc = adopt ? swapInPending() : kOk;
+    if (rc != kOk) return rc;
+    if (!current) return kOk;   // no render sequence yet: outputs untouched (Runtime.h:287-289)
+    Plan& p = *current;
+    if (p.packedRootChannels > 0 && nOut < (size_t)p.packedRootChannels) return kInvalidPropertyValue;   // (`pack_roots`, plan.cpp)
+
+    if (hGlobals.ringSlots != 1 || hGlobals.blockSlot != 0) {
+        hGlobals.ringSlots = 1; hGlobals.blockSlot = 0;
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, ringSlots) / 4), 1u, 0u});
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, blockSlot) / 4), 0u, 0u});
+    }
+    setGlobalsFor(nIn, nOut, n, sampleTime);
+    setInRing(nullptr, 0);
+    rc = ensureOutRing(std::max<size_t>(nOut, 1) * blockSize);
+    if (rc != kOk) return rc;
+    // option "resident": a run of plain blocks (nothing to flush, every fade settled, the same plan and channel counts) is handed
+    // to the resident kernel through mapped host memory — no launch, no stream synchronise
+    {
+        const bool plain = residentOpt && n == (size_t)blockSize && residentEligible(p, nIn, nOut);
+        if (residentLive && (!plain || residentPlan != &p || residentNIn != nIn || residentNOut != nOut)) residentStop();
+        if (!plain) residentStreak = 0;
+        else if (!residentLive && ++residentStreak > residentAfter) {
+            rc = residentStart(p, nIn, nOut);
+            if (rc != kOk) return rc;
+        }
+        if (residentLive) {
+            rc = residentBlock(in, nIn, out, nOut, n);
+            if (rc != kResidentGone) return rc;
+        }
+    }
+    // A whole block of a settled sequence whose island shapes are all compiled goes through the specialised kernels as a
+    // launch set of one (stages pipelined inside the workgroup, no interpreter image); everything else block by block.
+    const bool specLevels = n == (size_t)blockSize && specBlockOk(p);
+    const bool specBlock = specLevels && batchEligible(p, nOut, true);
+    const bool specFade = specLevels && !specBlock;      // root fades running: same level launches, the per-block epilogue behind them
+    if (specLevels) {
+        rc = ensureHbm(arenaBuffers(p, 1));
+        if (rc != kOk) return rc;
+    }
+
+    if (nIn > 0) {
+        const size_t floats = nIn * (size_t)blockSize;
+        if (floats > hInFloats) {
+            if (hIn) (void)hipHostFree(hIn);
+            HIP_OK(hipHostMalloc((void**)&hIn, floats * sizeof(float), hipHostMallocDefault));
+            hInFloats = floats;
+        }
+        for (size_t c = 0; c < nIn; ++c) {
+            std::memcpy(hIn + c * blockSize, in[c], n * sizeof(float));
+            if (n < (size_t)blockSize) std::memset(hIn + c * blockSize + n, 0, (blockSize - n) * sizeof(float));
+        }
+        HIP_OK(hipMemcpyAsync(dHbm, hIn, floats * sizeof(float), hipMemcpyHostToDevice, stream));
+    }
+    rc = flushPending();
+    if (rc != kOk) return rc;
+    curBlockTime = sampleTime;
+    // the epilogue writes the output block straight into the pinned host buffer (mapped into the device's address space): one
+    // launch and one PCIe write burst less than rendering into HBM and copying back
+    float* outDev = nullptr;
+    if (nOut > 0) {
+        const size_t floats = std::max<size_t>(nOut, 1) * (size_t)blockSize;
+        if (floats > hOutFloats) {
+            HIP_OK(hipStreamSynchronize(stream));
+            if (hOut) (void)hipHostFree(hOut);
+            hOut = nullptr; hOutFloats = 0; hOutDev = nullptr;
+            // mapped AND coherent, said out loud: with `sync_poll` the host reads this block when the epilogue's word arrives, before the
+            // kernel has ended — no kernel-end release stands behind the samples, only the epilogue's own system-scope fence
+            HIP_OK(hipHostMalloc((void**)&hOut, floats * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+            hOutFloats = floats;
+            if (hipHostGetDevicePointer((void**)&hOutDev, hOut, 0) != hipSuccess) hOutDev = nullptr;
+        }
+        outDev = hostOutDirect ? hOutDev : nullptr;
+    }
+    // the call ends when the epilogue's word arrives (sync_poll): only when the epilogue writes the host's block itself and nothing is
+    // being profiled
+    flagArmed = false; armFlag = nullptr;
+    if (syncPoll && outDev && !profileLaunches && !debugSyncOn() && p.hosts.empty()) {
+        if (!hDone) {
+            HIP_OK(hipHostMalloc((void**)&hDone, 64, hipHostMallocMapped | hipHostMallocCoherent));
+            *hDone = 0;
+            HIP_OK(hipHostGetDevicePointer((void**)&dDone, hDone, 0));
+        }
+        armFlag = dDone; armValue = ++doneSeq;
+    }
+    if (specBlock) enqueueBatch(p, 1u, outDev);
+    else if (specFade) enqueueSpecBlock(p, outDev);
+    else { fixConvOverlaps(p); enqueueBlock(p, outDev); }
+    if (nOut > 0 && !outDev) HIP_OK(hipMemcpyAsync(hOut, dOutRing, nOut * (size_t)blockSize * sizeof(float), hipMemcpyDeviceToHost, stream));
+    armFlag = nullptr;
+    bool arrived = false;
+    if (flagArmed) {
+        // spin on the epilogue's word (2 ms at most: a graph that takes longer gains nothing from it; a kernel that faulted never
+        // publishes — the synchronise below reports it)
+        const uint32_t want = armValue;
+        uint32_t spins = 0;
+        std::chrono::steady_clock::time_point t0;
+        for (;;) {
+            if (__atomic_load_n(hDone, __ATOMIC_ACQUIRE) == want) { arrived = true; break; }
+            __builtin_ia32_pause();
+            if ((++spins & 0x3FFu) == 0u) {
+                const auto now = std::chrono::steady_clock::now();
+                if (spins == 0x400u) t0 = now;
+                else if (now - t0 > std::chrono::milliseconds(2)) break;
+            }
+        }
+        flagArmed = false;
+        syncPolls++;
+        if (!arrived) syncPollFallbacks++;
+    }
+    // (every 256th call still synchronises: the runtime retires its launch bookkeeping there; so does a call with plans / buffers
+    //  waiting to be released — freeDeferred's contract is a REAL synchronise of the stream, not the polled word)
+    bool synced = false;
+    if (!arrived || !deferredFree.empty() || !retiredPlans.empty() || (++unsyncedCalls & 255u) == 0u) {
+        HIP_OK(hipStreamSynchronize(stream));
+        HIP_OK(hipGetLastError());
+        synced = true;
+    }
+    if (profUsed) profCollect();
+    for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c], hOut + c * blockSize, n * sizeof(float));
+    mirrorRootFades(p, (uint32_t)n, (uint32_t)nOut, (uint32_t)nIn);
+    hGlobals.sampleTime += (int64_t)n;
+    st.blocksRendered++;
+    promoteDeferredShapes();
+    // the word arrived: the armed epilogue is the last work of this call on `stream`, which is in order and joined every side stream
+    // in front of it — the patch uploads of this call have been consumed, so the staging cursor may start over; nothing is freed
+    if (synced) freeDeferred(); else patchCursor = 0;
+    return kOk;
+}
+
+// ---- option "resident" (resident.hip) -------------------------------------------------------------------------------------------
+bool Engine::residentEligible(const Plan& p, size_t nIn, size_t nOut) const {
+    if (!p.convs.empty() || !p.hosts.empty() || profileLaunches || debugSyncOn() || hGlobals.trace) return false;
+    if (!patches.empty() || !freshRecs.empty() || !recClones.empty() || deviceClockBehind) return false;   // (something flushPending still has to bring to the device)
+    if (p.view.numRoots > kResidentMaxRoots || p.levelOffsets.size() < 2 || p.levelOffsets.size() - 1 > kResidentMaxLevels) return false;
+    if (p.levelOffsets.back() == 0u) return false;
+    return batchEligible(p, nOut, true);      // every running root's fade settled: the epilogue has no per-root state to advance
+}
+
+int Engine::residentStart(const Plan& p, size_t nIn, size_t nOut) {
+    if (!hResident) {
+        HIP_OK(hipHostMalloc((void**)&hResident, sizeof(ResidentCtl), hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_OK(hipHostGetDevicePointer((void**)&dResidentCtl, hResident, 0));
+        HIP_OK(hipMalloc((void**)&dResidentSync, 64));
+    }
+    const size_t inF = std::max<size_t>(nIn, 1) * (size_t)blockSize, outF = std::max<size_t>(nOut, 1) * (size_t)blockSize;
+    if (inF > resInFloats) {
+        if (hResIn) (void)hipHostFree(hResIn);
+        hResIn = nullptr; resInFloats = 0;
+        HIP_OK(hipHostMalloc((void**)&hResIn, inF * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_OK(hipHostGetDevicePointer((void**)&dResIn, hResIn, 0));
+        resInFloats = inF;
+    }
+    if (outF > resOutFloats) {
+        if (hResOut) (void)hipHostFree(hResOut);
+        hResOut = nullptr; resOutFloats = 0;
+        HIP_OK(hipHostMalloc((void**)&hResOut, outF * sizeof(float), hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_OK(hipHostGetDevicePointer((void**)&dResOut, hResOut, 0));
+        resOutFloats = outF;
+    }
+    ResidentLevels lv{};
+    lv.count = (uint32_t)p.levelOffsets.size() - 1;
+    uint32_t widest = 1;
+    for (uint32_t l = 0; l <= lv.count; ++l) lv.offset[l] = p.levelOffsets[l];
+    for (uint32_t l = 0; l < lv.count; ++l) widest = std::max(widest, lv.offset[l + 1] - lv.offset[l]);
+    // one workgroup per compute unit at most: every workgroup has to be ON the device for the barriers between the levels to complete
+    const uint32_t groups = std::min<uint32_t>(widest, (uint32_t)std::max(1, cuCount));
+    if (p.maxLdsBytes > residentLdsConfigured) {
+        HIP_OK(configure_resident(p.maxLdsBytes));
+        residentLdsConfigured = p.maxLdsBytes;
+    }
+    std::memset(hResident, 0, sizeof(ResidentCtl));
+    HIP_OK(hipMemsetAsync(dResidentSync, 0, 64, stream));
+    const uint64_t idleTicks = (uint64_t)residentIdleUs * 100ull, hangTicks = 5ull * 100000000ull;   // s_memrealtime: 100 MHz
+    HIP_OK(launch_resident(stream, p.view, dRecs, dHbm, dGlobals, dLcg, lv, groups, std::max<uint32_t>(p.maxLdsBytes, 1024u), dResidentCtl, dResIn, dResOut,
+                           dResidentSync, idleTicks, hangTicks));
+    residentTicksBody = residentTicksEpilogue = 0;
+    residentLive = true; residentSeq = 0; residentPlan = &p; residentNIn = nIn; residentNOut = nOut;
+    st.residentLaunches++;
+    return kOk;
+}
+
+void Engine::residentStop() {
+    if (!residentLive) return;
+    __atomic_store_n(&hResident->seq, kResidentQuit, __ATOMIC_RELEASE);
+    HIP_WARN(hipStreamSynchronize(stream));
+    if (__atomic_load_n(&hResident->exited, __ATOMIC_ACQUIRE) == 2u)
+        std::fprintf(stderr, "[elemhip] resident kernel: a device-wide barrier timed out; the block it was rendering is lost\n");
+    residentLive = false; residentStreak = 0; residentPlan = nullptr;
+    static const bool trace = std::getenv("ELEMHIP_RESIDENT_TRACE") != nullptr;
+    if (trace && residentSeq)
+        std::fprintf(stderr, "[elemhip] resident kernel left after %u blocks: levels %.2f us, epilogue %.2f us per block (device clock, from the block number's arrival)\n",
+                     residentSeq, 0.01 * (double)residentTicksBody / residentSeq, 0.01 * (double)residentTicksEpilogue / residentSeq);
+}
+
+int Engine::residentBlock(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t n) {
+    for (size_t c = 0; c < nIn; ++c) std::memcpy(hResIn + c * blockSize, in[c], n * sizeof(float));
+    const uint32_t seq = ++residentSeq;
+    __atomic_store_n(&hResident->seq, seq, __ATOMIC_RELEASE);
+    uint32_t spins = 0;
+    std::chrono::steady_clock::time_point t0;
+    for (;;) {
+        if (__atomic_load_n(&hResident->done, __ATOMIC_ACQUIRE) == seq) break;
+        if (__atomic_load_n(&hResident->exited, __ATOMIC_ACQUIRE) != 0u) {
+            // it left: by itself (idle) before it saw this block, or on a barrier time-out
+            const bool rendered = __atomic_load_n(&hResident->done, __ATOMIC_ACQUIRE) == seq;
+            const uint32_t code = hResident->exited;
+            HIP_WARN(hipStreamSynchronize(stream));
+            residentLive = false; residentStreak = 0; residentPlan = nullptr;
+            if (rendered) break;
+            if (code == 2u) return kHipError;
+            return kResidentGone;
+        }
+        __builtin_ia32_pause();
+        if ((++spins & 0xFFFu) == 0u) {
+            const auto now = std::chrono::steady_clock::now();
+            if (spins == 0x1000u) t0 = now;
+            else if (now - t0 > std::chrono::seconds(10)) {      // (the kernel's own time-outs are 5 s: this is a kernel that never started)
+                __atomic_store_n(&hResident->seq, kResidentQuit, __ATOMIC_RELEASE);
+                HIP_WARN(hipStreamSynchronize(stream));
+                residentLive = false; residentStreak = 0; residentPlan = nullptr;
+                return kHipError;
+            }
+        }
+    }
+    for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c], hResOut + c * blockSize, n * sizeof(float));
+    residentTicksBody += hResident->ticksBody; residentTicksEpilogue += hResident->ticksEpilogue;
+    curBlockTime = hGlobals.sampleTime;
+    hGlobals.sampleTime += (int64_t)n;
+    st.blocksRendered++; st.residentBlocks++;
+    islandBlocksInterp += current->levelOffsets.back();
+    return kOk;
+}
+
+int Engine::timeLaunches(size_t nOut, size_t numBlocks, float* msOut, size_t cap) {
+    RenderGuard lock(*this);
+    if (dry) return -kNoDevice;
+    if (hipSetDevice(device) != hipSuccess) return -kHipError;
+    int rc = swapInPending();
+    if (rc != kOk) return -rc;
+    if (!current) return 0;
+    const Plan& p = *current;
+    const size_t L = p.levelOffsets.size() - 1;
+    if (cap < L + 1) return -kInvalidPropertyValue;
+    rc = ensureOutRing(std::max<size_t>(nOut, 1) * blockSize);
+    if (rc != kOk) return -rc;
+    if (hGlobals.ringSlots != 1 || hGlobals.blockSlot != 0) {
+        hGlobals.ringSlots = 1; hGlobals.blockSlot = 0;
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, ringSlots) / 4), 1u, 0u});
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, blockSlot) / 4), 0u, 0u});
+    }
+    setGlobalsFor(0, nOut, (size_t)blockSize, hGlobals.sampleTime);
+    setInRing(nullptr, 0);
+    rc = flushPending();
+    if (rc != kOk) return -rc;
+    std::vector<hipEvent_t> ev(2 * (L + 2));   // + one empty pair: the cost of the event pair itself
+    for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) return -kHipError;
+    std::vector<double> acc(L + 2, 0.0);
+    // timeBatch > 1: time the multi-block launches elemhip_process_blocks issues (msOut = per LAUNCH of `batch` blocks)
+    const uint32_t batch = (timeBatch > 1 && p.convs.empty() && batchEligible(p, nOut)) ? (uint32_t)std::min<size_t>((size_t)timeBatch, maxSetBlocks(p)) : 1u;
+    const uint32_t arenaFloats = batch > 1 ? p.numHbmBuffers * (uint32_t)blockSize : 0u;
+    if (batch > 1) {
+        rc = ensureHbm(arenaBuffers(p, batch)); if (rc != kOk) return -rc;
+        rc = ensureOutRing(std::max<size_t>(nOut, 1) * blockSize * batch); if (rc != kOk) return -rc;
+    }
+    lastTimeBatch = batch;
+    fixConvOverlaps(p);
+    for (size_t b = 0; b < numBlocks; ++b) {
+        for (size_t l = 0; l < L; ++l) {
+            const uint32_t lb = p.levelOffsets[l], le = p.levelOffsets[l + 1];
+            (void)hipEventRecord(ev[2 * l], stream);
+            if (le > lb) { if (batch > 1) launchLevelBatch(p, l, batch, arenaFloats); else launch_level(stream, p.view, dRecs, dHbm, dGlobals, dLcg, lb, le - lb, p.levelLdsBytes[l], batch, arenaFloats, statelessRows); }
+            if (p.convLevelOffsets[l + 1] > p.convLevelOffsets[l])
+                launch_convolve(stream, p.view, dRecs, dHbm, dGlobals, p.convLevelOffsets[l], p.convLevelOffsets[l + 1] - p.convLevelOffsets[l]);
+            (void)hipEventRecord(ev[2 * l + 1], stream);
+        }
+        (void)hipEventRecord(ev[2 * L], stream);
+        if (batch > 1) launch_epilogue_batch(stream, p.view, dRecs, dHbm, dGlobals, dOutRing, batch, arenaFloats);
+        else launch_epilogue(stream, p.view, dRecs, dHbm, dGlobals, dOutRing);
+        (void)hipEventRecord(ev[2 * L + 1], stream);
+        (void)hipEventRecord(ev[2 * L + 2], stream);
+        (void)hipEventRecord(ev[2 * L + 3], stream);
+        if (hipStreamSynchronize(stream) != hipSuccess) return -kHipError;
+        for (size_t l = 0; l <= L + 1; ++l) { float ms = 0; (void)hipEventElapsedTime(&ms, ev[2 * l], ev[2 * l + 1]); acc[l] += ms; }
+        for (uint32_t k = 0; k < batch; ++k) mirrorRootFades(p, (uint32_t)blockSize, (uint32_t)nOut, 0);
+        hGlobals.sampleTime += (int64_t)blockSize * batch;
+        st.blocksRendered += batch;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    // an empty event pair measures the marker-to-marker cost that every timed launch also pays
+    const double empty = acc[L + 1] / (double)std::max<size_t>(numBlocks, 1);
+    for (size_t l = 0; l <= L; ++l) msOut[l] = (float)std::max(0.0, acc[l] / (double)std::max<size_t>(numBlocks, 1) - empty);
+    if (cap > L + 1) msOut[L + 1] = (float)empty;
+    if (cap > L + 2) msOut[L + 2] = (float)batch;   // blocks per timed launch
+    return (int)(L + 1);
+}
+
+int Engine::traceLevel(size_t nOut, uint32_t level, unsigned long long* out, size_t cap) {
+    RenderGuard lock(*this);
+    if (dry) return kNoDevice;
+    if (hipSetDevice(device) != hipSuccess) return kHipError;
+    int rc = swapInPending();
+    if (rc != kOk) return rc;
+    if (!current || cap < kWaves * 192) return kInvalidPropertyValue;
+    const Plan& p = *current;
+    const size_t L = p.levelOffsets.size() - 1;
+    rc = ensureOutRing(std::max<size_t>(nOut, 1) * blockSize);
+    if (rc != kOk) return rc;
+    unsigned long long* dTrace = nullptr;
+    HIP_OK(hipMalloc(&dTrace, kWaves * 192 * 8));
+    HIP_OK(hipMemset(dTrace, 0, kWaves * 192 * 8));
+    if (hGlobals.ringSlots != 1 || hGlobals.blockSlot != 0) {
+        hGlobals.ringSlots = 1; hGlobals.blockSlot = 0;
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, ringSlots) / 4), 1u, 0u});
+        patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, blockSlot) / 4), 0u, 0u});
+    }
+    setGlobalsFor(0, nOut, (size_t)blockSize, hGlobals.sampleTime);
+    setInRing(nullptr, 0);
+    rc = flushPending();
+    if (rc != kOk) return rc;
+    const uint64_t tp = (uint64_t)reinterpret_cast<uintptr_t>(dTrace);
+    const uint32_t batch = (timeBatch > 1 && p.convs.empty() && batchEligible(p, nOut)) ? (uint32_t)std::min<size_t>((size_t)timeBatch, maxSetBlocks(p)) : 1u;
+    const uint32_t arenaFloats = batch > 1 ? p.numHbmBuffers * (uint32_t)blockSize : 0u;
+    if (batch > 1) {
+        rc = ensureHbm(arenaBuffers(p, batch)); if (rc != kOk) return rc;
+        rc = ensureOutRing(std::max<size_t>(nOut, 1) * blockSize * batch); if (rc != kOk) return rc;
+    }
+    for (size_t l = 0; l < L; ++l) {
+        const uint32_t lb = p.levelOffsets[l], le = p.levelOffsets[l + 1];
+        const uint64_t v = (l == level) ? tp : 0;
+        HIP_OK(hipMemcpyAsync(reinterpret_cast<char*>(dGlobals) + offsetof(Globals, trace), &v, 8, hipMemcpyHostToDevice, stream));
+        if (le > lb) { if (batch > 1) launchLevelBatch(p, l, batch, arenaFloats); else launch_level(stream, p.view, dRecs, dHbm, dGlobals, dLcg, lb, le - lb, p.levelLdsBytes[l], batch, arenaFloats, statelessRows); }
+    }
+    const uint64_t zero = 0;
+    HIP_OK(hipMemcpyAsync(reinterpret_cast<char*>(dGlobals) + offsetof(Globals, trace), &zero, 8, hipMemcpyHostToDevice, stream));
+    if (batch > 1) launch_epilogue_batch(stream, p.view, dRecs, dHbm, dGlobals, dOutRing, batch, arenaFloats);
+    else launch_epilogue(stream, p.view, dRecs, dHbm, dGlobals, dOutRing);
+    HIP_OK(hipStreamSynchronize(stream));
+    HIP_OK(hipMemcpy(out, dTrace, kWaves * 192 * 8, hipMemcpyDeviceToHost));
+    (void)hipFree(dTrace);
+    for (uint32_t k = 0; k < batch; ++k) mirrorRootFades(p, (uint32_t)blockSize, (uint32_t)nOut, 0);
+    hGlobals.sampleTime += (int64_t)blockSize * batch;
+    st.blocksRendered += batch;
+    return kOk;
+}
+
+// A multi-block launch carries no per-block root/tap/convolver bookkeeping: it is used only while every
+// running root's fade is settled (Core.h:28-31) and the plan has neither taps nor convolvers.
+// every island shape of the sequence has its kernel loaded on this device (stateless islands stay with the interpreter kernel)
+bool Engine::specReady(const Plan& p) const {
+    if (specialize == 0 || p.shapes.empty()) return false;
+    bool any = false;
+    for (const Plan::SpecShape& sh : p.shapes) {
+        if (sh.entry->function(device)) any = true;
+        else if (!sh.optional) return false;
+    }
+    return any;
+}
+
+void Engine::promoteDeferredShapes() {
+    Plan* p = current.get();
+    if (!p || !p->deferredShapes) return;
+    if (st.blocksRendered - p->blocksAtAdoption < (uint64_t)std::max(0, lonelyBlocks)) return;
+    if (std::chrono::steady_clock::now() - p->adopted < std::chrono::milliseconds(std::max(0, lonelyMs))) return;
+    for (Plan::SpecShape& sh : p->shapes)
+        if (sh.deferred) { Jit::get().promote(sh.entry); sh.deferred = false; }
+    p->deferredShapes = 0;
+}
+
+bool Engine::anyRootRuns(const std::vector<int32_t>& rootIds, size_t nOut) const {
+    for (int32_t id : rootIds) {
+        auto it = nodes.find(id);
+        if (it == nodes.end()) return true;          // (cannot tell: launch)
+        const Node& r = it->second;
+        const bool on = r.target > 0.5f, settled = std::fabs(r.target - r.gain) <= 1e-6f;
+        if ((on || !settled) && r.channel >= 0 && (uint32_t)r.channel < nOut) return true;
+    }
+    return false;
+}
+
+// (oneBlock: a launch set of ONE — the batch epilogue promotes the taps after it like the per-block epilogue does, so tap
+// pairs that do not sit in one island are no obstacle)
+bool Engine::batchEligible(const Plan& p, size_t nOut, bool oneBlock) const {
+    if ((!oneBlock && !p.taps.empty() && !p.tapsInSets) || !p.hosts.empty()) return false;
+    // convolvers: the multi-block kernels (conv.hip) assume every node's 512-frame input block is empty at the start of a
+    // launch set, i.e. that every call so far rendered whole 512-frame blocks
+    if (!p.convs.empty() && !(convAligned && blockSize == (int)conv::kBlock)) return false;
+    for (int32_t id : p.rootIds) {
+        auto it = nodes.find(id);
+        if (it == nodes.end()) return false;
+        const Node& r = it->second;
+        const bool on = r.target > 0.5f;
+        const bool settled = std::fabs(r.target - r.gain) <= 1e-6f;
+        const bool running = (on || !settled) && r.channel >= 0 && (uint32_t)r.channel < nOut;
+        if (running && r.gain != r.target) return false;
+    }
+    return true;
+}
+
+hipEvent_t Engine::profEvent() {
+    if (profUsed == profEvents.size()) { hipEvent_t e = nullptr; (void)hipEventCreate(&e); profEvents.push_back(e); }
+    return profEvents[profUsed++];
+}
+
+// after a stream synchronize: fold the event pairs of this call into the per-level sums
+void Engine::profCollect() {
+    for (size_t k = 0; k + 1 < profUsed; k += 2) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, profEvents[k], profEvents[k + 1]) != hipSuccess) continue;
+        const uint32_t slot = profSlots[k / 2];
+        if (profMs.size() <= slot) profMs.resize(slot + 1, 0.0);
+        profMs[slot] += ms;
+    }
+    profUsed = 0; profSlots.clear();
+}
+
+// debug / tests: program text and compile state of the k-th specialised shape of the newest plan
+int Engine::specInfo(size_t k, std::string* source, std::string* log, int* state, uint32_t* islands) {
+    std::lock_guard<std::mutex> control(ctl);
+    RenderGuard lock(*this);
+    const std::shared_ptr<Plan> pl = pending ? pending : current;
+    if (!pl || k >= pl->shapes.size()) return -1;
+    const Plan::SpecShape& sh = pl->shapes[k];
+    if (source) *source = sh.entry->fullText();
+    if (log) *log = sh.entry->log;
+    if (state) *state = sh.entry->state.load();
+    if (islands) *islands = sh.count;
+    return (int)pl->shapes.size();
+}
+
+int Engine::launchProfile(double* msOut, size_t cap, uint64_t* launchSets, uint64_t* blocks) {
+    RenderGuard lock(*this);
+    if (launchSets) *launchSets = profSets;
+    if (blocks) *blocks = profBlocks;
+    const size_t n = std::min(cap, profMs.size());
+    for (size_t i = 0; i < n; ++i) msOut[i] = profMs[i];
+    return (int)profMs.size();
+}
+
+// One launch level of a multi-block launch. When every island shape of the level has its specialised kernel compiled
+// (jit.cpp) the level runs as one launch per shape plus an interpreter launch for the islands no shape covers
+// (stateless mixers and roots); until then the whole level goes through the interpreter kernel.
+void Engine::launchLevelBatch(const Plan& p, size_t l, uint32_t batch, uint32_t arenaFloats) {
+    const uint32_t b = p.levelOffsets[l], e = p.levelOffsets[l + 1];
+    if (e <= b) return;
+    bool spec = specialize != 0 && !p.shapes.empty();
+    std::vector<std::pair<hipFunction_t, const Plan::SpecShape*>> fns;   // function null: the shape is not compiled (yet)
+    struct InterpRun { uint32_t begin, count; };                          // contiguous stretches of specLists the interpreter kernel renders
+    std::vector<InterpRun> interpRuns;
+    if (spec) {
+        bool any = false;
+        int specTaken = 0;
+        for (const Plan::SpecShape& sh : p.shapes) {
+            if (sh.level != (uint32_t)l) continue;
+            // (the level's shapes are listed biggest first, plan.cpp: the first `maxShapeLaunches` compiled ones get their kernels)
+            hipFunction_t fn = specTaken < maxShapeLaunches ? sh.entry->function(device) : nullptr;
+            if (fn) ++specTaken;
+            any = any || fn != nullptr;
+            // A launch whose islands all belong to roots that do not run (a replaced root once its fade-out has settled stays in
+            // the plan until the next commit) would start workgroups that return at once — and, as a second launch of its
+            // level, cost a fork to a side stream and a join. The host mirrors the root fades (mirrorRootFades), and launch
+            // sets are only rendered while every running root's fade is settled: what runs does not change inside a set.
+            if (skipIdleLaunches && !anyRootRuns(sh.roots, hGlobals.numOut)) { st.idleLaunchesSkipped++; continue; }
+            if (fn) { fns.emplace_back(fn, &sh); continue; }
+            // not compiled (yet), or beyond the launch cap: joins the interpreter run that ends where its list begins, or starts one
+            if (!interpRuns.empty() && interpRuns.back().begin + interpRuns.back().count == sh.listBegin) interpRuns.back().count += sh.count;
+            else interpRuns.push_back({sh.listBegin, sh.count});
+        }
+        if (!any) spec = false;
+    }
+    if (!spec) { launch_level(stream, p.view, dRecs, dHbm, dGlobals, dLcg, b, e - b, p.levelLdsBytes[l], batch, arenaFloats, statelessRows); islandBlocksInterp += (uint64_t)(e - b) * batch; debugSync("set: interpreter level", (unsigned)l, batch); return; }
+    // The launches of one level are independent of each other (different islands): with more than one they go to side
+    // streams forked from / joined to the engine's stream, so two shapes of 64 islands each fill 128 CUs at once
+    // instead of 64 CUs twice.
+    uint32_t rb = p.restOffsets[l], re = p.restOffsets[l + 1];
+    if (re > rb && skipIdleLaunches && l < p.restRoots.size() && !anyRootRuns(p.restRoots[l], hGlobals.numOut)) { re = rb; st.idleLaunchesSkipped++; }
+    const size_t launches = fns.size() + interpRuns.size() + (re > rb ? 1 : 0);
+    if (launches == 0) return;
+    const bool fork = launches > 1;
+    if (fork) {
+        while (auxStreams.size() < launches - 1) {
+            hipStream_t s2 = nullptr; hipEvent_t ev = nullptr;
+            // a side stream must not share a hardware queue with the engine's stream (the runtime hands queues out round-robin
+            // per priority class; in a process with many streams two shapes of C4 landed on one queue and ran back to back,
+            // 12.9 -> 25 us per block): side streams alternate between the two other priority classes
+            int least = 0, greatest = 0;
+            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+            const int prio = (auxStreams.size() % 2 == 0) ? greatest : least;
+            if (least == greatest || hipStreamCreateWithPriority(&s2, hipStreamNonBlocking, prio) != hipSuccess)
+                HIP_WARN(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+            HIP_WARN(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            auxStreams.push_back(s2); auxDone.push_back(ev);
+        }
+        if (!forkEvent) HIP_WARN(hipEventCreateWithFlags(&forkEvent, hipEventDisableTiming));
+        HIP_WARN(hipEventRecord(forkEvent, stream));
+    }
+    size_t k = 0;
+    auto streamFor = [&](size_t idx) -> hipStream_t {
+        if (!fork || idx == 0) return stream;
+        hipStream_t s2 = auxStreams[idx - 1];
+        HIP_WARN(hipStreamWaitEvent(s2, forkEvent, 0));
+        return s2;
+    };
+    for (const InterpRun& r : interpRuns) {   // these shapes' islands go through the interpreter kernel (their lists have the levelIslands entry format)
+        PlanView pv = p.view;
+        pv.levelIslands = p.dSpecLists;
+        launch_level(streamFor(k++), pv, dRecs, dHbm, dGlobals, dLcg, r.begin, r.count, p.levelLdsBytes[l], batch, arenaFloats, statelessRows);
+        islandBlocksInterp += (uint64_t)r.count * batch;
+    }
+    for (auto& f : fns) {
+        hipStream_t st_ = streamFor(k++);
+        PlanView pv = p.view;
+        uint32_t* recs = dRecs; float* hbm = dHbm; const Globals* g = dGlobals; const uint32_t* lcg = dLcg;
+        const uint32_t* list = p.dSpecLists + f.second->listBegin;
+        // the stream ring sits behind the `batch` block slices of this launch set
+        uint32_t bt = batch, af = arenaFloats, sb = batch * arenaFloats, ss = p.numStreamBuffers * (uint32_t)blockSize;
+        void* args[] = {&pv, &recs, &hbm, &g, &lcg, &list, &bt, &af, &sb, &ss};
+        const uint32_t gy = f.second->stateless ? std::max(1u, std::min(batch, statelessRows)) : 1u;
+        HIP_WARN(hipModuleLaunchKernel(f.first, f.second->count, gy, 1, kThreads, 1, 1, 0, st_, args, nullptr));
+        st.specLaunches++;
+        islandBlocksSpec += (uint64_t)f.second->count * batch;
+        debugSync("set: specialised shape", f.second->count, batch);
+    }
+    if (re > rb) {
+        PlanView pv = p.view;
+        pv.levelIslands = p.dRestIslands;
+        launch_level(streamFor(k++), pv, dRecs, dHbm, dGlobals, dLcg, rb, re - rb, p.levelLdsBytes[l], batch, arenaFloats, statelessRows);
+        islandBlocksInterp += (uint64_t)(re - rb) * batch;
+        debugSync("set: interpreter rest", re - rb, batch);
+    }
+    if (fork) {
+        for (size_t i = 1; i < launches; ++i) {
+            HIP_WARN(hipEventRecord(auxDone[i - 1], auxStreams[i - 1]));
+            HIP_WARN(hipStreamWaitEvent(stream, auxDone[i - 1], 0));
+        }
+    }
+}
+
+// the convolve nodes of level l over a whole launch set: four launches (fft, mac, ifft, finish: conv.hip, "multi-block launches")
+void Engine::launchConvolveBatch(const Plan& p, size_t l, uint32_t batch, uint32_t arenaFloats) {
+    const uint32_t cb = p.convLevelOffsets[l], ce = p.convLevelOffsets[l + 1];
+    uint32_t mains = 0;
+    while (cb + mains < ce && (p.convWork[cb + mains] >> 16) == 0u) ++mains;   // main entries lead a level's work list
+    if (!mains) return;
+    // which nodes of the level have long-partition spectra (an IR can be replaced without a re-plan: looked up per launch set)
+    bool anyShortPath = false;
+    uint32_t stateBlocks = 1;
+    for (uint32_t k = 0; k < mains; ++k) {
+        const uint32_t ci = p.convWork[cb + k] & 0xFFFFu;
+        auto it = ci < p.convNodeIds.size() ? nodes.find(p.convNodeIds[ci]) : nodes.end();
+        if (it == nodes.end() || it->second.convQp == 0u) { anyShortPath = true; continue; }
+        stateBlocks = std::max(stateBlocks, std::max(it->second.convHistBlocks, it->second.convP));
+    }
+    const uint32_t longRows = (convLong && convMaxQp) ? convMaxQp - 1u : 0u;
+    const bool longSet = longRows && batch >= 8u && (batch & 7u) == 0u;
+    {   // the scratch holds per-node headers (which convolver's spectra its ring carries from set to set, conv_long.inc): they mean
+        // something only under the layout they were written for — a new allocation or another set geometry starts from zeroed scratch
+        const uint64_t key = ((uint64_t)(uint32_t)batchBlocks << 32) | longRows;
+        if (key != convScratchKey && dConvScratch) { HIP_WARN(hipMemsetAsync(dConvScratch, 0, convScratchFloats * sizeof(float), stream)); convScratchKey = key; }
+    }
+    if (longSet && stateBlocks > 1u) {
+        convLongSets++;
+        // staleness is a fact of a NODE (its header's H_OVL_STALE), not of the engine: a plan without this node may render
+        // block-at-a-time in between, and the node must still be repaired when a later plan brings it back
+        for (uint32_t k = 0; k < mains; ++k) {
+            const uint32_t ci = p.convWork[cb + k] & 0xFFFFu;
+            if (ci < p.convNodeIds.size()) convStaleNodes.insert(p.convNodeIds[ci]);
+        }
+    }
+    if (!longSet) fixConvOverlaps(p);
+    launch_convolve_batch(stream, p.view, dRecs, dHbm, dGlobals, cb, mains, batch, arenaFloats, dConvScratch, (uint32_t)batchBlocks, (uint32_t)convMfma,
+                          convMinP <= convolve_mfma_max_partitions(), convMaxP > convolve_mfma_max_partitions(), longRows, anyShortPath, stateBlocks,
+                          longSet ? setInDirect : nullptr, setNumIn, longSet ? setOutDirect : nullptr, setNumOut);
+}
+
+// A plan that consists of long-partition convolvers only (BASELINE configs[2]: root(convolve(in)) per channel — in and root folded into
+// the node's launches) needs neither the copy of the caller's input blocks into the arenas nor the bus-sum epilogue of a launch set:
+// the long-partition kernels read the [block][channel][frame] input where it lies, and when every output channel of the call is the
+// folded root of exactly one running convolver they write the caller's output buffer themselves (r05: 8.4 + 9.5 us of a 118 us C3 set).
+void Engine::chooseConvDirectIo(const Plan& p, size_t nIn, size_t nOut, uint32_t batch, bool haveIn, bool& dIn, bool& dOut) {
+    dIn = dOut = false;
+    if (!convDirectIo || !convLong || !convMaxQp || p.convs.empty() || !p.levelIslands.empty() || !p.hosts.empty() || !p.taps.empty()) return;
+    if (batch < 8u || (batch & 7u) != 0u) return;
+    std::vector<uint32_t> fused;
+    for (size_t ci = 0; ci < p.convs.size(); ++ci) {
+        auto it = ci < p.convNodeIds.size() ? nodes.find(p.convNodeIds[ci]) : nodes.end();
+        if (it == nodes.end() || it->second.convQp == 0u) return;            // a node without long-partition spectra: the 512-partition kernels read the arenas
+        if (p.convs[ci].fuseRootRec != kNone) fused.push_back(p.convs[ci].fuseRootRec);
+    }
+    dIn = haveIn;
+    std::vector<uint8_t> seen(nOut, 0);
+    size_t covered = 0;
+    for (int32_t id : p.rootIds) {
+        auto it = nodes.find(id);
+        if (it == nodes.end()) return;
+        const Node& r = it->second;
+        const bool on = r.target > 0.5f, settled = std::fabs(r.target - r.gain) <= 1e-6f;
+        if (!((on || !settled) && r.channel >= 0 && (size_t)r.channel < nOut)) continue;   // not running (or a channel the call does not ask for)
+        if (std::find(fused.begin(), fused.end(), r.rec) == fused.end() || seen[(size_t)r.channel]) return;
+        seen[(size_t)r.channel] = 1; ++covered;
+    }
+    dOut = covered == nOut && nOut > 0;
+}
+
+void Engine::fixConvOverlaps(const Plan& p) {
+    if (convStaleNodes.empty() || p.convs.empty() || !dConvScratch) return;
+    bool any = false;
+    for (int32_t id : p.convNodeIds) any = convStaleNodes.erase(id) > 0 || any;      // (the kernels return early for nodes whose header is not stale)
+    if (!any) return;
+    launch_convolve_fix_overlap(stream, p.view, dRecs, dHbm, dGlobals, 0u, (uint32_t)p.convWork.size(), dConvScratch, (uint32_t)batchBlocks,
+                                (convLong && convMaxQp) ? convMaxQp - 1u : 0u, convMaxP);
+}
+
+void Engine::enqueueBatch(const Plan& p, uint32_t batch, float* outRing) {
+    if (!outRing) outRing = dOutRing;
+    const uint32_t arenaFloats = p.numHbmBuffers * (uint32_t)blockSize;
+    const size_t L = p.levelOffsets.size() - 1;
+    const bool prof = profileLaunches && (profSetCounter++ % profileEvery) == 0u;
+    for (size_t l = 0; l < L; ++l) {
+        const uint32_t b = p.levelOffsets[l], e = p.levelOffsets[l + 1];
+        if (e <= b && p.convLevelOffsets[l + 1] <= p.convLevelOffsets[l]) continue;
+        if (prof) (void)hipEventRecord(profEvent(), stream);
+        launchLevelBatch(p, l, batch, arenaFloats);
+        launchConvolveBatch(p, l, batch, arenaFloats);
+        if (prof) { (void)hipEventRecord(profEvent(), stream); profSlots.push_back((uint32_t)l); }
+    }
+    if (prof && !setOutDirect) (void)hipEventRecord(profEvent(), stream);      // (a direct-I/O set has no epilogue to bracket: two stream operations less per set)
+    if (setOutDirect) {
+        // the convolvers wrote the caller's buffer themselves (chooseConvDirectIo): what is left of the epilogue is the device's sample
+        // clock, moved on by a parameter patch (applied in stream order with the next call's patches)
+        // (r06: ... and only once something is about to READ it — a stream of such sets has no island, no epilogue and no other
+        //  reader of the clock, and a patch launch per set was 4 us of kernel plus its launch gap in front of every 70 us of work:
+        //  flushPending brings the device's clock up to the host's before the first launch that is not another direct set)
+        deviceClockBehind = true;
+    } else {
+        launch_epilogue_batch(stream, p.view, dRecs, dHbm, dGlobals, outRing, batch, arenaFloats, armFlag, armValue);
+        if (armFlag && batch == 1u) flagArmed = true;
+    }
+    debugSync("set: epilogue", batch);
+    if (prof && !setOutDirect) { (void)hipEventRecord(profEvent(), stream); profSlots.push_back((uint32_t)L); }
+    if (prof) { profSets++; profBlocks += batch; if (profMs.size() <= L) profMs.resize(L + 1, 0.0); }     // (slot L = the epilogue, 0 for direct sets)
+}
+
+bool Engine::specBlockOk(const Plan& p) const { return specBlocks && p.convs.empty() && p.hosts.empty() && specReady(p); }
+
+void Engine::enqueueSpecBlock(const Plan& p, float* outRing) {
+    if (!outRing) outRing = dOutRing;
+    const uint32_t arenaFloats = p.numHbmBuffers * (uint32_t)blockSize;
+    const size_t L = p.levelOffsets.size() - 1;
+    for (size_t l = 0; l < L; ++l) launchLevelBatch(p, l, 1u, arenaFloats);
+    launch_epilogue(stream, p.view, dRecs, dHbm, dGlobals, outRing, armFlag, armValue);
+    if (armFlag) flagArmed = true;
+    debugSync("block: specialised levels + epilogue");
+    st.specFadeBlocks++;
+}
+
+int Engine::processBlocks(const float* inDev, size_t nIn, float* outDev, size_t nOut, size_t numBlocks, int64_t sampleTime) {
+    RenderGuard lock(*this);
+    if (dry) return kNoDevice;
+    if (hostBlockSize != blockSize) return kBlockTooLarge;     // (the device-resident layout is [block][channel][blockSize <= 512])
+    if (hipSetDevice(device) != hipSuccess) return kHipError;
+    int rc = enqueueBlocks(inDev, nIn, outDev, nOut, numBlocks, sampleTime);
+    if (rc != kOk) return rc;
+    HIP_OK(hipStreamSynchronize(stream));
+    HIP_OK(hipGetLastError());
+    if (profUsed) profCollect();
+    freeDeferred();
+    return kOk;
+}
+
+// `mu` held, device current. Everything is enqueued on `stream`; the caller synchronises.
+int Engine::enqueueBlocks(const float* inDev, size_t nIn, float* outDev, size_t nOut, size_t numBlocks, int64_t sampleTime) {
+    if (nIn > kMaxHostIn || nOut > kMaxOutBus) return kTooManyChannels;
+    armFlag = nullptr; flagArmed = false;      // (no launch set publishes elemhip_process' completion word)
+    int rc = swapInPending();
+    if (rc != kOk) return rc;
+    if (!current || numBlocks == 0) return kOk;
+    Plan& p = *current;
+    if (p.packedRootChannels > 0 && nOut < (size_t)p.packedRootChannels) {      // (plan.cpp `pack_roots`: a packed root would not run in the reference)
+        std::fprintf(stderr, "[elemhip] pack_roots: this plan needs calls with at least %d output channels\n", p.packedRootChannels);
+        return kInvalidPropertyValue;
+    }
+    const size_t bs = (size_t)blockSize;
+    const bool graphOk = useGraph && p.hosts.empty() && !debugSyncOn();   // call-out nodes synchronise inside a block: nothing to capture
+    const bool haveIn = nIn > 0 && inDev != nullptr;
+    const size_t G = graphOk ? (size_t)graphBlocks : 1;
+    rc = ensureOutRing(std::max<size_t>(nOut, 1) * bs * G);
+    if (rc != kOk) return rc;
+
+    setGlobalsFor(nIn, nOut, bs, sampleTime);
+    size_t done = 0;
+    while (done < numBlocks) {
+        if (batchBlocks > 1 && numBlocks - done > 1 && batchEligible(p, nOut)) {
+            // ---- multi-block launches: one kernel per level renders `chunk` blocks (kernels.hip) ----
+            const size_t setCap = std::min((size_t)batchBlocks, maxSetBlocks(p));
+            const size_t chunk = std::min(setCap, numBlocks - done);
+            rc = ensureHbm(arenaBuffers(p, setCap));
+            if (rc != kOk) return rc;
+            rc = ensureOutRing(std::max<size_t>(nOut, 1) * bs * (size_t)batchBlocks);
+            if (rc != kOk) return rc;
+            if (!p.convs.empty()) {
+                const size_t need = p.convs.size() * convolve_batch_scratch_floats((uint32_t)batchBlocks, (convLong && convMaxQp) ? convMaxQp - 1u : 0u);
+                if (need > convScratchFloats) {
+                    HIP_OK(hipStreamSynchronize(stream));
+                    if (dConvScratch) (void)hipFree(dConvScratch);
+                    dConvScratch = nullptr; convScratchFloats = 0;
+                    HIP_OK(hipMalloc(&dConvScratch, need * sizeof(float)));
+                    convScratchFloats = need;
+                    convScratchKey = ~0ull;        // (its per-node headers are garbage: zeroed before the first launch that reads them)
+                }
+            }
+            setInRing(nullptr, 0);
+            hGlobals.blockSlot = 0;
+            bool dIn = false, dOut = false;
+            chooseConvDirectIo(p, nIn, nOut, (uint32_t)chunk, haveIn, dIn, dOut);
+            float* const outTarget = (outDev && nOut > 0) ? outDev + done * nOut * bs : nullptr;
+            setInDirect = dIn ? inDev + done * nIn * bs : nullptr; setNumIn = (uint32_t)nIn;
+            setOutDirect = dOut ? (outTarget ? outTarget : dOutRing) : nullptr; setNumOut = (uint32_t)nOut;
+            if (dIn || dOut) convDirectSets++;
+            nextSetDirect = dOut;
+            if (haveIn && !dIn)   // host inputs of block b -> arena buffers 0..nIn-1 of block b's arena
+                HIP_OK(hipMemcpy2DAsync(dHbm, (size_t)p.numHbmBuffers * bs * sizeof(float), inDev + done * nIn * bs, nIn * bs * sizeof(float),
+                                        nIn * bs * sizeof(float), chunk, hipMemcpyDeviceToDevice, stream));
+            rc = flushPending();
+            nextSetDirect = false;
+            if (rc != kOk) return rc;
+            // the set's epilogue sums the roots straight into the caller's [block][channel][frame] buffer (r04: into the engine's ring and
+            // a device-to-device copy behind it — 5.6 us of a 135 us C3 set, 100 us of a C4 set)
+            enqueueBatch(p, (uint32_t)chunk, outTarget);
+            setInDirect = nullptr; setOutDirect = nullptr;
+            hGlobals.sampleTime += (int64_t)(chunk * bs);
+            done += chunk;
+            st.blocksRendered += chunk;
+            promoteDeferredShapes();
+            st.batchLaunches++;
+            continue;
+        }
+        if (specBlockOk(p)) {
+            // ---- one block through the specialised kernels (root fades running, or a call of one block) ----
+            rc = ensureHbm(arenaBuffers(p, 1));
+            if (rc != kOk) return rc;
+            if (hGlobals.ringSlots != 1u || hGlobals.blockSlot != 0u) {
+                hGlobals.ringSlots = 1u; hGlobals.blockSlot = 0u;
+                patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, ringSlots) / 4), 1u, 0u});
+                patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, blockSlot) / 4), 0u, 0u});
+            }
+            setInRing(nullptr, 0);
+            if (haveIn) HIP_OK(hipMemcpyAsync(dHbm, inDev + done * nIn * bs, nIn * bs * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            rc = flushPending();
+            if (rc != kOk) return rc;
+            curBlockTime = hGlobals.sampleTime;
+            if (batchEligible(p, nOut, true)) enqueueBatch(p, 1u); else enqueueSpecBlock(p);
+            if (outDev && nOut > 0)
+                HIP_OK(hipMemcpyAsync(outDev + done * nOut * bs, dOutRing, nOut * bs * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            mirrorRootFades(p, (uint32_t)bs, (uint32_t)nOut, (uint32_t)nIn);
+            hGlobals.sampleTime += (int64_t)bs;
+            done += 1;
+            st.blocksRendered += 1;
+            promoteDeferredShapes();
+            continue;
+        }
+        const size_t chunk = std::min(G, numBlocks - done);
+        // ring geometry for this chunk
+        if (hGlobals.ringSlots != (uint32_t)G || hGlobals.blockSlot != 0) {
+            hGlobals.ringSlots = (uint32_t)G; hGlobals.blockSlot = 0;
+            patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, ringSlots) / 4), (uint32_t)G, 0u});
+            patches.push_back(Patch{2u, (uint32_t)(offsetof(Globals, blockSlot) / 4), 0u, 0u});
+        }
+        // host inputs: block 0 of the chunk is copied here, the epilogue of block k stages block k + 1
+        setInRing(haveIn ? inDev + done * nIn * bs : nullptr, haveIn ? (uint32_t)chunk : 0u);
+        if (haveIn) HIP_OK(hipMemcpyAsync(dHbm, inDev + done * nIn * bs, nIn * bs * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        rc = flushPending();
+        if (rc != kOk) return rc;
+        fixConvOverlaps(p);      // (convolve nodes a long-partition set rendered last: their overlap, before block-at-a-time launches read it)
+        // (a plan is captured at its third block-at-a-time chunk: a live graph's plan renders the two blocks of its root fades this
+        //  way, then launch sets take over and the next commit replaces it — a capture would be made and thrown away every time)
+        if (graphOk && chunk == G && (p.graphExec || ++p.blockChunks > 2u)) {
+            if (!p.graphExec || p.graphBlocks != (int)G) {
+                if (p.graphExec) { (void)hipGraphExecDestroy(p.graphExec); p.graphExec = nullptr; }
+                hipGraph_t graph = nullptr;
+                HIP_OK(hipStreamSynchronize(stream));
+                const auto tc0 = std::chrono::steady_clock::now();
+                const uint64_t ibi = islandBlocksInterp;
+                HIP_OK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+                for (size_t b = 0; b < G; ++b) enqueueBlock(p);
+                HIP_OK(hipStreamEndCapture(stream, &graph));
+                islandBlocksInterp = ibi;                                   // (counted per replay below)
+                HIP_OK(hipGraphInstantiate(&p.graphExec, graph, nullptr, nullptr, 0));
+                (void)hipGraphDestroy(graph);
+                p.graphBlocks = (int)G;
+                st.graphCaptures++;
+                st.lastGraphCaptureMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count();
+            }
+            HIP_OK(hipGraphLaunch(p.graphExec, stream));
+            st.graphReplays++;
+            islandBlocksInterp += (uint64_t)G * p.levelIslands.size();
+        } else {
+            for (size_t b = 0; b < chunk; ++b) { curBlockTime = hGlobals.sampleTime + (int64_t)(b * bs); enqueueBlock(p); }
+        }
+        if (outDev && nOut > 0)
+            HIP_OK(hipMemcpyAsync(outDev + done * nOut * bs, dOutRing, chunk * nOut * bs * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        // host mirrors of device-side block state
+        for (size_t b = 0; b < chunk; ++b) mirrorRootFades(p, (uint32_t)bs, (uint32_t)nOut, (uint32_t)nIn);
+        hGlobals.sampleTime += (int64_t)(chunk * bs);
+        hGlobals.blockSlot = (uint32_t)((hGlobals.blockSlot + chunk) % G);
+        done += chunk;
+        st.blocksRendered += chunk;
+        promoteDeferredShapes();
+    }
+    return kOk;
+}
+
+int Engine::ensureHostStaging(size_t outFloats, size_t inFloats) {
+    if (!ioStream) {
+        HIP_OK(hipStreamCreateWithFlags(&ioStream, hipStreamNonBlocking));
+        for (int k = 0; k < 2; ++k) {
+            HIP_OK(hipEventCreateWithFlags(&evIn[k], hipEventDisableTiming));
+            HIP_OK(hipEventCreateWithFlags(&evRendered[k], hipEventDisableTiming));
+            HIP_OK(hipEventCreateWithFlags(&evOut[k], hipEventDisableTiming));
+        }
+    }
+    auto grow = [&](float* (&h)[2], float* (&d)[2], size_t& have, size_t want) -> int {
+        if (want <= have) return kOk;
+        HIP_OK(hipStreamSynchronize(stream));
+        HIP_OK(hipStreamSynchronize(ioStream));
+        // the new buffers first: a failed allocation leaves the old pair (and `have`) as they were
+        float* nh[2] = {nullptr, nullptr}; float* nd[2] = {nullptr, nullptr};
+        bool ok = true;
+        for (int k = 0; k < 2 && ok; ++k)
+            ok = hipHostMalloc((void**)&nh[k], want * sizeof(float), hipHostMallocDefault) == hipSuccess && hipMalloc(&nd[k], want * sizeof(float)) == hipSuccess;
+        if (!ok) {
+            for (int k = 0; k < 2; ++k) { if (nh[k]) (void)hipHostFree(nh[k]); if (nd[k]) (void)hipFree(nd[k]); }
+            (void)hipGetLastError();
+            return kHipError;
+        }
+        for (int k = 0; k < 2; ++k) {
+            if (h[k]) (void)hipHostFree(h[k]);
+            if (d[k]) (void)hipFree(d[k]);
+            h[k] = nh[k]; d[k] = nd[k];
+        }
+        have = want;
+        return kOk;
+    };
+    int rc = grow(hStageOut, dStageOut, stageOutFloats, outFloats);
+    if (rc != kOk) return rc;
+    return grow(hStageIn, dStageIn, stageInFloats, inFloats);
+}
+
+// Runtime::process for a whole offline render (offline-renderer/index.ts:87-133): planar host arrays of `numFrames` frames.
+// Set k (up to `batch_blocks` blocks) is gathered into pinned half k % 2, copied in on the copy stream, rendered on the
+// engine's stream into device half k % 2, copied out on the copy stream and scattered to the caller's arrays while set
+// k + 1 renders. The render lock is taken per set: a commit on another thread lands between two sets (block boundary).
+int Engine::processBlocksHost(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime) {
+    if (dry) return kNoDevice;
+    if (nIn > kMaxHostIn || nOut > kMaxOutBus) return kTooManyChannels;
+    if ((nIn && !in) || (nOut && !out)) return kInvalidInstructionFormat;
+    const size_t bs = (size_t)blockSize;
+    // whole HOST blocks, like the reference's block loop (a host block = hostBlockSize / blockSize engine blocks)
+    const size_t hb = (size_t)hostBlockSize;
+    bool tapSlices = hb % bs != 0;          // ragged slices (a host block that no k divides evenly): launch sets hold whole engine blocks
+    if (hb != bs && !tapSlices) { std::lock_guard<std::mutex> lock(mu); tapSlices = !tapNodeIds.empty(); }
+    if (tapSlices) {
+        // taps under a host block longer than the engine's: every slice needs its own stretch of the shared tap buffers (setTapSlice),
+        // which launch sets do not do — host block by host block through process()
+        std::vector<const float*> ip(nIn);
+        std::vector<float*> op(nOut);
+        std::vector<float> tailIn, tailOut;
+        for (size_t f0 = 0; f0 < numFrames; f0 += hb) {
+            const size_t nf = std::min(hb, numFrames - f0);
+            for (size_t c = 0; c < nIn; ++c) ip[c] = in[c] + f0;
+            for (size_t c = 0; c < nOut; ++c) op[c] = out[c] + f0;
+            if (nf < hb) {
+                // the last, partly filled host block is still a whole block to the engine (offline-renderer/index.ts:104-131: inputs
+                // padded with zeros, the frames beyond the caller's arrays dropped)
+                tailIn.assign(nIn * hb, 0.0f); tailOut.assign(nOut * hb, 0.0f);
+                for (size_t c = 0; c < nIn; ++c) { std::memcpy(tailIn.data() + c * hb, in[c] + f0, nf * sizeof(float)); ip[c] = tailIn.data() + c * hb; }
+                for (size_t c = 0; c < nOut; ++c) op[c] = tailOut.data() + c * hb;
+            }
+            const int rc = process(ip.data(), nIn, op.data(), nOut, hb, sampleTime + (int64_t)f0);
+            if (rc != kOk) return rc;
+            if (nf < hb) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + f0, tailOut.data() + c * hb, nf * sizeof(float));
+        }
+        return kOk;
+    }
+    const size_t numBlocks = ((numFrames + hb - 1) / hb) * (hb / bs);
+    if (numBlocks == 0) return kOk;
+    size_t setBlocks;
+    {
+        RenderGuard lock(*this);
+        if (hipSetDevice(device) != hipSuccess) return kHipError;
+        setBlocks = (size_t)std::max(1, batchBlocks);
+        if (setBlocks < 8) setBlocks = std::min<size_t>(64, numBlocks);     // per-block launch path: still stage whole chunks
+        setBlocks = std::min(setBlocks, numBlocks);
+        // launch sets hold whole HOST blocks: a newer render sequence is adopted at a set boundary (enqueueBlocks), and the reference
+        // swaps sequences at host-block boundaries only (Runtime.h:277-285)
+        if (hb > bs) setBlocks = std::min(numBlocks, std::max(hb / bs, setBlocks / (hb / bs) * (hb / bs)));
+        int rc = ensureHostStaging(setBlocks * std::max<size_t>(nOut, 1) * bs, setBlocks * std::max<size_t>(nIn, 1) * bs);
+        if (rc != kOk) return rc;
+    }
+    const size_t numSets = (numBlocks + setBlocks - 1) / setBlocks;
+    auto scatter = [&](size_t k) {     // pinned half -> the caller's planar arrays
+        const size_t b0 = k * setBlocks, nb = std::min(setBlocks, numBlocks - b0);
+        const float* src = hStageOut[k & 1];
+        auto part = [&](size_t bBegin, size_t bEnd) {
+            for (size_t b = bBegin; b < bEnd; ++b) {
+                const size_t f0 = (b0 + b) * bs;
+                if (f0 >= numFrames) break;                     // (the engine blocks that only fill up the last host block)
+                const size_t n = std::min(bs, numFrames - f0);
+                for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + f0, src + (b * nOut + c) * bs, n * sizeof(float));
+            }
+        };
+        // One thread copies ~10 GB/s; a set of many channels (C4: 128 outputs x 1024 blocks = 268 MB per 12.6 ms of rendering)
+        // needs more than that to stay hidden behind the next set, so big sets are cut over a few threads by block range.
+        const size_t bytes = nb * nOut * bs * sizeof(float);
+        size_t threads = bytes >= (16u << 20) ? std::min<size_t>(8, std::max<size_t>(1, std::thread::hardware_concurrency() / 4)) : 1;
+        threads = std::min(threads, nb);
+        if (threads <= 1) return part(0, nb);
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < threads; ++t) pool.emplace_back(part, nb * t / threads, nb * (t + 1) / threads);
+        part(0, nb / threads);
+        for (auto& th : pool) th.join();
+    };
+    int result = kOk;
+    size_t issued = 0, scattered = 0;
+    // a failing HIP call ends the loop; the tail below drains both streams, releases what was deferred and reports the code —
+    // `out` then holds the sets scattered so far (whole launch sets, in order), nothing is left in flight
+#define HOST_TRY(call) { if ((call) != hipSuccess) { std::fprintf(stderr, "[elemhip] %s failed: %s\n", #call, hipGetErrorString(hipGetLastError())); result = kHipError; break; } }
+    for (size_t k = 0; k < numSets; ++k) {
+        const size_t b0 = k * setBlocks, nb = std::min(setBlocks, numBlocks - b0);
+        const int half = (int)(k & 1);
+        if (nIn) {
+            if (k >= 2) HOST_TRY(hipEventSynchronize(evIn[half]));     // the H2D of set k - 2 has left this pinned half
+            float* dst = hStageIn[half];
+            for (size_t b = 0; b < nb; ++b) {
+                const size_t f0 = (b0 + b) * bs;
+                const size_t n = f0 < numFrames ? std::min(bs, numFrames - f0) : 0;
+                for (size_t c = 0; c < nIn; ++c) {
+                    float* d = dst + (b * nIn + c) * bs;
+                    if (n) std::memcpy(d, in[c] + f0, n * sizeof(float));
+                    if (n < bs) std::memset(d + n, 0, (bs - n) * sizeof(float));
+                }
+            }
+        }
+        {
+            RenderGuard lock(*this);
+            if (hipSetDevice(device) != hipSuccess) { result = kHipError; break; }
+            if (nIn) {
+                // (the copy stream is in order: this H2D runs behind the D2H of set k - 2, which waited for that set's render,
+                //  the last reader of this device half)
+                HOST_TRY(hipMemcpyAsync(dStageIn[half], hStageIn[half], nb * nIn * bs * sizeof(float), hipMemcpyHostToDevice, ioStream));
+                HOST_TRY(hipEventRecord(evIn[half], ioStream));
+                HOST_TRY(hipStreamWaitEvent(stream, evIn[half], 0));
+            }
+            if (k >= 2) HOST_TRY(hipStreamWaitEvent(stream, evOut[half], 0));   // the D2H of set k - 2 has drained this device half
+            int rc = enqueueBlocks(nIn ? dStageIn[half] : nullptr, nIn, nOut ? dStageOut[half] : nullptr, nOut, nb,
+                                   sampleTime + (int64_t)(b0 * bs));
+            if (rc != kOk) { result = rc; break; }
+            if (hb > bs) {                                      // (whole host blocks of hb / bs slices each: where each one ended, for the event relay)
+                const uint64_t per = hb / bs, base = st.blocksRendered - nb;
+                for (uint64_t e = per; e <= nb; e += per) { if (hostBlockEnds.size() >= 65536) hostBlockEnds.pop_front(); hostBlockEnds.push_back(base + e); }
+            }
+            HOST_TRY(hipEventRecord(evRendered[half], stream));
+            HOST_TRY(hipStreamWaitEvent(ioStream, evRendered[half], 0));
+            if (nOut) HOST_TRY(hipMemcpyAsync(hStageOut[half], dStageOut[half], nb * nOut * bs * sizeof(float), hipMemcpyDeviceToHost, ioStream));
+            HOST_TRY(hipEventRecord(evOut[half], ioStream));
+            issued = k + 1;
+        }
+        if (k >= 1) {   // set k - 1 arrives while set k renders
+            HOST_TRY(hipEventSynchronize(evOut[(k - 1) & 1]));
+            if (nOut) scatter(k - 1);
+            scattered = k;
+        }
+    }
+#undef HOST_TRY
+    if (issued > scattered && result == kOk) {       // the last set (every earlier one was scattered while its successor rendered)
+        const size_t last = issued - 1;
+        if (hipEventSynchronize(evOut[last & 1]) != hipSuccess) result = kHipError;
+        else if (nOut) scatter(last);
+    }
+    {
+        RenderGuard lock(*this);
+        if (hipStreamSynchronize(stream) != hipSuccess) result = result == kOk ? kHipError : result;
+        if (hipStreamSynchronize(ioStream) != hipSuccess) result = result == kOk ? kHipError : result;
+        if (hipGetLastError() != hipSuccess && result == kOk) result = kHipError;
+        if (profUsed) profCollect();
+        freeDeferred();
+    }
+    return result;
+}
+
+} // namespace elemhip

@@ -11,7 +11,8 @@
 // so far: an emitted frame is named by the absolute index of its first sample, and a device ring that keeps the last
 // `window + 8191` frames (device.h SCP_MASK) has every one of them, overruns included.
 //
-// Plain C++, no HIP: engine.cpp's relay and tests/native/event_replay_host.cpp compile the same text.
+// Plain C++, no HIP: the relay (engine_relay.cpp) and tests/native/event_replay_host.cpp compile the same text. Its neighbour
+// event_fold.h holds the relay's other host-only decisions (host blocks of a sliced window, meter / snapshot folds, scope runs).
 #pragma once
 #include <stdint.h>
 
