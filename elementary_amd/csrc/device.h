@@ -264,6 +264,13 @@ enum : uint32_t {
     CAP_RING = P0, CAP_MASK = P2, CAP_WRITE = 8, CAP_READ = 9, CAP_SCRATCH = 10, CAP_CHANGE = 11, CAP_READY = 12,
     CAP_CHANS = P3,      // mc.capture: capture channels (= children - 1; 0: the mono `capture` node), ring k at CAP_RING + k * (CAP_MASK + 1) floats
     CAP_CH = P4,         // mc.capture: the output channel this record renders (channel 0's record carries the recording state)
+    // The ring's capacity is CAP_MASK + 1 frames per channel: the reference's bitceil(sr), or — option "capture_history_blocks" — a whole
+    // relay window of takes on top of it. Recorded sample k lands at (CAP_ABS + scratch + k) & CAP_MASK, CAP_ABS = frames handed to the
+    // ring so far (mod 2^32); CAP_WRITE / CAP_READ stay the reference's positions mod CAP_REFMASK + 1 (at CAP_MASK == CAP_REFMASK
+    // CAP_ABS & CAP_MASK == CAP_WRITE). A ring with history carries a per-BLOCK log behind its last channel: CAP_LOGMASK + 1 entries of
+    // 4 dwords {CAP_BLK of the block, CAP_ABS at its end, gate fell in this block (0 / 1), 0} at entry CAP_BLK & CAP_LOGMASK (0: no log);
+    // CAP_BLK = blocks the node rendered so far. That is what a relay after every block would have seen (capture_replay.h).
+    CAP_REFMASK = P5, CAP_LOGMASK = P6, CAP_ABS = 13, CAP_BLK = 14,
     // meter: S0 min, S1 max, S2 readout count; snapshot: S0 previous trigger sample, S1 captured value, S2 capture count
     EVT_A = 8, EVT_B = 9, EVT_COUNT = 10,
     // ... and a per-BLOCK readout log (r05): ring of 4-dword entries {block number of this node, a, b, -} behind EVT_LOG with EVT_LOGMASK + 1

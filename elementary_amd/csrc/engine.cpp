@@ -506,6 +506,9 @@ int Engine::setOption(const std::string& key, double value) {
     // relay window (host blocks) the device rings of scope / fft nodes made FROM NOW ON keep: their blockwise relay stays exact over that
     // many blocks, ring overruns included (0: the reference's 8192 frames, windows as short as one block). Older nodes keep their ring.
     if (key == "event_history_blocks") { eventHistoryBlocks = (uint32_t)std::max(0, std::min((int)kEventLogEntries, (int)value)); return kOk; }
+    // the same for capture / mc.capture nodes made FROM NOW ON: a ring that keeps that many blocks of takes and a per-block log of what a
+    // relay after every block would have seen (capture_replay.h). 0: the reference's bitceil(sr) frames and a relay window of one block.
+    if (key == "capture_history_blocks") { captureHistoryBlocks = (uint32_t)std::max(0, std::min((int)kEventLogEntries, (int)value)); return kOk; }
     if (key == "batch_blocks") { batchBlocks = std::max(1, std::min(1024, (int)value)); return kOk; }      // blocks per multi-block launch (1 = off)
     if (key == "debug_build_delay_ms") { debugBuildDelayMs = std::max(0, (int)value); return kOk; }   // tests: stretches the unlocked part of a plan build
     if (key == "plan_cache") { planCache = std::max(0, std::min(2, (int)value)); islandCache.clear(); islandShapeCache.clear(); return kOk; }

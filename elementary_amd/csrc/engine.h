@@ -94,6 +94,11 @@ struct Node {
     // (host blocks) the ring was sized for by option "event_history_blocks" when the node was made (0: the plain 8192-frame ring)
     uint64_t ringWritten = 0;
     uint32_t ringRead = 0, ringFrames = 8192, historyBlocks = 0;
+    // capture / mc.capture: the relay window (host blocks) the ring was sized for by option "capture_history_blocks" when the node was
+    // made (0: the reference's bitceil(sr) frames, no per-block log; then ringFrames is that ring) and the absolute count of recorded
+    // frames the relay has drained so far (capture_replay.h; the device counts them in CAP_ABS). logRelayed: blocks of the log relayed.
+    uint32_t captureHistoryBlocks = 0;
+    uint64_t capRelayed = 0;
     uint32_t convSlices = 1;    // convolve: helper slices its current impulse response wants (conv.hip)
     uint32_t convQp = 0, convHistBlocks = 0, convP = 0;   // convolve: long-partition tap rows (0: none), blocks of its input ring, 512-partitions (conv_long.inc)
     bool mc = false;            // multi-output node (mc.*): one record per output channel, planned as one entry per channel
@@ -315,6 +320,7 @@ private:
     void* dFftTables[13] = {};             // [log2 size]: `size` doubles of window, then `size` (re, im) double pairs
     int  ensureFftTables(uint32_t size);
     uint8_t* dFft = nullptr; uint8_t* hFft = nullptr; size_t fftBytes = 0;
+    uint32_t captureHistoryBlocks = 0; // option "capture_history_blocks": relay window (host blocks) of takes the rings of NEW capture / mc.capture nodes keep (0: off)
     uint32_t eventHistoryBlocks = 0;   // option "event_history_blocks": relay window (host blocks) the rings of NEW scope / fft nodes keep (0: off)
     uint64_t fftLaunches = 0, fftFrames = 0;   // relay launches / frames transformed since the handle was made (describe_plan)
     // the relay's readers, one per node kind, over the context of one relay (engine_relay.cpp): they fetch off the render lock and
@@ -439,6 +445,8 @@ private:
     int  uploadRing(Node& n, const void* words, size_t count);
     void freeRec(uint32_t rec);                            // gc: the record back to the free list, queued writes to it dropped
     int  allocRing(Node& n, size_t floats);
+    size_t captureLogFloats(const Node& n) const;
+    void writeCaptureRing(Node& n, size_t cap);
     int  ensureResourceOnDevice(const ResourcePtr& r);
     int  setConvolverIr(Node& n, const ResourcePtr& res);
     ResourcePtr tapResource(const std::string& name);

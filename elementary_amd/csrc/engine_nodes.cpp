@@ -211,12 +211,28 @@ int Engine::createNode(int32_t id, const std::string& type) {   // Runtime.h:293
         rc = allocRing(nn, (size_t)(nn.op == OP_SCOPE ? 4u : 1u) * nn.ringFrames);
         if (rc == kOk) { writeParamPtr(nn, rec::SCP_RING, nn.ring.ptr); writeParam(nn, rec::SCP_MASK, nn.ringFrames - 1u); }
         if (rc == kOk && nn.op == OP_FFT) rc = ensureFftTables((uint32_t)analyzerDefaultSize(OP_FFT));
-    } else if (nn.op == OP_CAPTURE && !nn.mc) {                                   // Capture.h:17: ringBuffer(1, bitceil(sr)); (mc.capture: at commit)
-        const size_t cap = (size_t)bitceil((int)(size_t)sampleRate);
-        rc = allocRing(nn, cap);
-        if (rc == kOk) { writeParamPtr(nn, rec::CAP_RING, nn.ring.ptr); writeParam(nn, rec::CAP_MASK, (uint32_t)(cap - 1)); }
+    } else if (nn.op == OP_CAPTURE) {                                             // Capture.h:17: ringBuffer(1, bitceil(sr)); (mc.capture: at commit)
+        // Option "capture_history_blocks" = W: the device ring keeps W host blocks of takes on top of the reference's bitceil(sr) frames
+        // and a per-block log behind its last channel (device.h CAP_LOGMASK): everything a relay after every block would have drained
+        // over a W-block window is still there after it. The reference's positions stay mod bitceil(sr) (CAP_REFMASK). Kept to 2^24
+        // frames per channel like the scope ring.
+        const size_t cap = (size_t)bitceil((int)(size_t)sampleRate), top = (size_t)1 << 24;
+        nn.captureHistoryBlocks = cap >= top ? 0u : (uint32_t)std::min<size_t>(captureHistoryBlocks, (top - cap) / (size_t)std::max(1, hostBlockSize));
+        nn.ringFrames = nn.captureHistoryBlocks ? (uint32_t)bitceil((int)((size_t)nn.captureHistoryBlocks * (size_t)hostBlockSize + cap)) : (uint32_t)cap;
+        if (!nn.mc) {
+            rc = allocRing(nn, (size_t)nn.ringFrames + captureLogFloats(nn));
+            if (rc == kOk) { writeParamPtr(nn, rec::CAP_RING, nn.ring.ptr); writeCaptureRing(nn, cap); }
+        }
     }
     return rc;
+}
+
+// capture / mc.capture: floats of the per-block log behind the ring's channels, and the ring's masks into the record
+size_t Engine::captureLogFloats(const Node& n) const { return n.captureHistoryBlocks ? (size_t)kEventLogEntries * 4u : 0u; }
+void Engine::writeCaptureRing(Node& n, size_t cap) {
+    writeParam(n, rec::CAP_MASK, n.ringFrames - 1u);
+    writeParam(n, rec::CAP_REFMASK, (uint32_t)(cap - 1));
+    writeParam(n, rec::CAP_LOGMASK, n.captureHistoryBlocks ? kEventLogEntries - 1u : 0u);
 }
 
 int Engine::appendChild(int32_t parent, int32_t child, int32_t channel) {   // Runtime.h:335-366
@@ -634,15 +650,20 @@ int Engine::commit(std::unique_lock<std::mutex>& renderLock) {   // Runtime.h:20
             Node& n = it->second;
             const size_t chans = n.inlets.size() > 1 ? n.inlets.size() - 1 : 0, cap = (size_t)bitceil((int)(size_t)sampleRate);
             if (chans == 0) continue;
-            if (n.ring.bytes != chans * cap * sizeof(float)) {
-                const int rc = allocRing(n, chans * cap);
+            // (made under "capture_history_blocks": n.ringFrames frames per channel and the per-block log behind them, as the mono node's)
+            const size_t floats = chans * (size_t)n.ringFrames + captureLogFloats(n);
+            if (n.ring.bytes != floats * sizeof(float)) {
+                const int rc = allocRing(n, floats);
                 if (rc != kOk) return rc;
                 writeParamPtr(n, rec::CAP_RING, n.ring.ptr);
                 for (uint32_t cr : n.chanRecs) { writeRec(cr, rec::CAP_RING, shadow[(size_t)n.rec * kRecDwords + rec::CAP_RING]); writeRec(cr, rec::CAP_RING + 1, shadow[(size_t)n.rec * kRecDwords + rec::CAP_RING + 1]); }
             }
-            writeParam(n, rec::CAP_MASK, (uint32_t)(cap - 1));
+            writeCaptureRing(n, cap);
             writeParam(n, rec::CAP_CHANS, (uint32_t)chans);
             writeParam(n, rec::CAP_WRITE, 0u); writeParam(n, rec::CAP_READ, 0u);
+            // (the device ring is addressed by CAP_ABS: back to the write position with it. A ring with history keeps counting — a
+            //  relay after every block, which its relay reproduces, had drained everything before this commit.)
+            if (!n.captureHistoryBlocks) { writeParam(n, rec::CAP_ABS, 0u); n.capRelayed = 0; }
             ringsReset = true;
         }
         // (the reference drops the unread samples when the sequence is PUSHED, not when it is first rendered: an event poll between

@@ -5,6 +5,7 @@
 #include "fft_frames.h"
 #include "event_replay.h"
 #include "event_fold.h"
+#include "capture_replay.h"
 
 namespace elemhip {
 
@@ -196,37 +197,64 @@ int Engine::relayScope(RelayCtx& c, Node& n, const uint32_t* rc_, uint32_t order
 }
 
 // Capture.h:60-95 / mc/Capture.h:107-146: drain the ring(s) into the relay, emit once the gate fell
+// A node made with history (option "capture_history_blocks") under the blockwise relay: the per-block log says what a relay after every
+// block would have drained and when it would have emitted (capture_replay.h) — the window's frames come over in ONE stretch per
+// channel and are cut into those takes; the device's positions are left as such a relay would have left them. Its ring is addressed
+// by CAP_ABS, so the plain relay fetches the `avail` frames the reference's positions name from behind that count.
 int Engine::relayCapture(RelayCtx& c, Node& n, const uint32_t* rc_, uint32_t order) {
-    const uint32_t mask = shadow[(size_t)n.rec * kRecDwords + rec::CAP_MASK], cap = mask + 1u;
-    const uint32_t chans = n.mc ? shadow[(size_t)n.rec * kRecDwords + rec::CAP_CHANS] : 1u;
+    const uint32_t* sh = shadow.data() + (size_t)n.rec * kRecDwords;
+    const uint32_t mask = sh[rec::CAP_REFMASK], cap = sh[rec::CAP_MASK] + 1u;       // the reference's positions; frames of the device ring
+    const uint32_t chans = n.mc ? sh[rec::CAP_CHANS] : 1u;
     const uint32_t w = rc_[rec::CAP_WRITE], r = rc_[rec::CAP_READ], ready = rc_[rec::CAP_READY];
-    const uint32_t avail = evf::capture_avail(w, r, mask);
-    if (avail > 0 && n.ring.ptr && chans > 0) {
+    // `count` frames of every channel from ring index `from` to the end of the relay buffer(s)
+    auto drain = [&](uint32_t from, uint32_t count) {
         if (n.mc) { if (n.relayCh.size() != chans) n.relayCh.resize(chans); }      // (pendingEventData.resize(numChansToRead))
         for (uint32_t k = 0; k < chans; ++k) {
             std::vector<float>& dst = n.mc ? n.relayCh[k] : n.relay;
             const size_t at = dst.size();
-            dst.resize(at + avail);
-            if (!c.fetchRing((const float*)n.ring.ptr + (size_t)k * cap, cap, r, avail, 1, dst.data() + at)) return kHipError;
+            dst.resize(at + count);
+            if (!c.fetchRingAsync((const float*)n.ring.ptr + (size_t)k * cap, cap, from, count, 1, dst.data() + at)) return false;
         }
+        return hipStreamSynchronize(c.stream) == hipSuccess;
+    };
+    // the event of a take after host block `block`: the relay buffer(s) but for their newest `keep` frames, which belong to a later take
+    auto emit = [&](uint64_t block, size_t keep) {
+        std::string j = "{\"source\": " + srcOf(n) + ", \"data\": [";
+        auto cut = [&](std::vector<float>& v) { const size_t m = v.size() - std::min(keep, v.size()); numList(j, v.data(), m); v.erase(v.begin(), v.begin() + (std::ptrdiff_t)m); };
+        if (n.mc) for (size_t k = 0; k < n.relayCh.size(); ++k) { j += k ? ", [" : "["; cut(n.relayCh[k]); j += "]"; }
+        else cut(n.relay);
+        j += "]}";
+        c.evs.push_back({block, order, n.mc ? "mc.capture" : "capture", std::move(j)});
+    };
+    if (c.blockwise && n.captureHistoryBlocks && n.ring.ptr && chans > 0) {
+        const uint32_t lcap = sh[rec::CAP_LOGMASK] + 1u, blk = rc_[rec::CAP_BLK], take = std::min(blk - n.logRelayed, lcap);
+        std::vector<uint32_t> e((size_t)take * 4);
+        if (take && !c.fetchRing((const float*)n.ring.ptr + (size_t)chans * cap, lcap, blk - take, take, 4, reinterpret_cast<float*>(e.data()))) return kHipError;
+        std::vector<cpr::Entry> blocks = cpr::fold(c.win, e.data(), take);
+        if (blocks.empty()) blocks.push_back({c.lastBlock, rc_[rec::CAP_ABS], false});   // (nothing rendered since: a pending flag still goes out)
+        bool pending = ready != 0u;
+        for (const cpr::Entry& b : blocks) if (b.fell) pending = false;
+        std::vector<cpr::Take> takes;
+        const uint64_t end = cpr::replay(blocks.data(), blocks.size(), n.capRelayed, pending, takes);
+        // (a window longer than eventWindowBlocks(): the ring holds the newest frames only — 128 of it may be the scratch ahead)
+        const uint64_t from = std::max(n.capRelayed, end - std::min<uint64_t>(end, cap - 128u));
+        if (end > from && !drain((uint32_t)from, (uint32_t)(end - from))) return kHipError;
+        for (const cpr::Take& t : takes) emit(t.block, (size_t)(end - std::max(t.end, from)));
+        n.capRelayed = end; n.logRelayed = blk;
+        if (r != w) c.writeBack.push_back({&n, rec::CAP_READ, w});
+        if (ready) c.writeBack.push_back({&n, rec::CAP_READY, 0u});
+        return kOk;
+    }
+    const uint32_t avail = evf::capture_avail(w, r, mask);
+    if (avail > 0 && n.ring.ptr && chans > 0) {
+        // (without history CAP_ABS - avail IS the read position, mod the ring)
+        if (!drain(n.captureHistoryBlocks ? rc_[rec::CAP_ABS] - avail : r, avail)) return kHipError;
         c.writeBack.push_back({&n, rec::CAP_READ, (r + avail) & mask});
     }
+    n.capRelayed = cpr::unwrap(n.capRelayed, rc_[rec::CAP_ABS]); n.logRelayed = rc_[rec::CAP_BLK];
     if (!ready) return kOk;
     c.writeBack.push_back({&n, rec::CAP_READY, 0u});
-    std::string j = "{\"source\": " + srcOf(n) + ", \"data\": [";
-    if (n.mc) {
-        for (size_t k = 0; k < n.relayCh.size(); ++k) {
-            j += k ? ", [" : "[";
-            numList(j, n.relayCh[k].data(), n.relayCh[k].size());
-            j += "]";
-            n.relayCh[k].clear();
-        }
-    } else {
-        numList(j, n.relay.data(), n.relay.size());
-        n.relay.clear();
-    }
-    j += "]}";
-    c.evs.push_back({c.lastBlock, order, n.mc ? "mc.capture" : "capture", std::move(j)});
+    emit(c.lastBlock, 0);
     return kOk;
 }
 
@@ -346,7 +374,7 @@ int Engine::processQueuedEvents(void (*cb)(const char*, const char*, void*), voi
 // How many blocks may pass between two blockwise relays for their result to be exactly the per-block relay's: the per-block
 // readout logs hold 1024 blocks; a scope or fft ring of 8192 frames (`size` of them per event) must not overrun inside a window — one
 // made with history (option "event_history_blocks" = W) serves W blocks; a capture node's take is placed by the relay that sees its
-// gate fall, so it wants a relay per block.
+// gate fall, so it wants a relay per block — unless it was made with a history and a per-block log of its own ("capture_history_blocks").
 uint32_t Engine::eventWindowBlocks() {
     std::lock_guard<std::mutex> control(ctl);
     RenderGuard lock(*this);
@@ -359,7 +387,9 @@ uint32_t Engine::eventWindowBlocks() {
         auto nit = nodes.find(en.first);
         if (nit == nodes.end()) continue;
         const Node& n = nit->second;
-        if (n.op == OP_CAPTURE) return 1u;
+        // a capture ring with history (option "capture_history_blocks") keeps that many blocks of takes and the per-block log the relay
+        // places them by (capture_replay.h); without it the take is placed by the relay that sees the gate fall: a relay per block
+        if (n.op == OP_CAPTURE) { if (!n.captureHistoryBlocks) return 1u; w = std::min(w, n.captureHistoryBlocks); continue; }
         // a ring with history (option "event_history_blocks") holds every frame a per-block relay hands on over that many blocks, and
         // the relay replays the reads: whatever `size`, overruns included
         if ((n.op == OP_SCOPE || n.op == OP_FFT) && n.historyBlocks) { w = std::min(w, n.historyBlocks); continue; }

@@ -1019,6 +1019,14 @@ __device__ __forceinline__ void run_scope(const Ctx& c, const Member& m, uint32_
 // ring write at one channel (no input: zeros out, nothing written). The transform happens at the relay (fft_frames.hip).
 __device__ __forceinline__ void run_fft(const Ctx& c, const Member& m, uint32_t s0, uint32_t s1) { run_scope<1u>(c, m, s0, s1); }
 
+// The block's entry of a capture ring's per-block log (device.h CAP_LOGMASK; `behind` = floats of the ring's channels, the log sits
+// after them): entered by ONE lane at the end of every block the node renders.
+__device__ __forceinline__ void capture_log(rup r, gfp ring, size_t behind, uint32_t abs0, uint32_t fell) {
+    const uint32_t blk = r[rec::CAP_BLK], lm = r[rec::CAP_LOGMASK];
+    if (lm && ring) { gup e = (gup)(ring + behind) + (size_t)(blk & lm) * 4u; e[0] = blk; e[1] = abs0; e[2] = fell; e[3] = 0u; }
+    r[rec::CAP_BLK] = blk + 1u;
+}
+
 // CaptureNode (Capture.h:21-58): pass-through of input 1; while the gate (input 0) is non-zero its samples are recorded. The
 // reference collects them in a 128-frame scratch it appends to its ring when full or when the gate falls (MultiChannelRingBuffer
 // ::write, an overrun nudging the read position); here the scratch IS the ring ahead of the write position — the k-th recorded
@@ -1039,9 +1047,12 @@ __device__ __forceinline__ void run_mccapture(const Ctx& c, const Member& m, uin
     else zero_fill(c, m, s0, s1);
     if (ch != 0u || s1 <= s0) return;
     gfp ring = rec_ptr(r, rec::CAP_RING);
-    const uint32_t mask = UNI(r[rec::CAP_MASK]), cap = mask + 1u, chans = min(UNI(r[rec::CAP_CHANS]), nin - 1u);
+    // the reference's ring positions (mod cap = bitceil(sr)); the device ring holds CAP_MASK + 1 frames per channel — the same, or a
+    // whole relay window's takes (device.h CAP_ABS) — and is addressed by the count of frames handed over so far
+    const uint32_t hmask = UNI(r[rec::CAP_MASK]), mask = UNI(r[rec::CAP_REFMASK]), cap = mask + 1u, ringChans = UNI(r[rec::CAP_CHANS]), chans = min(ringChans, nin - 1u);
+    const size_t hcap = (size_t)hmask + 1u;
     const uint32_t oG = opnd_uniform(c, m, 0);
-    uint32_t w = UNI(r[rec::CAP_WRITE]), rd = UNI(r[rec::CAP_READ]), ready = UNI(r[rec::CAP_READY]);
+    uint32_t w = UNI(r[rec::CAP_WRITE]), rd = UNI(r[rec::CAP_READ]), ready = UNI(r[rec::CAP_READY]), abs0 = UNI(r[rec::CAP_ABS]), fell = 0u;
     float last = u2f(UNI(r[rec::CAP_CHANGE]));
     uint32_t wStart = 0u, wStop = 0u;
     auto flush = [&](uint32_t a, uint32_t b) {                            // MultiChannelRingBuffer::write(inputData + 1, numIns - 1, b - a, a)
@@ -1052,9 +1063,9 @@ __device__ __forceinline__ void run_mccapture(const Ctx& c, const Member& m, uin
         if (ring)
             for (uint32_t k = 0; k < chans; ++k) {
                 const uint32_t oK = opnd_uniform(c, m, k + 1u);
-                for (uint32_t j = c.lane; j < ns; j += 64u) ring[(size_t)k * cap + ((w + j) & mask)] = fetch(c, oK, a + j);
+                for (uint32_t j = c.lane; j < ns; j += 64u) ring[(size_t)k * hcap + ((abs0 + j) & hmask)] = fetch(c, oK, a + j);
             }
-        w = nw;
+        w = nw; abs0 += ns;
     };
     for (uint32_t base = s0; base < s1; base += 64u) {
         const uint32_t i = base + c.lane;
@@ -1074,7 +1085,7 @@ __device__ __forceinline__ void run_mccapture(const Ctx& c, const Member& m, uin
             if (gs) wStop = base + 64u - (uint32_t)__builtin_clzll(gs);
             if (!fe) break;
             flush(wStart, wStop);                                                            // the gate fell at frame `end`: hand over, then that frame's own gate counts again
-            ready = 1u; wStart = 0u; wStop = 0u;
+            ready = 1u; fell = 1u; wStart = 0u; wStop = 0u;
             fm &= ~(1ull << end);
             pos = end;
         }
@@ -1082,8 +1093,9 @@ __device__ __forceinline__ void run_mccapture(const Ctx& c, const Member& m, uin
     if (wStop > wStart) flush(wStart, wStop);
     WAVE_SYNC();
     if (c.lane == 0) {
-        r[rec::CAP_WRITE] = w; r[rec::CAP_READ] = rd; r[rec::CAP_READY] = ready;
+        r[rec::CAP_WRITE] = w; r[rec::CAP_READ] = rd; r[rec::CAP_READY] = ready; r[rec::CAP_ABS] = abs0;
         r[rec::CAP_CHANGE] = f2u(fetch(c, oG, s1 - 1u));
+        capture_log(r, ring, (size_t)ringChans * hcap, abs0, fell);
     }
 }
 
@@ -1092,11 +1104,12 @@ __device__ __forceinline__ void run_capture(const Ctx& c, const Member& m, uint3
     if (member_nin(c, m) < 2) return zero_fill(c, m, s0, s1);
     rup r = c.recs + m.rec * kRecDwords;
     gfp ring = rec_ptr(r, rec::CAP_RING);
-    const uint32_t mask = r[rec::CAP_MASK], cap = mask + 1u;
+    // (positions mod cap = bitceil(sr) as the reference keeps them; the device ring of CAP_MASK + 1 frames is addressed by CAP_ABS)
+    const uint32_t hmask = r[rec::CAP_MASK], mask = r[rec::CAP_REFMASK], cap = mask + 1u;
     const uint32_t oG = opnd_uniform(c, m, 0), oX = opnd_uniform(c, m, 1);
-    uint32_t w = r[rec::CAP_WRITE], rd = r[rec::CAP_READ], s = r[rec::CAP_SCRATCH], ready = r[rec::CAP_READY];
+    uint32_t w = r[rec::CAP_WRITE], rd = r[rec::CAP_READ], s = r[rec::CAP_SCRATCH], ready = r[rec::CAP_READY], abs0 = r[rec::CAP_ABS], fell = 0u;
     const float z = u2f(r[rec::CAP_CHANGE]);
-    uint32_t head = w + s;                                            // where the next recorded sample goes
+    uint32_t head = abs0 + s;                                         // where the next recorded sample goes
     for (uint32_t base = s0; base < s1; base += 64u) {
         const uint32_t i = base + c.lane;
         const bool on = i < s1;
@@ -1105,9 +1118,10 @@ __device__ __forceinline__ void run_capture(const Ctx& c, const Member& m, uint3
         if (on) put(c, m, i, x);
         const bool rec_ = on && g != 0.0f;                            // static_cast<bool>(gate)
         const uint64_t gm = __ballot(rec_), fm = __ballot(on && (g - prev) < 0.0f);   // Change.h: sign of the difference < -0.5
-        if (rec_ && ring) ring[(head + (uint32_t)__popcll(gm & ((1ull << c.lane) - 1ull))) & mask] = x;
+        if (rec_ && ring) ring[(head + (uint32_t)__popcll(gm & ((1ull << c.lane) - 1ull))) & hmask] = x;
         const uint32_t cnt = (uint32_t)__popcll(gm);
         head += cnt;
+        if (fm != 0ull) fell = 1u;
         if (fm == 0ull && s + cnt < 128u) { s += cnt; continue; }   // no flush inside these 64 frames
         const uint32_t nf = min(64u, s1 - base);
         for (uint32_t j = 0; j < nf; ++j) {
@@ -1116,15 +1130,16 @@ __device__ __forceinline__ void run_capture(const Ctx& c, const Member& m, uint3
                 const uint32_t freeSlots = rd > w ? rd - w : cap - (w - rd);
                 const uint32_t nw = (w + s) & mask;
                 if (s >= freeSlots) rd = (nw + 1u) & mask;
-                w = nw; s = 0u;
+                w = nw; abs0 += s; s = 0u;
                 if (falling) ready = 1u;
             }
             if ((gm >> j) & 1ull) ++s;
         }
     }
     if (c.lane == 0 && s1 > s0) {
-        r[rec::CAP_WRITE] = w; r[rec::CAP_READ] = rd; r[rec::CAP_SCRATCH] = s; r[rec::CAP_READY] = ready;
+        r[rec::CAP_WRITE] = w; r[rec::CAP_READ] = rd; r[rec::CAP_SCRATCH] = s; r[rec::CAP_READY] = ready; r[rec::CAP_ABS] = abs0;
         r[rec::CAP_CHANGE] = f2u(fetch(c, oG, s1 - 1u));
+        capture_log(r, ring, (size_t)hmask + 1u, abs0, fell);
     }
 }
 

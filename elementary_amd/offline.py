@@ -21,10 +21,12 @@ class OfflineRenderer:
 
     def initialize(self, num_input_channels: int = 0, num_output_channels: int = 2, sample_rate: float = 44100,
                    block_size: int = 512, virtual_file_system: Optional[Dict[str, np.ndarray]] = None,
-                   event_history_blocks: int = 0) -> None:
+                   event_history_blocks: int = 0, capture_history_blocks: int = 0) -> None:
         """``event_history_blocks`` (no counterpart in the reference; 0 = off): engine option of the same name — `scope` and `fft`
         nodes keep a device ring long enough for a relay window of that many blocks, so ``process`` still renders launch sets of
-        that size with such a listener attached (engines without ``set_option`` relay after every block anyway)."""
+        that size with such a listener attached (engines without ``set_option`` relay after every block anyway).
+        ``capture_history_blocks`` (likewise): the same for `capture` and `mc.capture` nodes — a device ring that keeps that many
+        blocks of takes and a per-block log from which the blockwise relay places every take at the block where the gate fell."""
         self.num_in = int(num_input_channels)
         self.num_out = int(num_output_channels)
         self.block_size = int(block_size)
@@ -32,6 +34,8 @@ class OfflineRenderer:
         self._rt = self._factory(self.sample_rate, self.block_size)
         if event_history_blocks and hasattr(self._rt, "set_option"):
             self._rt.set_option("event_history_blocks", int(event_history_blocks))
+        if capture_history_blocks and hasattr(self._rt, "set_option"):
+            self._rt.set_option("capture_history_blocks", int(capture_history_blocks))
         self._time = 0
         for k, v in (virtual_file_system or {}).items():
             self._rt.add_shared_resource(k, v)
@@ -67,7 +71,7 @@ class OfflineRenderer:
         if host_batch is not None and window is not None and any(self._listeners.values()) and total > bs:
             # listeners to serve: the reference relays events after EVERY block (index.ts:112-122). The engine keeps per-block readout
             # logs, so the block loop still runs as launch sets — `event_window_blocks()` blocks per engine call (1024 with meters and
-            # snapshots only, fewer with a scope ring, one with a capture node) — and the BLOCKWISE relay after each call hands the
+            # snapshots only, fewer with a scope ring, one with a capture node made without history) — and the BLOCKWISE relay after each call hands the
             # listeners every block's events in block order, as the per-block loop would have
             w = max(1, int(window())) * bs
             for k in range(0, total, w):

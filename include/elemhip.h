@@ -178,7 +178,12 @@ uint32_t elemhip_event_window_blocks(elemhip_t*);
  * AFTERWARDS keep a device ring of bitceil(W * blockSize + 8192) frames per channel instead of 8192 (4 MB per channel at W = 1024 and
  * 512 frames), and the blockwise relay replays the reference ring's per-block reads and overrun nudges on the host: for such nodes
  * elemhip_event_window_blocks() is min(W, 1024 / slices per block) whatever their `size` — overruns included, the events are the
- * per-block relay's. Nodes that already exist keep their 8192-frame ring and the rule above; `capture` stays at 1. */
+ * per-block relay's. Nodes that already exist keep their 8192-frame ring and the rule above; `capture` stays at 1.
+ * elemhip_set_option(h, "capture_history_blocks", W), same range and default: `capture` and `mc.capture` nodes created AFTERWARDS keep
+ * a device ring of bitceil(W * blockSize + bitceil(sampleRate)) frames per capture channel (4 MB at W = 1024, 512 frames and 48 kHz)
+ * and a per-block log of the frames handed to the ring and of falling gate edges; the blockwise relay replays from it what a relay
+ * after every block would have drained and emitted, and elemhip_event_window_blocks() is min(W, 1024 / slices per block) for them.
+ * Nodes that already exist keep their ring of bitceil(sampleRate) frames and a window of 1. */
 
 int  elemhip_trace_level(elemhip_t*, size_t nOut, uint32_t level, unsigned long long* out, size_t cap);
 /* Debug/test hook: JSON description of the current render plan (islands, launch levels, LDS).
@@ -202,7 +207,7 @@ int  elemhip_sum_buses(int deviceOrdinal, void* hipStream, float* dst, const flo
  * waits for them), "spec_blocks" / "host_out_direct" (elemhip_process through the specialised kernels / output written straight
  * into pinned host memory), "use_graph" / "graph_blocks" (per-block launch path replayed from a hipGraph), "stateless_rows",
  * "mixer_split", "pipeline_copies", "merge_phases", "pack_islands" / "pack_max" / "cu_count" (lane-packing of isomorphic
- * islands), "event_history_blocks" (above, at elemhip_event_window_blocks), "profile_launches", "time_batch". Unknown keys return code 6. */
+ * islands), "event_history_blocks" / "capture_history_blocks" (above, at elemhip_event_window_blocks), "profile_launches", "time_batch". Unknown keys return code 6. */
 int  elemhip_set_option(elemhip_t*, const char* key, double value);
 
 #ifdef __cplusplus
