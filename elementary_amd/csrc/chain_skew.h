@@ -1,0 +1,77 @@
+// chain_skew.h — the lane schedule of the quad-skewed recurrence loop of the specialised kernels (island_ops.inc, chain_loop_d).
+//
+// A recurrence task of up to 16 members gives every member FOUR lanes. All four run the member's whole chain with the same
+// instructions on the same operand values, but lane 4m+k (skew k) runs it 4k frames late: at loop step s it computes frame
+// s - 4k. After the 16 steps of group g the LAST four results of a lane are therefore frames 16g + 12 - 4k .. 16g + 15 - 4k:
+// the four lanes of a quad hold the group's 16 frames between them, and ONE 16-byte store per lane writes the group where
+// the unskewed loop issues four (a store costs the lone recurrence wave per INSTRUCTION, not per byte or per lane).
+//
+//   step of the block    0 ........ n-1 | n .. n+11
+//   skew 0               frames 0 .. n-1 | holds
+//   skew k               holds for 4k steps (head), then frames 0 .. n-1, the last 4k of them in the tail
+//
+// Head: in group 0 a lane of skew k sits out the first 4k steps (its state is the block's initial state). Tail: after the
+// last group it runs 4k more steps, so that every lane of a quad ends the block with the member's final state. The operands
+// of step s are loaded per lane, 16 bytes at a time, 16k bytes in front of the unskewed address; in the head and the tail
+// that address is clamped into the operand's block buffer (what a clamped load returns is never used: its steps are the ones
+// the predicates switch off).
+//
+// Written as plain index arithmetic for host and device alike: tests/native/chain_skew_host.cpp emulates the loop with these
+// functions and checks frames, final states and load offsets without a GPU.
+#ifndef ELEMHIP_CHAIN_SKEW_H
+#define ELEMHIP_CHAIN_SKEW_H
+#ifndef __HIPCC_RTC__        // (the run-time compiler has no host headers: jit.cpp declares the fixed-width names)
+#include <stdint.h>
+#endif
+
+#if defined(__HIPCC__) || defined(__HIP__) || defined(__HIPCC_RTC__)
+#define CSKEW_FD __host__ __device__ constexpr __forceinline__
+#else
+#define CSKEW_FD constexpr inline
+#endif
+
+namespace chain_skew {
+
+constexpr uint32_t kGroup = 16;        // frames per group (chain_loop_d CHG)
+constexpr uint32_t kQuad = 4;          // lanes per member = frames per 16-byte piece
+constexpr uint32_t kMaxCount = 16;     // members of a task that fit a 64-lane wave
+constexpr uint32_t kTailSteps = 12;    // steps after the last group (skew 3 runs all of them)
+
+// the task shapes the schedule covers
+CSKEW_FD bool applies(uint32_t count) { return count >= 1u && count <= kMaxCount; }
+
+// lane -> member of the task (lanes at or beyond 4 * count mirror the last member)
+CSKEW_FD uint32_t lane_member(uint32_t lane, uint32_t count) {
+    return lane / kQuad < count ? lane / kQuad : count - 1u;
+}
+// lane -> skew (mirror lanes run unskewed: they neither store nor own a frame)
+CSKEW_FD uint32_t lane_skew(uint32_t lane, uint32_t count) { return lane < kQuad * count ? lane % kQuad : 0u; }
+// lanes that store: bit l set = lane l writes its piece of every group
+CSKEW_FD unsigned long long store_mask(uint32_t count) { return count >= kMaxCount ? ~0ull : ((1ull << (kQuad * count)) - 1ull); }
+
+// first of the four frames that y[12..15] of a lane of skew k hold after the 16 steps of group g
+CSKEW_FD uint32_t stored_frame(uint32_t g, uint32_t k) { return kGroup * g + (kGroup - kQuad) - kQuad * k; }
+// ... and the byte offset of that piece inside its group (the rest of the address is the unskewed loop's)
+CSKEW_FD uint32_t store_bias(uint32_t k) { return 4u * ((kGroup - kQuad) - kQuad * k); }
+
+// head: does a lane of skew k execute step j (0 .. 15) of group 0?
+CSKEW_FD bool head_active(uint32_t k, uint32_t j) { return j >= kQuad * k; }
+// tail: does it execute step j (0 .. 11) after the last group?
+CSKEW_FD bool tail_active(uint32_t k, uint32_t j) { return j < kQuad * k; }
+
+// Byte offset, inside the operand's block buffer of n frames, of the 16-byte piece q (0 .. 3) of group g that a lane of skew k
+// loads: frames 16g + 4q - 4k .. +3. Group n / 16 is the tail's. Clamped into [0, 4n - 16]; only head (g = 0) and tail pieces
+// ever hit a bound, and exactly those whose steps head_active / tail_active switch off.
+CSKEW_FD uint32_t load_offset(uint32_t g, uint32_t q, uint32_t k, uint32_t n) {
+    return 4u * (kGroup * g + kQuad * q) < 16u * k ? 0u
+         : (4u * (kGroup * g + kQuad * q) - 16u * k > 4u * n - 16u ? 4u * n - 16u : 4u * (kGroup * g + kQuad * q) - 16u * k);
+}
+// Steady groups (1 .. n / 16 - 1) need no clamp: the lane's offset is the unskewed one plus this bias, taken from a VGPR offset
+// that carries store_bias(0) = 48 bytes extra — so that it never goes below the buffer's own offset, whatever that is — with the
+// 48 bytes taken off the instruction's immediate again.
+CSKEW_FD uint32_t load_bias(uint32_t k) { return store_bias(0u) - 16u * k; }
+constexpr int kLoadImmBias = -48;
+
+} // namespace chain_skew
+
+#endif // ELEMHIP_CHAIN_SKEW_H

@@ -1158,8 +1158,10 @@ constexpr int CH = 8;
 // per 128 frames).
 struct SIn { uint32_t base; float cval; gfp arena; uint32_t goff; bool isG; uint32_t boff; bool isS; };   // isG: the operand streams from the HBM arena (specialised kernels only);
                                                                // boff / isS: the buffer's byte offset inside its slice, slice of the stream ring (else of the block's arena)
-struct SOut { uint32_t lds; gfp arena; uint32_t goff; bool isG; uint32_t cnt; Deferred* defer; uint32_t boff; bool isS; };   // isG: the recurrence writes its block straight to the arena;
+struct SOut { uint32_t lds; gfp arena; uint32_t goff; bool isG; uint32_t cnt; Deferred* defer; uint32_t boff; bool isS; bool quad; };   // isG: the recurrence writes its block straight to the arena;
                                                                // cnt: members of the task (specialised kernels; 64 = every lane stores); defer: Ctx::defer
+                                                               // quad: member m of the task sits in lanes 4m .. 4m+3 (chain_skew.h), not in lane m
+constexpr uint32_t kCntQuad = 0x80000000u;                     // Member::cnt of a task laid out in quads (set by spec_stateful, read by sout_of)
 // (isG is a separate flag, not a null test: the compiler cannot prove arena base + offset non-null, the flag folds)
 
 __device__ __forceinline__ SIn sin_const(float v) { SIn s; s.base = 0u; s.cval = v; s.arena = (gfp)nullptr; s.goff = 0u; s.isG = false; s.boff = 0u; s.isS = false; return s; }
@@ -1182,14 +1184,14 @@ __device__ __forceinline__ SIn sin_of(const Ctx& c, uint32_t o) {
 }
 __device__ __forceinline__ SOut sout_of(const Ctx& c, const Member& m) {
     SOut o;
-    o.lds = m.outLds; o.arena = c.hbm0; o.goff = 0u; o.isG = false; o.cnt = 64u; o.defer = c.defer; o.boff = 0u; o.isS = false;
+    o.lds = m.outLds; o.arena = c.hbm0; o.goff = 0u; o.isG = false; o.cnt = 64u; o.defer = c.defer; o.boff = 0u; o.isS = false; o.quad = false;
 #ifdef ELEMHIP_SPEC
     if (m.gdirect) { o.isG = true; o.goff = hbm_off(c, m.outHbm); o.boff = (m.outHbm & ~(uint32_t)kOpStream) * c.stride * 4u; o.isS = (m.outHbm & kOpStream) != 0u; }
-    o.cnt = m.cnt;
+    o.cnt = m.cnt & ~kCntQuad; o.quad = (m.cnt & kCntQuad) != 0u;
 #endif
     return o;
 }
-__device__ __forceinline__ SOut sout_lds(uint32_t w) { SOut o; o.lds = w; o.arena = (gfp)nullptr; o.goff = 0u; o.isG = false; o.cnt = 64u; o.defer = nullptr; o.boff = 0u; o.isS = false; return o; }
+__device__ __forceinline__ SOut sout_lds(uint32_t w) { SOut o; o.lds = w; o.arena = (gfp)nullptr; o.goff = 0u; o.isG = false; o.cnt = 64u; o.defer = nullptr; o.boff = 0u; o.isS = false; o.quad = false; return o; }
 __device__ __forceinline__ void sout_put(const SOut& o, uint32_t t, float y) {   // per-frame store (tails, rare shapes)
     if (o.isG) ((gfp)((char __attribute__((address_space(1)))*)o.arena + o.goff))[t] = y; else lds[o.lds + t] = y;
 }
@@ -1239,6 +1241,168 @@ __device__ __forceinline__ void chain_store_group(const v4f_& a0, const v4f_& a1
                    "i"(OFF), "i"(OFF + 16), "i"(OFF + 32), "i"(OFF + 48)
                  : "memory");
 }
+// ---- the quad-skewed form of the loop (chain_skew.h): one 16-byte store per lane and group ---------------------------------
+// chain_store_piece / chain_store_piece_lds: the ONE store of a group — every lane of a quad its own four frames — with EXEC cut to
+// the task's 4 * count member lanes exactly as chain_store_group does it. voff already carries the lane's place inside the group.
+template <int OFF>
+__device__ __forceinline__ void chain_store_piece(const v4f_& a, uint32_t voff, __amdgpu_buffer_rsrc_t rsrc, uint32_t soff, unsigned long long mask) {
+    static_assert(OFF >= 0 && OFF < 4096, "12-bit immediate");
+    unsigned long long saved;
+    asm volatile("s_mov_b64 %0, exec\n\t"
+                 "s_mov_b64 exec, %5\n\t"
+                 "buffer_store_dwordx4 %1, %2, %3, %4 offen offset:%c6\n\t"
+                 "s_mov_b64 exec, %0\n\t"
+                 "s_nop 0"
+                 : "=&s"(saved)
+                 : "v"(a), "v"(voff), "s"(rsrc), "s"(soff), "s"(mask), "i"(OFF)
+                 : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void chain_store_piece_lds(const v4f_& a, uint32_t addr, unsigned long long mask) {
+    static_assert(OFF >= 0 && OFF < 65536, "16-bit immediate");
+    unsigned long long saved;
+    asm volatile("s_mov_b64 %0, exec\n\t"
+                 "s_mov_b64 exec, %3\n\t"
+                 "ds_write_b128 %2, %1 offset:%c4\n\t"
+                 "s_mov_b64 exec, %0"
+                 : "=&s"(saved)
+                 : "v"(a), "v"(addr), "s"(mask), "i"(OFF)
+                 : "memory");
+}
+// Taken by chain_loop_d when the task is laid out in quads, every streamed operand comes from the arena and the block is the
+// kernel's own (a multiple of the span). Per lane the instruction stream of a steady group is the unskewed loop's minus three of
+// its four stores; the lane's skew lives in its VGPR offsets alone. Group 0 of a block (the head) and the up to 12 steps behind the
+// last group (the tail) are peeled: their steps are predicated per lane, their loads clamped into the operand's block buffer —
+// global loads are not range-checked by anything. The last span issues only the tail's loads (three pieces per operand) where the
+// unskewed loop re-reads a whole span that nothing uses.
+template <int NIN, uint32_t CM, int DEPTH, typename Step>
+__device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut out, Step&& step) {
+    constexpr int NS0 = NIN - __builtin_popcount(CM & ((1u << NIN) - 1u));
+    constexpr int NS = NS0 > 0 ? NS0 : 1;
+    constexpr uint32_t n = ELEMHIP_SPEC_BLOCK, span = (uint32_t)(DEPTH * CHG);
+    static_assert(n % span == 0u && n >= span, "whole spans only");
+    static_assert(CHG == (int)chain_skew::kGroup, "chain_skew.h is written for 16-frame groups");
+    const uint32_t skew = chain_skew::lane_skew(opaque_lane(), out.cnt);
+    gfp arena = out.arena;
+#pragma unroll
+    for (int k = 0; k < NIN; ++k) if (in[k].isG) arena = in[k].arena;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((float*)arena, 0, 0x7FFFFFFF, 0x00020000);
+    uint32_t ooff = (out.isG ? out.goff : (out.lds << 2)) + chain_skew::store_bias(skew);
+    uint32_t ioff[NIN];
+#pragma unroll
+    for (int k = 0; k < NIN; ++k) ioff[k] = in[k].goff + chain_skew::load_bias(skew);
+#define CHAIN_OPAQUE_OFFSETS() do { asm volatile("" : "+v"(ooff)); _Pragma("unroll") for (int k_ = 0; k_ < NIN; ++k_) asm volatile("" : "+v"(ioff[k_])); } while (0)
+    const unsigned long long smask = chain_skew::store_mask(out.cnt);
+    typedef const char __attribute__((address_space(1)))* gccp;
+    // a steady group: D-th of the span at byte offset soff of the block (never group 0, never the tail's)
+    auto load = [&](uint32_t soff, auto Dc, float (&x)[NS][CHG]) {
+        constexpr int D = decltype(Dc)::value;
+        int s_ = 0;
+#pragma unroll
+        for (int k = 0; k < NIN; ++k) {
+            if (!((CM >> k) & 1u)) {
+#pragma unroll
+                for (int q = 0; q < CHG / 4; ++q) {
+                    const v4f a = *(gcv4)((gccp)arena + ioff[k] + soff + (D * CHG * 4 + 16 * q + chain_skew::kLoadImmBias));
+                    x[s_][4 * q] = a.x; x[s_][4 * q + 1] = a.y; x[s_][4 * q + 2] = a.z; x[s_][4 * q + 3] = a.w;
+                }
+                ++s_;
+            }
+        }
+    };
+    // group G (0: the head's, n / 16: the tail's), pieces [0, NQ): every piece at its own clamped offset
+    auto load_edge = [&](uint32_t G, auto NQc, float (&x)[NS][CHG]) {
+        constexpr int NQ = decltype(NQc)::value;
+        int s_ = 0;
+#pragma unroll
+        for (int k = 0; k < NIN; ++k) {
+            if (!((CM >> k) & 1u)) {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const v4f a = *(gcv4)((gccp)arena + (in[k].goff + chain_skew::load_offset(G, (uint32_t)q, skew, n)));
+                    x[s_][4 * q] = a.x; x[s_][4 * q + 1] = a.y; x[s_][4 * q + 2] = a.z; x[s_][4 * q + 3] = a.w;
+                }
+                ++s_;
+            }
+        }
+    };
+    auto wait_group = [&](float (&x)[NS][CHG], auto Lc) {   // one wait per group, for its LAST load (vector loads return in order)
+        constexpr int L = decltype(Lc)::value;
+        if constexpr (NS0 > 0) {
+#pragma unroll
+            for (int k_ = 0; k_ < NS; ++k_) asm volatile("" : "+v"(x[k_][L - 4]), "+v"(x[k_][L - 3]), "+v"(x[k_][L - 2]), "+v"(x[k_][L - 1]));
+        }
+    };
+    auto operands = [&](const float (&x)[NS][CHG], int j, float (&xs)[NIN]) {
+        int s_ = 0;
+#pragma unroll
+        for (int k = 0; k < NIN; ++k) {
+            if ((CM >> k) & 1u) xs[k] = in[k].cval;
+            else xs[k] = x[s_++][j];
+        }
+    };
+    // HEAD: group 0 of the block — a lane of skew k holds for its first 4k steps
+    auto run = [&](float (&x)[NS][CHG], uint32_t soff, auto Dc, auto Hc) {
+        constexpr int D = decltype(Dc)::value;
+        constexpr bool HEAD = decltype(Hc)::value != 0;
+        float y[CHG];
+        wait_group(x, IntC<CHG>{});
+#pragma unroll
+        for (int j = 0; j < CHG; ++j) {
+            float xs[NIN];
+            operands(x, j, xs);
+            if constexpr (HEAD) { y[j] = 0.0f; if (chain_skew::head_active(skew, (uint32_t)j)) y[j] = step(xs); }
+            else y[j] = step(xs);
+        }
+        v4f a;
+        a.x = y[CHG - 4]; a.y = y[CHG - 3]; a.z = y[CHG - 2]; a.w = y[CHG - 1];
+        if (out.isG) chain_store_piece<D * CHG * 4>(a, ooff, rsrc, soff, smask);
+        else chain_store_piece_lds<D * CHG * 4>(a, ooff + soff, smask);
+    };
+    float X[DEPTH][NS][CHG];
+    CHAIN_OPAQUE_OFFSETS();
+    if constexpr (NS0 > 0) {
+        load_edge(0u, IntC<CHG / 4>{}, X[0]);
+        static_for<1, DEPTH>([&](auto Dc) { load(0u, Dc, X[decltype(Dc)::value]); });
+        take_deferred<DEPTH * NS0 * (CHG / 4)>(out.defer);   // the previous block is published under this block's first loads
+    } else take_deferred<0>(out.defer);
+    auto span_body = [&](uint32_t soff, auto Hc, auto Lc) {
+        constexpr bool HEAD = decltype(Hc)::value != 0, LAST = decltype(Lc)::value != 0;
+        CHAIN_OPAQUE_OFFSETS();
+        static_for<0, DEPTH>([&](auto Dc) {
+            constexpr int D = decltype(Dc)::value;
+            run(X[D], soff, Dc, IntC<(HEAD && D == 0) ? 1 : 0>{});
+            if constexpr (NS0 > 0) {
+                if constexpr (!LAST) load(soff + span * 4u, Dc, X[D]);
+                else if constexpr (D == 0) load_edge(n / (uint32_t)CHG, IntC<(int)chain_skew::kTailSteps / 4>{}, X[0]);
+            }
+        });
+    };
+    constexpr int NSPAN = (int)(n / span);
+    if constexpr (NS0 > 0) {
+        // Streamed operands: the spans are written out one after the other. As a loop around a peeled head and last span the
+        // prefetched registers were carried through phi copies at every span end, each behind a wait for ITS load — the whole
+        // next span drained there (vmcnt 24, 20 .. 2 in a row) instead of one group at a time.
+        static_for<0, NSPAN>([&](auto Sc) {
+            constexpr int S = decltype(Sc)::value;
+            span_body((uint32_t)S * span * 4u, IntC<S == 0 ? 1 : 0>{}, IntC<S == NSPAN - 1 ? 1 : 0>{});
+        });
+    } else if constexpr (n == span) span_body(0u, IntC<1>{}, IntC<1>{});
+    else {
+        span_body(0u, IntC<1>{}, IntC<0>{});
+        for (uint32_t t0 = span; t0 + span < n; t0 += span) span_body(t0 * 4u, IntC<0>{}, IntC<0>{});
+        span_body((n - span) * 4u, IntC<0>{}, IntC<1>{});
+    }
+    // TAIL: the lanes of skew k catch up their last 4k frames (nothing is stored: every frame of the block already is)
+    wait_group(X[0], IntC<(int)chain_skew::kTailSteps>{});
+#pragma unroll
+    for (int j = 0; j < (int)chain_skew::kTailSteps; ++j) {
+        float xs[NIN];
+        operands(X[0], j, xs);
+        if (chain_skew::tail_active(skew, (uint32_t)j)) (void)step(xs);
+    }
+#undef CHAIN_OPAQUE_OFFSETS
+}
 // DEPTH = groups in flight per streamed operand (16 VGPRs each).
 template <int NIN, uint32_t CM, int DEPTH, typename Step>
 __device__ __forceinline__ void chain_loop_d(const SIn (&in)[NIN], const SOut out, uint32_t n, Step&& step) {
@@ -1253,7 +1417,18 @@ __device__ __forceinline__ void chain_loop_d(const SIn (&in)[NIN], const SOut ou
     // VGPR offset — for a store the extra lanes' offset is out of range and the hardware drops it: no EXEC change, no branch,
     // straight-line code in which the compiler's wait counts for the prefetched loads stay exact — the span's position in
     // the scalar offset, the frame inside the span in the 12-bit immediate.
-    const bool io = opaque_lane() < out.cnt;
+    if constexpr (ELEMHIP_SPEC_BLOCK % (DEPTH * CHG) == 0 && NIN <= 3) {
+        if (out.quad && n == (uint32_t)ELEMHIP_SPEC_BLOCK) {
+            bool allG = true;                                // (folds: the operand kinds are compile-time facts of the task)
+#pragma unroll
+            for (int k = 0; k < NIN; ++k) if (!((CM >> k) & 1u)) allG = allG && in[k].isG;
+            if (__builtin_amdgcn_ballot_w64(!allG) == 0ull) return chain_loop_q<NIN, CM, DEPTH>(in, out, step);
+        }
+    }
+    // (a quad task that stays on this loop — an LDS operand, the wide biquad — stores from the first lane of each quad)
+    unsigned long long smask = out.quad ? (chain_skew::store_mask(out.cnt) & 0x1111111111111111ull)
+                                        : (out.cnt >= 64u ? ~0ull : ((1ull << out.cnt) - 1ull));   // the task's member lanes
+    const bool io = ((smask >> opaque_lane()) & 1ull) != 0ull;
     gfp arena = out.arena;
 #pragma unroll
     for (int k = 0; k < NIN; ++k) if (in[k].isG) arena = in[k].arena;
@@ -1268,7 +1443,6 @@ __device__ __forceinline__ void chain_loop_d(const SIn (&in)[NIN], const SOut ou
 #define CHAIN_OPAQUE_OFFSETS() do { asm volatile("" : "+v"(ooff)); _Pragma("unroll") for (int k_ = 0; k_ < NIN; ++k_) asm volatile("" : "+v"(ioff[k_])); } while (0)
     typedef unsigned int u4v __attribute__((ext_vector_type(4)));
     // soff: byte offset of the span inside the block (wave-uniform); D: group of the span (compile-time: folds into the immediate)
-    unsigned long long smask = out.cnt >= 64u ? ~0ull : ((1ull << out.cnt) - 1ull);   // the task's member lanes
     auto load = [&](uint32_t soff, auto Dc, float (&x)[NS][CHG]) {
         constexpr int D = decltype(Dc)::value;
         int s_ = 0;

@@ -104,7 +104,15 @@ __device__ __forceinline__ void spec_stateful(const Ctx& c, uint32_t off) {
             // Lane-per-node recurrence. EVERY lane runs it (lanes >= count repeat the last member: same loads, same
             // arithmetic, same stores of the same values): a lone wave issues a VALU op in 4.07 cycles with all 64 lanes
             // enabled and in 5.09 with a partial EXEC mask (tools/micro/issue2.hip), and nothing else hides the difference.
-            const Member m = T::member_lane(c, off, c.lane);
+            // A task of up to 16 plain float recurrences is laid out in quads (chain_skew.h): member m in lanes 4m .. 4m+3, so that
+            // the four lanes of a member can run its chain 0, 4, 8 and 12 frames late and share the stores of a group. (The wide
+            // biquad keeps one lane per member: its 6-operand loop sits at the register limit of its kernels.)
+            constexpr bool quad = chain_skew::applies(count) &&
+                (op == OP_PHASOR || op == OP_SPHASOR || op == OP_POLE || op == OP_ENV || op == OP_COUNTER || op == OP_ACCUM ||
+                 op == OP_LATCH || op == OP_MAXHOLD || op == OP_PHASE);
+            const uint32_t mlane = quad ? chain_skew::lane_member(c.lane, count) : c.lane;
+            Member m = T::member_lane(c, off, mlane);
+            if constexpr (quad) m.cnt |= kCntQuad;
             if constexpr (op == OP_PHASOR) ser_phasor<(int)cm>(c, m, cm);
             else if constexpr (op == OP_SPHASOR) ser_sphasor<(int)cm>(c, m, cm);
             else if constexpr (op == OP_POLE) ser_pole<(int)cm>(c, m, cm);
@@ -125,7 +133,7 @@ __device__ __forceinline__ void spec_stateful(const Ctx& c, uint32_t off) {
             //  its arithmetic too — in a task of phasors only it used to run the oscillator form, inc = f / sr instead of
             //  f * (1 / sr), and raced its own final phase into the phasor's record: wrong by 512 x an ulp of inc at every launch
             //  boundary, invisible inside a launch set where the phase stays in lane 0's register)
-            else if constexpr (op == OP_PHASE) ser_phase(c, m, (c.lane < count ? c.lane : count - 1u) >= T::s0);
+            else if constexpr (op == OP_PHASE) ser_phase(c, m, (mlane < count ? mlane : count - 1u) >= T::s0);
             else static_assert(op == OP_INVALID, "opcode without a recurrence body");
         }
         WAVE_SYNC();

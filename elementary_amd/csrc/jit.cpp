@@ -39,7 +39,7 @@
 #include <thread>
 #include <unordered_set>
 
-#include "build/spec_text.inc"   // kSpecDeviceH, kSpecOpsInc, kSpecInc: the sources as raw string literals
+#include "build/spec_text.inc"   // kSpecDeviceH, kSpecSkewH, kSpecOpsInc, kSpecInc: the sources as raw string literals
 
 namespace elemhip {
 
@@ -399,12 +399,12 @@ void Jit::setEntryCap(uint32_t cap) {
 // everything in front of the generated text (a function of the LDS size and the engine's block size)
 static std::string sourcePrefix(uint32_t ldsWords, uint32_t block, size_t reserveExtra) {
     std::string s;
-    s.reserve(sizeof(kSpecDeviceH) + sizeof(kSpecOpsInc) + sizeof(kSpecInc) + reserveExtra + 256);
+    s.reserve(sizeof(kSpecDeviceH) + sizeof(kSpecSkewH) + sizeof(kSpecOpsInc) + sizeof(kSpecInc) + reserveExtra + 256);
     s += "#define ELEMHIP_SPEC 1\n#define ELEMHIP_SPEC_LDS_WORDS " + std::to_string(ldsWords) + "\n#define ELEMHIP_SPEC_BLOCK " + std::to_string(block) + "\n";
     // hiprtc has no host headers: the fixed-width names the sources use (same underlying types as <stdint.h> on this target)
     s += "typedef unsigned char uint8_t; typedef unsigned short uint16_t; typedef unsigned int uint32_t; typedef unsigned long uint64_t;\n"
          "typedef signed char int8_t; typedef short int16_t; typedef int int32_t; typedef long int64_t; typedef unsigned long uintptr_t;\n";
-    s += kSpecDeviceH; s += "\n"; s += kSpecOpsInc; s += "\n"; s += kSpecInc; s += "\n";
+    s += kSpecDeviceH; s += "\n"; s += kSpecSkewH; s += "\n"; s += kSpecOpsInc; s += "\n"; s += kSpecInc; s += "\n";
     return s;
 }
 
