@@ -123,6 +123,14 @@ int elemhip_process_blocks_host(elemhip_t* h, const float* const* in, size_t nIn
     return h->engine.processBlocksHost(in, nIn, out, nOut, numFrames, st);
 }
 
+int elemhip_process_blocks_pcm(elemhip_t* h, const float* const* in, size_t nIn, void* const* streams, size_t nStreams, float* const* planar,
+                               size_t numFrames, int64_t st, const elemhip_pcm_spec* spec, elemhip_pcm_channel_stats* stats) {
+    if (!h || !spec) return elemhip::kInvalidInstructionFormat;
+    static_assert(sizeof(elemhip_pcm_channel_stats) == sizeof(Engine::PcmChannelStats) && sizeof(elemhip_pcm_spec) == sizeof(Engine::PcmSpec), "same layout");
+    const Engine::PcmSpec sp{spec->format, spec->channels_per_stream, spec->dither, spec->seed};
+    return h->engine.processBlocksPcm(in, nIn, streams, nStreams, planar, numFrames, st, sp, reinterpret_cast<Engine::PcmChannelStats*>(stats));
+}
+
 int elemhip_add_shared_resource(elemhip_t* h, const char* name, const float* const* ch, size_t nCh, size_t nSamples) {
     if (!h || !name) return 0;
     return h->engine.addSharedResource(name, ch, nCh, nSamples) ? 1 : 0;

@@ -183,6 +183,8 @@ Engine::~Engine() {
         if (evRendered[k]) (void)hipEventDestroy(evRendered[k]);
         if (evOut[k]) (void)hipEventDestroy(evOut[k]);
     }
+    for (int k = 0; k < 2; ++k) { if (hPcm[k]) (void)hipHostFree(hPcm[k]); if (dPcm[k]) (void)hipFree(dPcm[k]); }
+    if (dPcmRowBase) (void)hipFree(dPcmRowBase);
     if (ioStream) (void)hipStreamDestroy(ioStream);
     if (relayStream) { (void)hipStreamSynchronize(relayStream); (void)hipStreamDestroy(relayStream); }
     if (evRelay) (void)hipEventDestroy(evRelay);

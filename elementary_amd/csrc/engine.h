@@ -207,6 +207,19 @@ public:
     // blocks (a short tail of the inputs is zero-padded, the outputs receive numFrames frames). Launch sets are staged
     // through pinned double buffers: the D2H of set k and the H2D of set k + 1 run on a copy stream while set k + 1 renders.
     int processBlocksHost(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime);
+    // The same render delivered as PCM (pcm_pack.h): `nStreams` streams of `spec.channelsPerStream` interleaved channels each — stream s,
+    // sample (frame, g) = output channel s * G + g — as int16, packed 24-bit or float32, numFrames * G samples per stream. Behind the
+    // last render level of every launch set a pack kernel (pcm_pack.hip) converts the set's output block where it lies in HBM; one
+    // D2H per set brings the packed streams and the per-channel statistics to a pinned half, one contiguous memcpy per stream puts
+    // them into the caller's buffers while the next set renders. `planar` (may be null): nStreams * G planar float arrays that receive
+    // the very samples that were packed — the float copy and scatter of processBlocksHost run only then. `stats` (may be null): one
+    // per channel, over the delivered frames of this call. Where processBlocksHost renders host block by host block through process()
+    // (taps under a sliced host block, ragged slices) the floats are on the host already and are packed there by the header's scalar
+    // loop: the same functions, the same bits.
+    struct PcmSpec { uint32_t format, channelsPerStream, dither, seed; };
+    struct PcmChannelStats { float peak; uint32_t reserved; uint64_t over, nonfinite; };
+    int processBlocksPcm(const float* const* in, size_t nIn, void* const* streams, size_t nStreams, float* const* planar,
+                         size_t numFrames, int64_t sampleTime, const PcmSpec& spec, PcmChannelStats* stats);
     // render `numBlocks` blocks with a HIP event pair around every kernel launch; msOut[l] = mean
     // duration of launch level l (l < numLevels), msOut[numLevels] = epilogue. Returns levels + 1.
     int timeLaunches(size_t nOut, size_t numBlocks, float* msOut, size_t cap);
@@ -346,6 +359,15 @@ private:
     size_t stageOutFloats = 0, stageInFloats = 0;
     hipEvent_t evIn[2] = {nullptr, nullptr}, evRendered[2] = {nullptr, nullptr}, evOut[2] = {nullptr, nullptr};
     int ensureHostStaging(size_t outFloats, size_t inFloats);
+    // PCM delivery (processBlocksPcm): packed halves behind the float ones (streams, then the set's per-channel statistics), and
+    // the pack kernel's row table for the group size in use
+    struct PcmJob;
+    unsigned char* hPcm[2] = {nullptr, nullptr}; unsigned char* dPcm[2] = {nullptr, nullptr};
+    size_t pcmBytes = 0;
+    uint16_t* dPcmRowBase = nullptr; uint32_t pcmTableGroup = 0, pcmRowDwords = 0;
+    int ensurePcmStaging(size_t bytes, uint32_t group);
+    // the set loop of processBlocksHost / processBlocksPcm (`pcm` null: planar floats only)
+    int renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm);
     // enqueue `numBlocks` blocks on `stream` (no synchronise at the end): the body of processBlocks
     int enqueueBlocks(const float* inDev, size_t nIn, float* outDev, size_t nOut, size_t numBlocks, int64_t sampleTime);
 

@@ -1,6 +1,7 @@
 // engine_render.cpp — the per-block launch sequence (process), launch sets (processBlocks / processBlocksHost), the resident
 // kernel's host side and the measurement calls. Everything a render call reaches lives in this unit or inline in engine.h.
 #include "engine_impl.h"
+#include <functional>
 #include <thread>
 
 namespace elemhip {
@@ -1143,6 +1144,46 @@ int Engine::ensureHostStaging(size_t outFloats, size_t inFloats) {
     return grow(hStageIn, dStageIn, stageInFloats, inFloats);
 }
 
+int Engine::ensurePcmStaging(size_t bytes, uint32_t group) {
+    if (group != pcmTableGroup) {
+        // (the device is idle between calls: every host-path call ends with both streams synchronised)
+        if (!dPcmRowBase) HIP_OK(hipMalloc((void**)&dPcmRowBase, pcm_pack::kMaxGroup * sizeof(uint16_t)));
+        std::vector<uint16_t> table(group);
+        const uint32_t dwords = pcm_pack_row_table(group, table.data());
+        HIP_OK(hipStreamSynchronize(stream));
+        HIP_OK(hipMemcpy(dPcmRowBase, table.data(), group * sizeof(uint16_t), hipMemcpyHostToDevice));
+        pcmTableGroup = group; pcmRowDwords = dwords;
+    }
+    if (bytes <= pcmBytes) return kOk;
+    HIP_OK(hipStreamSynchronize(stream));
+    if (ioStream) HIP_OK(hipStreamSynchronize(ioStream));
+    // the new buffers first: a failed allocation leaves the old pair (and pcmBytes) as they were
+    unsigned char* nh[2] = {nullptr, nullptr}; unsigned char* nd[2] = {nullptr, nullptr};
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; ++k)
+        ok = hipHostMalloc((void**)&nh[k], bytes, hipHostMallocDefault) == hipSuccess && hipMalloc((void**)&nd[k], bytes) == hipSuccess;
+    if (!ok) {
+        for (int k = 0; k < 2; ++k) { if (nh[k]) (void)hipHostFree(nh[k]); if (nd[k]) (void)hipFree(nd[k]); }
+        (void)hipGetLastError();
+        return kHipError;
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (hPcm[k]) (void)hipHostFree(hPcm[k]);
+        if (dPcm[k]) (void)hipFree(dPcm[k]);
+        hPcm[k] = nh[k]; dPcm[k] = nd[k];
+    }
+    pcmBytes = bytes;
+    return kOk;
+}
+
+// what a processBlocksPcm call carries through the set loop
+struct Engine::PcmJob {
+    PcmSpec spec;
+    void* const* streams; size_t nStreams;
+    std::vector<uint32_t> peakBits; std::vector<uint64_t> over, nonfinite;      // per channel, summed over the sets
+    uint32_t validOf[2] = {0, 0};                                                // delivered frames of the set in each half
+};
+
 // Runtime::process for a whole offline render (offline-renderer/index.ts:87-133): planar host arrays of `numFrames` frames.
 // Set k (up to `batch_blocks` blocks) is gathered into pinned half k % 2, copied in on the copy stream, rendered on the
 // engine's stream into device half k % 2, copied out on the copy stream and scattered to the caller's arrays while set
@@ -1151,7 +1192,33 @@ int Engine::processBlocksHost(const float* const* in, size_t nIn, float* const* 
     if (dry) return kNoDevice;
     if (nIn > kMaxHostIn || nOut > kMaxOutBus) return kTooManyChannels;
     if ((nIn && !in) || (nOut && !out)) return kInvalidInstructionFormat;
+    return renderHostSets(in, nIn, out, nOut, numFrames, sampleTime, nullptr);
+}
+
+int Engine::processBlocksPcm(const float* const* in, size_t nIn, void* const* streams, size_t nStreams, float* const* planar,
+                             size_t numFrames, int64_t sampleTime, const PcmSpec& spec, PcmChannelStats* stats) {
+    if (!pcm_pack::format_ok(spec.format) || spec.channelsPerStream == 0u || (nStreams && !streams) || (nIn && !in)) return kInvalidInstructionFormat;
+    if (nIn > kMaxHostIn || nStreams > kMaxOutBus || nStreams * (size_t)spec.channelsPerStream > kMaxOutBus) return kTooManyChannels;
+    if (dry) return kNoDevice;
+    const size_t nOut = nStreams * spec.channelsPerStream;
+    PcmJob job;
+    job.spec = spec; job.streams = streams; job.nStreams = nStreams;
+    job.peakBits.assign(nOut, 0u); job.over.assign(nOut, 0u); job.nonfinite.assign(nOut, 0u);
+    const int rc = nOut ? renderHostSets(in, nIn, planar, nOut, numFrames, sampleTime, &job) : kOk;
+    if (stats)
+        for (size_t c = 0; c < nOut; ++c) {
+            std::memcpy(&stats[c].peak, &job.peakBits[c], 4);
+            stats[c].reserved = 0u; stats[c].over = job.over[c]; stats[c].nonfinite = job.nonfinite[c];
+        }
+    return rc;
+}
+
+// (`out` may be null with `pcm`: nobody asked for the planar floats)
+int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm) {
     const size_t bs = (size_t)blockSize;
+    const bool wantFloat = nOut > 0 && out != nullptr;
+    const uint32_t pcmG = pcm ? pcm->spec.channelsPerStream : 1u, pcmFmt = pcm ? pcm->spec.format : 0u;
+    const size_t pcmB = pcm ? pcm_pack::sample_bytes(pcmFmt) : 0;
     // whole HOST blocks, like the reference's block loop (a host block = hostBlockSize / blockSize engine blocks)
     const size_t hb = (size_t)hostBlockSize;
     bool tapSlices = hb % bs != 0;          // ragged slices (a host block that no k divides evenly): launch sets hold whole engine blocks
@@ -1162,20 +1229,30 @@ int Engine::processBlocksHost(const float* const* in, size_t nIn, float* const* 
         std::vector<const float*> ip(nIn);
         std::vector<float*> op(nOut);
         std::vector<float> tailIn, tailOut;
+        std::vector<uint8_t*> sp(pcm ? pcm->nStreams : 0);
         for (size_t f0 = 0; f0 < numFrames; f0 += hb) {
             const size_t nf = std::min(hb, numFrames - f0);
             for (size_t c = 0; c < nIn; ++c) ip[c] = in[c] + f0;
-            for (size_t c = 0; c < nOut; ++c) op[c] = out[c] + f0;
-            if (nf < hb) {
+            for (size_t c = 0; c < nOut; ++c) op[c] = wantFloat ? out[c] + f0 : nullptr;
+            if (nf < hb || pcm) {
                 // the last, partly filled host block is still a whole block to the engine (offline-renderer/index.ts:104-131: inputs
-                // padded with zeros, the frames beyond the caller's arrays dropped)
-                tailIn.assign(nIn * hb, 0.0f); tailOut.assign(nOut * hb, 0.0f);
-                for (size_t c = 0; c < nIn; ++c) { std::memcpy(tailIn.data() + c * hb, in[c] + f0, nf * sizeof(float)); ip[c] = tailIn.data() + c * hb; }
+                // padded with zeros, the frames beyond the caller's arrays dropped); a PCM call renders every host block here
+                tailOut.assign(nOut * hb, 0.0f);
                 for (size_t c = 0; c < nOut; ++c) op[c] = tailOut.data() + c * hb;
+            }
+            if (nf < hb) {
+                tailIn.assign(nIn * hb, 0.0f);
+                for (size_t c = 0; c < nIn; ++c) { std::memcpy(tailIn.data() + c * hb, in[c] + f0, nf * sizeof(float)); ip[c] = tailIn.data() + c * hb; }
             }
             const int rc = process(ip.data(), nIn, op.data(), nOut, hb, sampleTime + (int64_t)f0);
             if (rc != kOk) return rc;
-            if (nf < hb) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + f0, tailOut.data() + c * hb, nf * sizeof(float));
+            if ((nf < hb || pcm) && wantFloat) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + f0, tailOut.data() + c * hb, nf * sizeof(float));
+            if (pcm) {
+                // the floats are on the host: the header's scalar loop packs them — the kernel's functions, the kernel's bits
+                for (size_t s = 0; s < pcm->nStreams; ++s) sp[s] = static_cast<uint8_t*>(pcm->streams[s]) + f0 * pcmG * pcmB;
+                pcm_pack::pack_host(pcmFmt, pcmG, (uint32_t)pcm->nStreams, pcm->spec.dither != 0u, pcm->spec.seed, tailOut.data(), hb, nf,
+                                    sampleTime + (int64_t)f0, sp.data(), pcm->peakBits.data(), pcm->over.data(), pcm->nonfinite.data());
+            }
         }
         return kOk;
     }
@@ -1193,30 +1270,51 @@ int Engine::processBlocksHost(const float* const* in, size_t nIn, float* const* 
         if (hb > bs) setBlocks = std::min(numBlocks, std::max(hb / bs, setBlocks / (hb / bs) * (hb / bs)));
         int rc = ensureHostStaging(setBlocks * std::max<size_t>(nOut, 1) * bs, setBlocks * std::max<size_t>(nIn, 1) * bs);
         if (rc != kOk) return rc;
+        if (pcm) {
+            rc = ensurePcmStaging(pcm->nStreams * (size_t)pcm_pack::stream_stride(setBlocks * bs, pcmG, pcmFmt) + nOut * sizeof(pcm_pack::ChannelStats), pcmG);
+            if (rc != kOk) return rc;
+        }
     }
     const size_t numSets = (numBlocks + setBlocks - 1) / setBlocks;
-    auto scatter = [&](size_t k) {     // pinned half -> the caller's planar arrays
+    // One thread copies ~10 GB/s; a set of many channels (C4: 128 outputs x 1024 blocks = 268 MB per 12.6 ms of rendering)
+    // needs more than that to stay hidden behind the next set, so big sets are cut over a few threads.
+    auto spread = [&](size_t bytes, size_t maxParts, const std::function<void(size_t, size_t)>& part) {      // part(t, threads)
+        size_t threads = bytes >= (16u << 20) ? std::min<size_t>(8, std::max<size_t>(1, std::thread::hardware_concurrency() / 4)) : 1;
+        threads = std::min(threads, maxParts);
+        if (threads <= 1) return part(0, 1);
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < threads; ++t) pool.emplace_back(part, t, threads);
+        part(0, threads);
+        for (auto& th : pool) th.join();
+    };
+    auto scatter = [&](size_t k) {     // pinned half -> the caller's planar arrays (by block range)
         const size_t b0 = k * setBlocks, nb = std::min(setBlocks, numBlocks - b0);
         const float* src = hStageOut[k & 1];
-        auto part = [&](size_t bBegin, size_t bEnd) {
-            for (size_t b = bBegin; b < bEnd; ++b) {
+        spread(nb * nOut * bs * sizeof(float), nb, [&](size_t t, size_t threads) {
+            for (size_t b = nb * t / threads; b < nb * (t + 1) / threads; ++b) {
                 const size_t f0 = (b0 + b) * bs;
                 if (f0 >= numFrames) break;                     // (the engine blocks that only fill up the last host block)
                 const size_t n = std::min(bs, numFrames - f0);
                 for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + f0, src + (b * nOut + c) * bs, n * sizeof(float));
             }
-        };
-        // One thread copies ~10 GB/s; a set of many channels (C4: 128 outputs x 1024 blocks = 268 MB per 12.6 ms of rendering)
-        // needs more than that to stay hidden behind the next set, so big sets are cut over a few threads by block range.
-        const size_t bytes = nb * nOut * bs * sizeof(float);
-        size_t threads = bytes >= (16u << 20) ? std::min<size_t>(8, std::max<size_t>(1, std::thread::hardware_concurrency() / 4)) : 1;
-        threads = std::min(threads, nb);
-        if (threads <= 1) return part(0, nb);
-        std::vector<std::thread> pool;
-        for (size_t t = 1; t < threads; ++t) pool.emplace_back(part, nb * t / threads, nb * (t + 1) / threads);
-        part(0, nb / threads);
-        for (auto& th : pool) th.join();
+        });
     };
+    auto deliverPcm = [&](size_t k) {  // pinned packed half -> the caller's streams (one contiguous stretch per stream), statistics summed
+        const size_t valid = pcm->validOf[k & 1], f0 = k * setBlocks * bs;
+        const size_t stride = (size_t)pcm_pack::stream_stride(valid, pcmG, pcmFmt), len = valid * pcmG * pcmB;
+        const unsigned char* src = hPcm[k & 1];
+        spread(pcm->nStreams * len, len / 4096 + 1, [&](size_t t, size_t threads) {
+            const size_t lo = len * t / threads, hi = len * (t + 1) / threads;
+            for (size_t s = 0; s < pcm->nStreams; ++s)
+                std::memcpy(static_cast<unsigned char*>(pcm->streams[s]) + f0 * pcmG * pcmB + lo, src + s * stride + lo, hi - lo);
+        });
+        const pcm_pack::ChannelStats* st = reinterpret_cast<const pcm_pack::ChannelStats*>(src + pcm->nStreams * stride);
+        for (size_t c = 0; c < nOut; ++c) {
+            pcm->peakBits[c] = std::max(pcm->peakBits[c], st[c].peakBits);
+            pcm->over[c] += st[c].over; pcm->nonfinite[c] += st[c].nonfinite;
+        }
+    };
+    auto deliver = [&](size_t k) { if (wantFloat) scatter(k); if (pcm) deliverPcm(k); };
     int result = kOk;
     size_t issued = 0, scattered = 0;
     // a failing HIP call ends the loop; the tail below drains both streams, releases what was deferred and reports the code —
@@ -1256,15 +1354,33 @@ int Engine::processBlocksHost(const float* const* in, size_t nIn, float* const* 
                 const uint64_t per = hb / bs, base = st.blocksRendered - nb;
                 for (uint64_t e = per; e <= nb; e += per) { if (hostBlockEnds.size() >= 65536) hostBlockEnds.pop_front(); hostBlockEnds.push_back(base + e); }
             }
+            size_t pcmCopy = 0;
+            if (pcm) {
+                // the pack kernel behind the set's last level, on the same stream: the output block is still warm in L2. Its packed
+                // half was drained by the D2H of set k - 2 (evOut above).
+                const size_t valid = std::min(nb * bs, numFrames - b0 * bs);
+                const size_t stride = (size_t)pcm_pack::stream_stride(valid, pcmG, pcmFmt), statsOff = pcm->nStreams * stride;
+                pcm->validOf[half] = (uint32_t)valid;
+                HOST_TRY(hipMemsetAsync(dPcm[half] + statsOff, 0, nOut * sizeof(pcm_pack::ChannelStats), stream));
+                PcmPackArgs a{};
+                a.src = dStageOut[half]; a.dst = dPcm[half]; a.stats = reinterpret_cast<pcm_pack::ChannelStats*>(dPcm[half] + statsOff);
+                a.rowBase = dPcmRowBase; a.time0 = sampleTime + (int64_t)(b0 * bs); a.streamStride = stride;
+                a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nOut; a.G = pcmG; a.numStreams = (uint32_t)pcm->nStreams;
+                a.validFrames = (uint32_t)valid; a.tilesPerBlock = pcm_pack::tiles_per_block((uint32_t)bs, pcmG); a.rowDwords = pcmRowDwords;
+                a.dither = pcm->spec.dither ? 1u : 0u; a.seed = pcm->spec.seed;
+                HOST_TRY(launch_pcm_pack(stream, a, pcmFmt));
+                pcmCopy = statsOff + nOut * sizeof(pcm_pack::ChannelStats);
+            }
             HOST_TRY(hipEventRecord(evRendered[half], stream));
             HOST_TRY(hipStreamWaitEvent(ioStream, evRendered[half], 0));
-            if (nOut) HOST_TRY(hipMemcpyAsync(hStageOut[half], dStageOut[half], nb * nOut * bs * sizeof(float), hipMemcpyDeviceToHost, ioStream));
+            if (wantFloat || !pcm) { if (nOut) HOST_TRY(hipMemcpyAsync(hStageOut[half], dStageOut[half], nb * nOut * bs * sizeof(float), hipMemcpyDeviceToHost, ioStream)); }
+            if (pcm) HOST_TRY(hipMemcpyAsync(hPcm[half], dPcm[half], pcmCopy, hipMemcpyDeviceToHost, ioStream));
             HOST_TRY(hipEventRecord(evOut[half], ioStream));
             issued = k + 1;
         }
         if (k >= 1) {   // set k - 1 arrives while set k renders
             HOST_TRY(hipEventSynchronize(evOut[(k - 1) & 1]));
-            if (nOut) scatter(k - 1);
+            if (nOut) deliver(k - 1);
             scattered = k;
         }
     }
@@ -1272,7 +1388,7 @@ int Engine::processBlocksHost(const float* const* in, size_t nIn, float* const* 
     if (issued > scattered && result == kOk) {       // the last set (every earlier one was scattered while its successor rendered)
         const size_t last = issued - 1;
         if (hipEventSynchronize(evOut[last & 1]) != hipSuccess) result = kHipError;
-        else if (nOut) scatter(last);
+        else if (nOut) deliver(last);
     }
     {
         RenderGuard lock(*this);

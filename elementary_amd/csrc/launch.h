@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include "device.h"
+#include "pcm_pack.h"
 
 namespace elemhip {
 
@@ -67,6 +68,18 @@ struct FftFrame {
 };
 // `maxSize`: the largest `size` among the frames — the launch's LDS is sized by it
 hipError_t launch_fft_frames(hipStream_t s, const FftFrame* framesDev, uint32_t count, uint32_t maxSize);
+// ---- PCM delivery (pcm_pack.hip): one workgroup per tile of (block, stream), pcm_pack.h ----
+struct PcmPackArgs {
+    const float*    src;            // the set's output, [block][numChannels][blockSize]
+    unsigned char*  dst;            // [stream] at `streamStride` bytes (a multiple of 16; the base 16-byte aligned): validFrames * G samples each
+    pcm_pack::ChannelStats* stats;  // [numStreams * G], added into
+    const uint16_t* rowBase;        // pcm_pack_row_table(G) on the device
+    int64_t         time0;          // sample time of the set's first frame (the dither's key)
+    uint64_t        streamStride;
+    uint32_t        blockSize, numChannels, G, numStreams, validFrames, tilesPerBlock, rowDwords, dither, seed;
+};
+uint32_t pcm_pack_row_table(uint32_t G, uint16_t* out);      // out[G]; returns PcmPackArgs::rowDwords
+hipError_t launch_pcm_pack(hipStream_t s, const PcmPackArgs& a, uint32_t format);
 hipError_t launch_bus_sum(hipStream_t s, float* dst, const float* const* partials, uint32_t count, size_t n);   // dst = ((p0 + p1) + p2) + ... (rank order)
 
 } // namespace elemhip

@@ -127,6 +127,84 @@ class OfflineRenderer:
                 if m > 0:
                     buf[k:k + m] = out[i, :m]
 
+    def process_pcm(self, inputs: Sequence[np.ndarray], num_streams: int, channels_per_stream: int, num_frames: int, fmt="s16",
+                    dither_seed: Optional[int] = None, want_float: bool = False, sample_time: Optional[int] = None):
+        """``process`` delivered as interleaved PCM packed on the GPU (``Runtime.process_blocks_pcm``, same arguments apart from the
+        engine): returns ``(streams, stats, planar)``. With listeners attached the render walks ``event_window_blocks()`` windows
+        with the blockwise relay between them, as ``process`` does; every window is packed at its absolute time, so the bytes are
+        those of one call."""
+        if len(inputs) != self.num_in:
+            raise ValueError(f"Invalid input data; expected {self.num_in} buffers.")
+        if int(num_streams) * int(channels_per_stream) != self.num_out:
+            raise ValueError(f"Invalid stream layout; expected {self.num_out} channels in all.")
+        pcm = getattr(self._rt, "process_blocks_pcm", None)
+        if pcm is None:
+            raise RuntimeError("this engine has no PCM delivery (process_blocks_pcm)")
+        bs, total = self.block_size, int(num_frames)
+        if sample_time is not None:
+            self._time = int(sample_time)
+        listening = any(self._listeners.values()) and hasattr(self._rt, "event_window_blocks")
+        w = max(1, int(self._rt.event_window_blocks())) * bs if listening else max(total, 1)
+        parts = []
+        for k in range(0, max(total, 1), w):
+            m = min(w, total - k)
+            x = None
+            if self.num_in:
+                x = np.zeros((self.num_in, m), dtype=np.float32)
+                for i, buf in enumerate(inputs):
+                    seg = np.asarray(buf[k:k + m], dtype=np.float32)
+                    x[i, :len(seg)] = seg
+            parts.append(pcm(x, num_streams, channels_per_stream, m, fmt, dither_seed=dither_seed, want_float=want_float, sample_time=self._time))
+            self._time += ((m + bs - 1) // bs) * bs
+            events = self._rt.process_queued_events(blockwise=True) if listening else self._rt.process_queued_events()
+            for kind, payload in events:
+                for cb in self._listeners.get(kind, []):
+                    cb(payload)
+        if len(parts) == 1:
+            return parts[0]
+        streams = [np.concatenate([p[0][s] for p in parts]) for s in range(int(num_streams))]
+        stats = {"peak": np.max([p[1]["peak"] for p in parts], axis=0), "over": np.sum([p[1]["over"] for p in parts], axis=0, dtype=np.uint64),
+                 "nonfinite": np.sum([p[1]["nonfinite"] for p in parts], axis=0, dtype=np.uint64)}
+        planar = np.concatenate([p[2] for p in parts], axis=1) if want_float else None
+        return streams, stats, planar
+
+    def write_wav(self, path, inputs: Sequence[np.ndarray], num_frames: int, fmt="s16", channels_per_stream: Optional[int] = None,
+                  dither_seed: Optional[int] = None, chunk_frames: int = 1 << 20):
+        """Render ``num_frames`` frames into RIFF/WAVE files, ``chunk_frames`` (rounded to whole blocks) per engine call: one file per
+        stream of ``channels_per_stream`` channels (default: all output channels in one file). ``path``: the file's name, or — for
+        more than one stream — a list of names or a name with ``{}`` for the stream number. Returns the statistics of the render."""
+        from .wav import WavWriter
+        G = self.num_out if channels_per_stream is None else int(channels_per_stream)
+        S = self.num_out // max(G, 1)
+        if isinstance(path, (list, tuple)):
+            paths = list(path)
+        elif S == 1:
+            paths = [str(path)]
+        else:
+            if "{}" not in str(path):
+                raise ValueError("several streams need a list of paths or a path with {} for the stream number")
+            paths = [str(path).format(s) for s in range(S)]
+        if len(paths) != S:
+            raise ValueError(f"{S} streams need {S} paths")
+        bs, total = self.block_size, int(num_frames)
+        chunk = max(bs, (int(chunk_frames) // bs) * bs)
+        writers = [WavWriter(p, fmt if isinstance(fmt, str) else {1: "s16", 2: "s24", 3: "f32"}[int(fmt)], G, self.sample_rate) for p in paths]
+        stats = None
+        try:
+            for k in range(0, total, chunk):
+                m = min(chunk, total - k)
+                streams, st, _ = self.process_pcm([np.asarray(b)[k:k + m] for b in inputs], S, G, m, fmt, dither_seed=dither_seed)
+                for wtr, a in zip(writers, streams):
+                    wtr.write(a)
+                if stats is None:
+                    stats = st
+                else:
+                    stats = {"peak": np.maximum(stats["peak"], st["peak"]), "over": stats["over"] + st["over"], "nonfinite": stats["nonfinite"] + st["nonfinite"]}
+        finally:
+            for wtr in writers:
+                wtr.close()
+        return stats
+
     def update_virtual_file_system(self, vfs: Dict[str, np.ndarray]) -> None:
         for k, v in vfs.items():
             self._rt.add_shared_resource(k, v)

@@ -50,6 +50,9 @@ def load_library() -> C.CDLL:
         _fpp = C.POINTER(C.POINTER(C.c_float))
         lib.elemhip_process_blocks_host.argtypes = [C.c_void_p, _fpp, C.c_size_t, _fpp, C.c_size_t, C.c_size_t, C.c_int64]
         lib.elemhip_process_blocks_host.restype = C.c_int
+        lib.elemhip_process_blocks_pcm.argtypes = [C.c_void_p, _fpp, C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, _fpp, C.c_size_t, C.c_int64,
+                                                   C.POINTER(_PcmSpec), C.POINTER(_PcmChannelStats)]
+        lib.elemhip_process_blocks_pcm.restype = C.c_int
         lib.elemhip_set_stream.argtypes = [C.c_void_p, C.c_void_p]
         lib.elemhip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
         lib.elemhip_get_stats.argtypes = [C.c_void_p, C.c_void_p]
@@ -61,6 +64,22 @@ def load_library() -> C.CDLL:
         lib.elemhip_sum_buses.restype = C.c_int
         _lib = lib
     return _lib
+
+
+class _PcmSpec(C.Structure):
+    _fields_ = [("format", C.c_uint32), ("channels_per_stream", C.c_uint32), ("dither", C.c_uint32), ("seed", C.c_uint32)]
+
+
+class _PcmChannelStats(C.Structure):
+    _fields_ = [("peak", C.c_float), ("reserved", C.c_uint32), ("over", C.c_uint64), ("nonfinite", C.c_uint64)]
+
+
+PCM_FORMATS = {"s16": 1, "s24": 2, "f32": 3}
+
+
+def pcm_format(fmt) -> int:
+    """'s16' / 's24' / 'f32' (or the C-ABI's 1 / 2 / 3) -> the C-ABI's format number; anything else is handed on for the engine to refuse."""
+    return PCM_FORMATS.get(fmt.lower(), 0) if isinstance(fmt, str) else int(fmt)
 
 
 class _Stats(C.Structure):
@@ -141,6 +160,51 @@ class Runtime(CRuntime):
             nb = (int(num_frames) + self.block_size - 1) // self.block_size
             self.sample_time += nb * self.block_size
         return out
+
+    def process_blocks_pcm(self, inputs, num_streams: int, channels_per_stream: int, num_frames: Optional[int] = None, fmt="s16",
+                           dither_seed: Optional[int] = None, want_float: bool = False, sample_time: Optional[int] = None):
+        """``elemhip_process_blocks_pcm``: the offline block loop delivered as interleaved PCM, packed on the GPU.
+
+        The ``num_streams * channels_per_stream`` output channels come back as ``num_streams`` arrays — ``int16 [frames, G]`` for
+        ``fmt`` 's16', ``uint8 [frames, G, 3]`` (little-endian) for 's24', ``float32 [frames, G]`` for 'f32'; sample ``(frame, g)`` of
+        stream ``s`` is output channel ``s * G + g``. ``dither_seed``: None = no dither, else TPDF dither keyed on it and on the
+        absolute frame time. Returns ``(streams, stats, planar)``: ``stats`` = ``{'peak': float32[nOut], 'over': uint64[nOut],
+        'nonfinite': uint64[nOut]}`` over the delivered frames, ``planar`` = float32 ``[nOut, frames]`` (the very samples that were
+        packed) when ``want_float``, else None.
+        """
+        import numpy as np
+        from ._cabi import _ptr_array
+        rows = []
+        if inputs is not None:
+            a = np.ascontiguousarray(inputs, dtype=np.float32)
+            if a.ndim == 1:
+                a = a[None, :]
+            rows = [a[i] for i in range(a.shape[0])]
+            if num_frames is None:
+                num_frames = a.shape[1]
+        if num_frames is None:
+            raise ValueError("num_frames is needed without inputs")
+        n, S, G, code = int(num_frames), int(num_streams), int(channels_per_stream), pcm_format(fmt)
+        shape, dtype = {1: ((n, G), np.int16), 2: ((n, G, 3), np.uint8)}.get(code, ((n, G), np.float32))
+        streams = [np.zeros(shape, dtype=dtype) for _ in range(S)]
+        planar = np.zeros((S * G, n), dtype=np.float32) if want_float else None
+        stats = (_PcmChannelStats * max(1, S * G))()
+        spec = _PcmSpec(code, G, 0 if dither_seed is None else 1, 0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFF)
+        sp = (C.c_void_p * max(1, S))(*[C.c_void_p(a.ctypes.data) for a in streams])
+        st = self.sample_time if sample_time is None else int(sample_time)
+        rc = self._lib.elemhip_process_blocks_pcm(self._h, _ptr_array(rows), len(rows), sp, S,
+                                                  _ptr_array([planar[i] for i in range(S * G)]) if want_float else None,
+                                                  n, st, C.byref(spec), stats)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_process_blocks_pcm failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        if sample_time is None:
+            self.sample_time += ((n + self.block_size - 1) // self.block_size) * self.block_size
+        out_stats = {"peak": np.array([stats[c].peak for c in range(S * G)], dtype=np.float32),
+                     "over": np.array([stats[c].over for c in range(S * G)], dtype=np.uint64),
+                     "nonfinite": np.array([stats[c].nonfinite for c in range(S * G)], dtype=np.uint64)}
+        return streams, out_stats, planar
 
     def event_window_blocks(self) -> int:
         """Blocks a ``process_queued_events(blockwise=True)`` window may span and still equal a relay after every block."""

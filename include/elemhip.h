@@ -103,6 +103,27 @@ int elemhip_process_blocks(elemhip_t*, const float* in_dev, size_t nIn, float* o
 int elemhip_process_blocks_host(elemhip_t*, const float* const* in, size_t nIn, float* const* out, size_t nOut,
                                 size_t numFrames, int64_t sampleTime);
 
+/* EXTENSION (no counterpart in the reference): the same render delivered as interleaved PCM, packed on the GPU behind the last
+ * render level of every launch set (elementary_amd/csrc/pcm_pack.hip; the arithmetic: pcm_pack.h). The nStreams * channels_per_stream
+ * output channels leave as nStreams streams; sample (frame, g) of stream s is output channel s * channels_per_stream + g.
+ *   format  1: little-endian int16   2: 3 bytes per sample, little-endian two's complement, packed   3: float32, bits unchanged
+ *   dither  0: none   1: TPDF, 2 LSB peak to peak, keyed on `seed`, the channel and the ABSOLUTE frame time (sampleTime + frame):
+ *           the bytes do not depend on how a render is cut into calls. Integer formats round to nearest even and clamp; a non-finite
+ *           sample is delivered as 0 and counted.
+ *   streams nStreams buffers of numFrames * channels_per_stream samples each; overwritten
+ *   planar  NULL, or nStreams * channels_per_stream planar float arrays of numFrames frames: the very samples that were packed
+ *   stats   NULL, or one per channel over the delivered frames: peak = max |x| of the finite samples, over = finite |x| > 1.0,
+ *           nonfinite — the same in every format
+ * Launch sets, double buffering and block-size rules are those of elemhip_process_blocks_host. Codes: 103 when nStreams *
+ * channels_per_stream exceeds the output bus (1024), 8 for an unknown format, channels_per_stream == 0 or NULL streams / spec, 101 on
+ * a dry handle. */
+typedef struct elemhip_pcm_spec { uint32_t format, channels_per_stream, dither /*0 none, 1 TPDF*/, seed; } elemhip_pcm_spec;
+typedef struct elemhip_pcm_channel_stats { float peak; uint32_t reserved; uint64_t over, nonfinite; } elemhip_pcm_channel_stats;
+int elemhip_process_blocks_pcm(elemhip_t*, const float* const* in, size_t nIn,
+                               void* const* streams, size_t nStreams,   /* nStreams buffers of numFrames * channels_per_stream samples */
+                               float* const* planar,                    /* NULL, or nStreams*channels_per_stream planar float arrays: the very samples that were packed */
+                               size_t numFrames, int64_t sampleTime, const elemhip_pcm_spec*, elemhip_pcm_channel_stats* stats /* NULL or one per channel */);
+
 /* bool addSharedResource(name, unique_ptr<SharedResource>)       Runtime.h:83,461-465 (insert-only) */
 int    elemhip_add_shared_resource(elemhip_t*, const char* name, const float* const* channels, size_t nCh, size_t nSamples);
 /* void pruneSharedResources()                                    Runtime.h:89,467-471 */

@@ -115,6 +115,17 @@ public:
         return rc;
     }
 
+    // EXTENSION (no counterpart in elem::Runtime): the same block loop delivered as interleaved PCM, packed on the GPU
+    // (elemhip_process_blocks_pcm): nStreams buffers of numFrames * spec.channels_per_stream samples, stream s / sample (frame, g) =
+    // output channel s * G + g; `planar` (or null) receives the floats that were packed, `stats` (or null) one entry per channel.
+    int processBlocksPcm(const float** in, size_t nIn, void* const* streams, size_t nStreams, float** planar, size_t numFrames,
+                         elemhip_pcm_spec const& spec, elemhip_pcm_channel_stats* stats = nullptr, void* userData = nullptr) {
+        const int64_t t = userData ? *static_cast<int64_t*>(userData) : implicitTime;
+        const int rc = elemhip_process_blocks_pcm(h, in, nIn, streams, nStreams, planar, numFrames, t, &spec, stats);
+        if (!userData) implicitTime += (int64_t)numFrames;
+        return rc;
+    }
+
     // bool addSharedResource(name, unique_ptr<SharedResource>)         Runtime.h:83 — planar float channels
     bool addSharedResource(std::string const& name, const float* const* channels, size_t nCh, size_t nSamples) {
         return elemhip_add_shared_resource(h, name.c_str(), channels, nCh, nSamples) != 0;
