@@ -131,6 +131,17 @@ int elemhip_process_blocks_pcm(elemhip_t* h, const float* const* in, size_t nIn,
     return h->engine.processBlocksPcm(in, nIn, streams, nStreams, planar, numFrames, st, sp, reinterpret_cast<Engine::PcmChannelStats*>(stats));
 }
 
+int elemhip_process_blocks_pcm_io(elemhip_t* h, const void* const* inStreams, size_t nInStreams, const elemhip_pcm_in_spec* inSpec,
+                                  void* const* outStreams, size_t nOutStreams, const elemhip_pcm_spec* outSpec, float* const* planar, size_t nPlanar,
+                                  size_t numFrames, int64_t st, elemhip_pcm_channel_stats* stats) {
+    if (!h || (nInStreams && (!inSpec || !inStreams))) return elemhip::kInvalidInstructionFormat;
+    const Engine::PcmSource src{inSpec ? inSpec->format : 0u, inSpec ? inSpec->channels_per_stream : 0u, inStreams, nInStreams};
+    Engine::PcmSpec sp{};
+    if (outSpec) sp = Engine::PcmSpec{outSpec->format, outSpec->channels_per_stream, outSpec->dither, outSpec->seed};
+    return h->engine.processBlocksPcmIo(src, outStreams, nOutStreams, outSpec ? &sp : nullptr, planar, nPlanar, numFrames, st,
+                                        reinterpret_cast<Engine::PcmChannelStats*>(stats));
+}
+
 int elemhip_add_shared_resource(elemhip_t* h, const char* name, const float* const* ch, size_t nCh, size_t nSamples) {
     if (!h || !name) return 0;
     return h->engine.addSharedResource(name, ch, nCh, nSamples) ? 1 : 0;

@@ -185,6 +185,8 @@ Engine::~Engine() {
     }
     for (int k = 0; k < 2; ++k) { if (hPcm[k]) (void)hipHostFree(hPcm[k]); if (dPcm[k]) (void)hipFree(dPcm[k]); }
     if (dPcmRowBase) (void)hipFree(dPcmRowBase);
+    for (int k = 0; k < 2; ++k) { if (hPcmIn[k]) (void)hipHostFree(hPcmIn[k]); if (dPcmIn[k]) (void)hipFree(dPcmIn[k]); }
+    if (dPcmInRowBase) (void)hipFree(dPcmInRowBase);
     if (ioStream) (void)hipStreamDestroy(ioStream);
     if (relayStream) { (void)hipStreamSynchronize(relayStream); (void)hipStreamDestroy(relayStream); }
     if (evRelay) (void)hipEventDestroy(evRelay);

@@ -220,6 +220,16 @@ public:
     struct PcmChannelStats { float peak; uint32_t reserved; uint64_t over, nonfinite; };
     int processBlocksPcm(const float* const* in, size_t nIn, void* const* streams, size_t nStreams, float* const* planar,
                          size_t numFrames, int64_t sampleTime, const PcmSpec& spec, PcmChannelStats* stats);
+    // Both deliveries fed with PCM (pcm_unpack.h): the nIn = src.nStreams * src.channelsPerStream input channels arrive as interleaved
+    // streams of numFrames * G samples — stream s, sample (frame, g) = input channel s * G + g — int16, packed 24-bit or float32. Per
+    // launch set one contiguous memcpy per stream fills a pinned packed half, one H2D brings it over and an unpack kernel
+    // (pcm_unpack.hip) converts and de-interleaves it into the set's input block where the render kernels read it; a short tail is
+    // zero there as it is for planar input. `outSpec` null: the `nPlanar` output channels as planar floats (processBlocksHost);
+    // else processBlocksPcm's delivery, `planar` (may be null) nOutStreams * G arrays. Where the block-by-block path renders, the
+    // header's scalar loop unpacks on the host: the same floats.
+    struct PcmSource { uint32_t format, channelsPerStream; const void* const* streams; size_t nStreams; };
+    int processBlocksPcmIo(const PcmSource& src, void* const* outStreams, size_t nOutStreams, const PcmSpec* outSpec, float* const* planar,
+                           size_t nPlanar, size_t numFrames, int64_t sampleTime, PcmChannelStats* stats);
     // render `numBlocks` blocks with a HIP event pair around every kernel launch; msOut[l] = mean
     // duration of launch level l (l < numLevels), msOut[numLevels] = epilogue. Returns levels + 1.
     int timeLaunches(size_t nOut, size_t numBlocks, float* msOut, size_t cap);
@@ -366,8 +376,16 @@ private:
     size_t pcmBytes = 0;
     uint16_t* dPcmRowBase = nullptr; uint32_t pcmTableGroup = 0, pcmRowDwords = 0;
     int ensurePcmStaging(size_t bytes, uint32_t group);
+    // PCM input (processBlocksPcmIo): packed halves in front of the float input halves, the unpack kernel's row table
+    unsigned char* hPcmIn[2] = {nullptr, nullptr}; unsigned char* dPcmIn[2] = {nullptr, nullptr};
+    size_t pcmInBytes = 0;
+    uint16_t* dPcmInRowBase = nullptr; uint32_t pcmInTableGroup = 0, pcmInRowDwords = 0;
+    int ensurePcmInStaging(size_t bytes, uint32_t group);
+    int growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], size_t& have, size_t want);
+    int ensureRowTable(uint16_t*& dev, uint32_t& haveGroup, uint32_t& dwords, uint32_t group);
     // the set loop of processBlocksHost / processBlocksPcm (`pcm` null: planar floats only)
-    int renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm);
+    int renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
+                       const PcmSource* src = nullptr);      // `src`: the inputs as PCM streams (`in` is null then)
     // enqueue `numBlocks` blocks on `stream` (no synchronise at the end): the body of processBlocks
     int enqueueBlocks(const float* inDev, size_t nIn, float* outDev, size_t nOut, size_t numBlocks, int64_t sampleTime);
 

@@ -1,6 +1,7 @@
 // engine_render.cpp — the per-block launch sequence (process), launch sets (processBlocks / processBlocksHost), the resident
 // kernel's host side and the measurement calls. Everything a render call reaches lives in this unit or inline in engine.h.
 #include "engine_impl.h"
+#include "pcm_unpack.h"
 #include <functional>
 #include <thread>
 
@@ -1144,36 +1145,49 @@ int Engine::ensureHostStaging(size_t outFloats, size_t inFloats) {
     return grow(hStageIn, dStageIn, stageInFloats, inFloats);
 }
 
-int Engine::ensurePcmStaging(size_t bytes, uint32_t group) {
-    if (group != pcmTableGroup) {
-        // (the device is idle between calls: every host-path call ends with both streams synchronised)
-        if (!dPcmRowBase) HIP_OK(hipMalloc((void**)&dPcmRowBase, pcm_pack::kMaxGroup * sizeof(uint16_t)));
-        std::vector<uint16_t> table(group);
-        const uint32_t dwords = pcm_pack_row_table(group, table.data());
-        HIP_OK(hipStreamSynchronize(stream));
-        HIP_OK(hipMemcpy(dPcmRowBase, table.data(), group * sizeof(uint16_t), hipMemcpyHostToDevice));
-        pcmTableGroup = group; pcmRowDwords = dwords;
-    }
-    if (bytes <= pcmBytes) return kOk;
+int Engine::ensureRowTable(uint16_t*& dev, uint32_t& haveGroup, uint32_t& dwords, uint32_t group) {
+    if (group == haveGroup) return kOk;
+    // (the device is idle between calls: every host-path call ends with both streams synchronised)
+    if (!dev) HIP_OK(hipMalloc((void**)&dev, pcm_pack::kMaxGroup * sizeof(uint16_t)));
+    std::vector<uint16_t> table(group);
+    const uint32_t n = pcm_pack_row_table(group, table.data());
+    HIP_OK(hipStreamSynchronize(stream));
+    HIP_OK(hipMemcpy(dev, table.data(), group * sizeof(uint16_t), hipMemcpyHostToDevice));
+    haveGroup = group; dwords = n;
+    return kOk;
+}
+
+int Engine::growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], size_t& have, size_t want) {
+    if (want <= have) return kOk;
     HIP_OK(hipStreamSynchronize(stream));
     if (ioStream) HIP_OK(hipStreamSynchronize(ioStream));
-    // the new buffers first: a failed allocation leaves the old pair (and pcmBytes) as they were
+    // the new buffers first: a failed allocation leaves the old pair (and `have`) as they were
     unsigned char* nh[2] = {nullptr, nullptr}; unsigned char* nd[2] = {nullptr, nullptr};
     bool ok = true;
     for (int k = 0; k < 2 && ok; ++k)
-        ok = hipHostMalloc((void**)&nh[k], bytes, hipHostMallocDefault) == hipSuccess && hipMalloc((void**)&nd[k], bytes) == hipSuccess;
+        ok = hipHostMalloc((void**)&nh[k], want, hipHostMallocDefault) == hipSuccess && hipMalloc((void**)&nd[k], want) == hipSuccess;
     if (!ok) {
         for (int k = 0; k < 2; ++k) { if (nh[k]) (void)hipHostFree(nh[k]); if (nd[k]) (void)hipFree(nd[k]); }
         (void)hipGetLastError();
         return kHipError;
     }
     for (int k = 0; k < 2; ++k) {
-        if (hPcm[k]) (void)hipHostFree(hPcm[k]);
-        if (dPcm[k]) (void)hipFree(dPcm[k]);
-        hPcm[k] = nh[k]; dPcm[k] = nd[k];
+        if (h[k]) (void)hipHostFree(h[k]);
+        if (d[k]) (void)hipFree(d[k]);
+        h[k] = nh[k]; d[k] = nd[k];
     }
-    pcmBytes = bytes;
+    have = want;
     return kOk;
+}
+
+int Engine::ensurePcmStaging(size_t bytes, uint32_t group) {
+    const int rc = ensureRowTable(dPcmRowBase, pcmTableGroup, pcmRowDwords, group);
+    return rc != kOk ? rc : growPackedHalves(hPcm, dPcm, pcmBytes, bytes);
+}
+
+int Engine::ensurePcmInStaging(size_t bytes, uint32_t group) {
+    const int rc = ensureRowTable(dPcmInRowBase, pcmInTableGroup, pcmInRowDwords, group);
+    return rc != kOk ? rc : growPackedHalves(hPcmIn, dPcmIn, pcmInBytes, bytes);
 }
 
 // what a processBlocksPcm call carries through the set loop
@@ -1213,9 +1227,37 @@ int Engine::processBlocksPcm(const float* const* in, size_t nIn, void* const* st
     return rc;
 }
 
-// (`out` may be null with `pcm`: nobody asked for the planar floats)
-int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm) {
+int Engine::processBlocksPcmIo(const PcmSource& src, void* const* outStreams, size_t nOutStreams, const PcmSpec* outSpec, float* const* planar,
+                               size_t nPlanar, size_t numFrames, int64_t sampleTime, PcmChannelStats* stats) {
+    if (src.nStreams && (!pcm_pack::format_ok(src.format) || src.channelsPerStream == 0u || !src.streams)) return kInvalidInstructionFormat;
+    if (outSpec ? (!pcm_pack::format_ok(outSpec->format) || outSpec->channelsPerStream == 0u || (nOutStreams && !outStreams)) : (nPlanar && !planar))
+        return kInvalidInstructionFormat;
+    for (size_t s = 0; s < src.nStreams; ++s) if (!src.streams[s] && numFrames) return kInvalidInstructionFormat;
+    if (src.nStreams > kMaxHostIn || src.nStreams * (size_t)src.channelsPerStream > kMaxHostIn) return kTooManyChannels;
+    if (outSpec ? (nOutStreams > kMaxOutBus || nOutStreams * (size_t)outSpec->channelsPerStream > kMaxOutBus) : nPlanar > kMaxOutBus) return kTooManyChannels;
+    if (dry) return kNoDevice;
+    const size_t nIn = src.nStreams * src.channelsPerStream;
+    const PcmSource* from = src.nStreams ? &src : nullptr;
+    if (!outSpec) return renderHostSets(nullptr, nIn, planar, nPlanar, numFrames, sampleTime, nullptr, from);
+    const size_t nOut = nOutStreams * outSpec->channelsPerStream;
+    PcmJob job;
+    job.spec = *outSpec; job.streams = outStreams; job.nStreams = nOutStreams;
+    job.peakBits.assign(nOut, 0u); job.over.assign(nOut, 0u); job.nonfinite.assign(nOut, 0u);
+    const int rc = nOut ? renderHostSets(nullptr, nIn, planar, nOut, numFrames, sampleTime, &job, from) : kOk;
+    if (stats)
+        for (size_t c = 0; c < nOut; ++c) {
+            std::memcpy(&stats[c].peak, &job.peakBits[c], 4);
+            stats[c].reserved = 0u; stats[c].over = job.over[c]; stats[c].nonfinite = job.nonfinite[c];
+        }
+    return rc;
+}
+
+// (`out` may be null with `pcm`: nobody asked for the planar floats; with `src` the nIn input channels come from its streams, `in` is null)
+int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
+                           const PcmSource* src) {
     const size_t bs = (size_t)blockSize;
+    const uint32_t srcG = src ? src->channelsPerStream : 1u, srcFmt = src ? src->format : 0u;
+    const size_t srcB = src ? pcm_pack::sample_bytes(srcFmt) : 0;
     const bool wantFloat = nOut > 0 && out != nullptr;
     const uint32_t pcmG = pcm ? pcm->spec.channelsPerStream : 1u, pcmFmt = pcm ? pcm->spec.format : 0u;
     const size_t pcmB = pcm ? pcm_pack::sample_bytes(pcmFmt) : 0;
@@ -1230,9 +1272,10 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         std::vector<float*> op(nOut);
         std::vector<float> tailIn, tailOut;
         std::vector<uint8_t*> sp(pcm ? pcm->nStreams : 0);
+        std::vector<const unsigned char*> srcAt(src ? src->nStreams : 0);
         for (size_t f0 = 0; f0 < numFrames; f0 += hb) {
             const size_t nf = std::min(hb, numFrames - f0);
-            for (size_t c = 0; c < nIn; ++c) ip[c] = in[c] + f0;
+            for (size_t c = 0; c < nIn; ++c) ip[c] = src ? nullptr : in[c] + f0;
             for (size_t c = 0; c < nOut; ++c) op[c] = wantFloat ? out[c] + f0 : nullptr;
             if (nf < hb || pcm) {
                 // the last, partly filled host block is still a whole block to the engine (offline-renderer/index.ts:104-131: inputs
@@ -1240,7 +1283,13 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 tailOut.assign(nOut * hb, 0.0f);
                 for (size_t c = 0; c < nOut; ++c) op[c] = tailOut.data() + c * hb;
             }
-            if (nf < hb) {
+            if (src) {
+                // the inputs are needed on the host: the header's scalar loop unpacks them — the kernel's functions, the kernel's floats
+                tailIn.resize(nIn * hb);
+                for (size_t s = 0; s < src->nStreams; ++s) srcAt[s] = static_cast<const unsigned char*>(src->streams[s]) + f0 * srcG * srcB;
+                pcm_unpack::unpack_host(srcFmt, srcG, (uint32_t)src->nStreams, srcAt.data(), nf, tailIn.data(), hb, hb);
+                for (size_t c = 0; c < nIn; ++c) ip[c] = tailIn.data() + c * hb;
+            } else if (nf < hb) {
                 tailIn.assign(nIn * hb, 0.0f);
                 for (size_t c = 0; c < nIn; ++c) { std::memcpy(tailIn.data() + c * hb, in[c] + f0, nf * sizeof(float)); ip[c] = tailIn.data() + c * hb; }
             }
@@ -1270,6 +1319,10 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         if (hb > bs) setBlocks = std::min(numBlocks, std::max(hb / bs, setBlocks / (hb / bs) * (hb / bs)));
         int rc = ensureHostStaging(setBlocks * std::max<size_t>(nOut, 1) * bs, setBlocks * std::max<size_t>(nIn, 1) * bs);
         if (rc != kOk) return rc;
+        if (src) {
+            rc = ensurePcmInStaging(src->nStreams * (size_t)pcm_pack::stream_stride(setBlocks * bs, srcG, srcFmt), srcG);
+            if (rc != kOk) return rc;
+        }
         if (pcm) {
             rc = ensurePcmStaging(pcm->nStreams * (size_t)pcm_pack::stream_stride(setBlocks * bs, pcmG, pcmFmt) + nOut * sizeof(pcm_pack::ChannelStats), pcmG);
             if (rc != kOk) return rc;
@@ -1323,10 +1376,22 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
     for (size_t k = 0; k < numSets; ++k) {
         const size_t b0 = k * setBlocks, nb = std::min(setBlocks, numBlocks - b0);
         const int half = (int)(k & 1);
+        // (sets hold whole host blocks, so a set starts in front of numFrames)
+        const size_t srcValid = src ? std::min(nb * bs, numFrames - b0 * bs) : 0, srcStride = src ? (size_t)pcm_pack::stream_stride(srcValid, srcG, srcFmt) : 0;
         if (nIn) {
             if (k >= 2) HOST_TRY(hipEventSynchronize(evIn[half]));     // the H2D of set k - 2 has left this pinned half
+            if (src) {
+                // one contiguous stretch per stream: the set's valid frames, as they lie in the caller's streams
+                const size_t len = srcValid * srcG * srcB;
+                unsigned char* dst = hPcmIn[half];
+                spread(src->nStreams * len, len / 4096 + 1, [&](size_t t, size_t threads) {
+                    const size_t lo = len * t / threads, hi = len * (t + 1) / threads;
+                    for (size_t s = 0; s < src->nStreams; ++s)
+                        std::memcpy(dst + s * srcStride + lo, static_cast<const unsigned char*>(src->streams[s]) + b0 * bs * srcG * srcB + lo, hi - lo);
+                });
+            }
             float* dst = hStageIn[half];
-            for (size_t b = 0; b < nb; ++b) {
+            for (size_t b = 0; b < nb && !src; ++b) {
                 const size_t f0 = (b0 + b) * bs;
                 const size_t n = f0 < numFrames ? std::min(bs, numFrames - f0) : 0;
                 for (size_t c = 0; c < nIn; ++c) {
@@ -1342,9 +1407,23 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             if (nIn) {
                 // (the copy stream is in order: this H2D runs behind the D2H of set k - 2, which waited for that set's render,
                 //  the last reader of this device half)
-                HOST_TRY(hipMemcpyAsync(dStageIn[half], hStageIn[half], nb * nIn * bs * sizeof(float), hipMemcpyHostToDevice, ioStream));
+                if (src) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], src->nStreams * srcStride, hipMemcpyHostToDevice, ioStream))
+                else HOST_TRY(hipMemcpyAsync(dStageIn[half], hStageIn[half], nb * nIn * bs * sizeof(float), hipMemcpyHostToDevice, ioStream));
                 HOST_TRY(hipEventRecord(evIn[half], ioStream));
                 HOST_TRY(hipStreamWaitEvent(stream, evIn[half], 0));
+                if (src) {
+                    // the unpack kernel in front of the set's first level, on the render's stream. Both halves it touches are free:
+                    // dStageIn[half] was last read by the render of set k - 2, earlier on this stream; dPcmIn[half] was last read by
+                    // the unpack of set k - 2, earlier on this stream too, and the H2D that refilled it ran behind the D2H of set
+                    // k - 1 on the copy stream, which waited for evRendered of that set — recorded behind both. The kernel writes every
+                    // row of all nb blocks, zeros behind srcValid: nothing of set k - 2 is left in the half.
+                    PcmUnpackArgs a{};
+                    a.src = dPcmIn[half]; a.dst = dStageIn[half]; a.rowBase = dPcmInRowBase; a.streamStride = srcStride;
+                    a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nIn; a.G = srcG; a.numStreams = (uint32_t)src->nStreams;
+                    a.validFrames = (uint32_t)srcValid; a.numBlocks = (uint32_t)nb; a.tilesPerBlock = pcm_pack::tiles_per_block((uint32_t)bs, srcG);
+                    a.rowDwords = pcmInRowDwords;
+                    HOST_TRY(launch_pcm_unpack(stream, a, srcFmt));
+                }
             }
             if (k >= 2) HOST_TRY(hipStreamWaitEvent(stream, evOut[half], 0));   // the D2H of set k - 2 has drained this device half
             int rc = enqueueBlocks(nIn ? dStageIn[half] : nullptr, nIn, nOut ? dStageOut[half] : nullptr, nOut, nb,

@@ -80,6 +80,15 @@ struct PcmPackArgs {
 };
 uint32_t pcm_pack_row_table(uint32_t G, uint16_t* out);      // out[G]; returns PcmPackArgs::rowDwords
 hipError_t launch_pcm_pack(hipStream_t s, const PcmPackArgs& a, uint32_t format);
+// ---- PCM input (pcm_unpack.hip): the inverse, one workgroup per tile of (block, stream), pcm_unpack.h ----
+struct PcmUnpackArgs {
+    const unsigned char* src;       // [stream] at `streamStride` bytes (a multiple of 16; the base 16-byte aligned): validFrames * G samples each
+    float*          dst;            // the set's input, [numBlocks][numChannels][blockSize]: rows s * G + g of every block are written whole
+    const uint16_t* rowBase;        // pcm_pack_row_table(G) on the device
+    uint64_t        streamStride;
+    uint32_t        blockSize, numChannels, G, numStreams, validFrames, numBlocks, tilesPerBlock, rowDwords;   // frames behind validFrames: zero
+};
+hipError_t launch_pcm_unpack(hipStream_t s, const PcmUnpackArgs& a, uint32_t format);
 hipError_t launch_bus_sum(hipStream_t s, float* dst, const float* const* partials, uint32_t count, size_t n);   // dst = ((p0 + p1) + p2) + ... (rank order)
 
 } // namespace elemhip

@@ -205,6 +205,106 @@ class OfflineRenderer:
                 wtr.close()
         return stats
 
+    def process_pcm_io(self, in_streams: Sequence[np.ndarray], in_fmt, num_frames: Optional[int] = None, out_fmt=None,
+                       num_streams: Optional[int] = None, channels_per_stream: Optional[int] = None, dither_seed: Optional[int] = None,
+                       want_float: bool = False, sample_time: Optional[int] = None):
+        """``process`` / ``process_pcm`` fed with interleaved PCM that is unpacked on the GPU (``Runtime.process_blocks_pcm_io``):
+        ``in_streams`` are arrays in stream layout (``WavReader.read``, or what ``process_pcm`` returns) that together hold the
+        ``num_input_channels`` input channels; a stream shorter than ``num_frames`` is padded with silence. ``out_fmt`` None: returns
+        float32 ``[num_output_channels, num_frames]``; else ``(streams, stats, planar)`` as ``process_pcm`` does. With listeners attached
+        the render walks ``event_window_blocks()`` windows with the blockwise relay between them, as ``process`` does."""
+        pcm_io = getattr(self._rt, "process_blocks_pcm_io", None)
+        if pcm_io is None:
+            raise RuntimeError("this engine takes no PCM input (process_blocks_pcm_io)")
+        ins = [np.asarray(a) for a in in_streams]
+        if sum(int(a.shape[1]) for a in ins) != self.num_in:
+            raise ValueError(f"Invalid input data; expected {self.num_in} channels in all.")
+        if out_fmt is not None and int(num_streams) * int(channels_per_stream) != self.num_out:
+            raise ValueError(f"Invalid stream layout; expected {self.num_out} channels in all.")
+        bs = self.block_size
+        total = int(num_frames) if num_frames is not None else (int(ins[0].shape[0]) if ins else 0)
+        if sample_time is not None:
+            self._time = int(sample_time)
+        listening = any(self._listeners.values()) and hasattr(self._rt, "event_window_blocks")
+        w = max(1, int(self._rt.event_window_blocks())) * bs if listening else max(total, 1)
+        parts = []
+        for k in range(0, max(total, 1), w):
+            m = min(w, total - k)
+            x = []
+            for a in ins:
+                seg = a[k:k + m]
+                if seg.shape[0] < m:      # (silence is all-zero bytes in every format)
+                    seg = np.concatenate([seg, np.zeros((m - seg.shape[0],) + a.shape[1:], dtype=a.dtype)])
+                x.append(seg)
+            parts.append(pcm_io(x, in_fmt, self.num_out, m, out_fmt, num_streams, channels_per_stream, dither_seed=dither_seed,
+                                want_float=want_float, sample_time=self._time))
+            self._time += ((m + bs - 1) // bs) * bs
+            events = self._rt.process_queued_events(blockwise=True) if listening else self._rt.process_queued_events()
+            for kind, payload in events:
+                for cb in self._listeners.get(kind, []):
+                    cb(payload)
+        if len(parts) == 1:
+            return parts[0]
+        if out_fmt is None:
+            return np.concatenate(parts, axis=1)
+        streams = [np.concatenate([p[0][s] for p in parts]) for s in range(int(num_streams))]
+        stats = {"peak": np.max([p[1]["peak"] for p in parts], axis=0), "over": np.sum([p[1]["over"] for p in parts], axis=0, dtype=np.uint64),
+                 "nonfinite": np.sum([p[1]["nonfinite"] for p in parts], axis=0, dtype=np.uint64)}
+        planar = np.concatenate([p[2] for p in parts], axis=1) if want_float else None
+        return streams, stats, planar
+
+    def process_wav(self, in_paths, out_paths, out_fmt="s16", channels_per_stream: Optional[int] = None, num_frames: Optional[int] = None,
+                    dither_seed: Optional[int] = None, chunk_frames: int = 1 << 20):
+        """RIFF/WAVE files through the graph into RIFF/WAVE files, ``chunk_frames`` (rounded to whole blocks) per engine call; the samples
+        cross the host as they lie in the files and are converted on the GPU in both directions. ``in_paths``: one name or a list —
+        the files' channels become the input channels in file order (files of one format, one channel count and the renderer's
+        sample rate). ``out_paths`` / ``channels_per_stream``: as ``write_wav``'s ``path``. ``num_frames``: frames to render, default
+        the (longest) input's length; longer than that — a reverb's tail — renders the rest from silence. Returns the statistics."""
+        from .wav import WavReader, WavWriter
+        ins = [str(in_paths)] if isinstance(in_paths, (str, bytes)) or hasattr(in_paths, "__fspath__") else [str(p) for p in in_paths]
+        G = self.num_out if channels_per_stream is None else int(channels_per_stream)
+        S = self.num_out // max(G, 1)
+        if isinstance(out_paths, (list, tuple)):
+            outs = [str(p) for p in out_paths]
+        elif S == 1:
+            outs = [str(out_paths)]
+        else:
+            if "{}" not in str(out_paths):
+                raise ValueError("several streams need a list of paths or a path with {} for the stream number")
+            outs = [str(out_paths).format(s) for s in range(S)]
+        if len(outs) != S:
+            raise ValueError(f"{S} streams need {S} paths")
+        fmt = out_fmt if isinstance(out_fmt, str) else {1: "s16", 2: "s24", 3: "f32"}[int(out_fmt)]
+        readers, writers, stats = [], [], None
+        try:
+            for p in ins:
+                readers.append(WavReader(p))
+            for r in readers:
+                if r.sample_rate != int(round(self.sample_rate)):
+                    raise ValueError(f"sample rate {r.sample_rate} of an input file, the renderer runs at {int(round(self.sample_rate))}")
+                if (r.fmt, r.channels) != (readers[0].fmt, readers[0].channels):
+                    raise ValueError(f"input files of one kind are expected: {readers[0].fmt} x {readers[0].channels} and {r.fmt} x {r.channels}")
+            if sum(r.channels for r in readers) != self.num_in:
+                raise ValueError(f"Invalid input data; expected {self.num_in} channels in all.")
+            bs = self.block_size
+            total = int(num_frames) if num_frames is not None else max([r.frames for r in readers], default=0)
+            chunk = max(bs, (int(chunk_frames) // bs) * bs)
+            writers = [WavWriter(p, fmt, G, self.sample_rate) for p in outs]
+            in_fmt = readers[0].fmt if readers else "s16"
+            for k in range(0, total, chunk):
+                m = min(chunk, total - k)
+                streams, st, _ = self.process_pcm_io([r.read(m) for r in readers], in_fmt, m, fmt, S, G, dither_seed=dither_seed)
+                for wtr, a in zip(writers, streams):
+                    wtr.write(a)
+                if stats is None:
+                    stats = st
+                else:
+                    stats = {"peak": np.maximum(stats["peak"], st["peak"]), "over": stats["over"] + st["over"], "nonfinite": stats["nonfinite"] + st["nonfinite"]}
+        finally:
+            for x in readers + writers:
+                x.close()
+        return stats
+
     def update_virtual_file_system(self, vfs: Dict[str, np.ndarray]) -> None:
         for k, v in vfs.items():
             self._rt.add_shared_resource(k, v)

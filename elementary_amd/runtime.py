@@ -53,6 +53,9 @@ def load_library() -> C.CDLL:
         lib.elemhip_process_blocks_pcm.argtypes = [C.c_void_p, _fpp, C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, _fpp, C.c_size_t, C.c_int64,
                                                    C.POINTER(_PcmSpec), C.POINTER(_PcmChannelStats)]
         lib.elemhip_process_blocks_pcm.restype = C.c_int
+        lib.elemhip_process_blocks_pcm_io.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(_PcmInSpec), C.POINTER(C.c_void_p), C.c_size_t,
+                                                      C.POINTER(_PcmSpec), _fpp, C.c_size_t, C.c_size_t, C.c_int64, C.POINTER(_PcmChannelStats)]
+        lib.elemhip_process_blocks_pcm_io.restype = C.c_int
         lib.elemhip_set_stream.argtypes = [C.c_void_p, C.c_void_p]
         lib.elemhip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
         lib.elemhip_get_stats.argtypes = [C.c_void_p, C.c_void_p]
@@ -68,6 +71,10 @@ def load_library() -> C.CDLL:
 
 class _PcmSpec(C.Structure):
     _fields_ = [("format", C.c_uint32), ("channels_per_stream", C.c_uint32), ("dither", C.c_uint32), ("seed", C.c_uint32)]
+
+
+class _PcmInSpec(C.Structure):
+    _fields_ = [("format", C.c_uint32), ("channels_per_stream", C.c_uint32)]
 
 
 class _PcmChannelStats(C.Structure):
@@ -205,6 +212,72 @@ class Runtime(CRuntime):
                      "over": np.array([stats[c].over for c in range(S * G)], dtype=np.uint64),
                      "nonfinite": np.array([stats[c].nonfinite for c in range(S * G)], dtype=np.uint64)}
         return streams, out_stats, planar
+
+    def process_blocks_pcm_io(self, in_streams, in_fmt, num_outputs: Optional[int] = None, num_frames: Optional[int] = None, out_fmt=None,
+                              num_streams: Optional[int] = None, channels_per_stream: Optional[int] = None, dither_seed: Optional[int] = None,
+                              want_float: bool = False, sample_time: Optional[int] = None, in_channels_per_stream: Optional[int] = None):
+        """``elemhip_process_blocks_pcm_io``: the offline block loop FED with interleaved PCM, unpacked on the GPU.
+
+        ``in_streams``: a list of arrays in the layout ``process_blocks_pcm`` returns — ``int16 [frames, G]`` for ``in_fmt`` 's16',
+        ``uint8 [frames, G, 3]`` (little-endian) for 's24', ``float32 [frames, G]`` for 'f32'; sample ``(frame, g)`` of stream ``s``
+        is input channel ``s * G + g`` (``G`` is read off the arrays unless ``in_channels_per_stream`` says it). s16 samples are worth
+        ``code * 2**-15``, s24 ``code * 2**-23``, f32 passes as bits. ``out_fmt`` None: returns float32 ``[num_outputs, frames]`` as
+        ``process_blocks_host`` does; else ``(streams, stats, planar)`` as ``process_blocks_pcm`` does for ``num_streams`` streams of
+        ``channels_per_stream`` channels in ``out_fmt``.
+        """
+        import numpy as np
+        from ._cabi import _ptr_array
+        in_code = pcm_format(in_fmt)
+        want = {1: (np.int16, 2), 2: (np.uint8, 3), 3: (np.float32, 2)}.get(in_code)
+        ins = []
+        for a in (in_streams or []):
+            a = np.ascontiguousarray(a)
+            if want is not None and (a.dtype != want[0] or a.ndim != want[1] or (in_code == 2 and a.shape[2] != 3)):
+                raise ValueError(f"a {in_fmt} input stream is {np.dtype(want[0]).name} [frames, G{', 3' if in_code == 2 else ''}], got {a.dtype} {a.shape}")
+            if a.dtype.byteorder == ">":
+                a = a.byteswap().newbyteorder()
+            ins.append(a)
+        if ins and (any(a.shape[0] != ins[0].shape[0] for a in ins) or any(a.ndim > 1 and a.shape[1] != ins[0].shape[1] for a in ins)):
+            raise ValueError("the input streams differ in frames or in channels per stream")
+        in_g = int(in_channels_per_stream) if in_channels_per_stream is not None else (int(ins[0].shape[1]) if ins and ins[0].ndim > 1 else 1)
+        if num_frames is None:
+            if not ins:
+                raise ValueError("num_frames is needed without inputs")
+            num_frames = ins[0].shape[0]
+        n = int(num_frames)
+        if ins and want is not None and in_channels_per_stream is None and ins[0].shape[0] < n:
+            raise ValueError(f"the input streams hold {ins[0].shape[0]} frames, {n} are asked for")
+        ip = (C.c_void_p * max(1, len(ins)))(*[C.c_void_p(a.ctypes.data) for a in ins])
+        in_spec = _PcmInSpec(in_code, in_g)
+        st = self.sample_time if sample_time is None else int(sample_time)
+        if out_fmt is None:
+            if num_outputs is None:
+                raise ValueError("num_outputs is needed for planar float output")
+            out = np.empty((int(num_outputs), n), dtype=np.float32)
+            rc = self._lib.elemhip_process_blocks_pcm_io(self._h, ip, len(ins), C.byref(in_spec), None, 0, None,
+                                                         _ptr_array([out[i] for i in range(int(num_outputs))]), int(num_outputs), n, st, None)
+            result = out
+        else:
+            S, G, code = int(num_streams), int(channels_per_stream), pcm_format(out_fmt)
+            shape, dtype = {1: ((n, G), np.int16), 2: ((n, G, 3), np.uint8)}.get(code, ((n, G), np.float32))
+            streams = [np.zeros(shape, dtype=dtype) for _ in range(S)]
+            planar = np.zeros((S * G, n), dtype=np.float32) if want_float else None
+            stats = (_PcmChannelStats * max(1, S * G))()
+            spec = _PcmSpec(code, G, 0 if dither_seed is None else 1, 0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFF)
+            sp = (C.c_void_p * max(1, S))(*[C.c_void_p(a.ctypes.data) for a in streams])
+            rc = self._lib.elemhip_process_blocks_pcm_io(self._h, ip, len(ins), C.byref(in_spec), sp, S, C.byref(spec),
+                                                         _ptr_array([planar[i] for i in range(S * G)]) if want_float else None, S * G if want_float else 0,
+                                                         n, st, stats)
+            result = (streams, {"peak": np.array([stats[c].peak for c in range(S * G)], dtype=np.float32),
+                                "over": np.array([stats[c].over for c in range(S * G)], dtype=np.uint64),
+                                "nonfinite": np.array([stats[c].nonfinite for c in range(S * G)], dtype=np.uint64)}, planar)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_process_blocks_pcm_io failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        if sample_time is None:
+            self.sample_time += ((n + self.block_size - 1) // self.block_size) * self.block_size
+        return result
 
     def event_window_blocks(self) -> int:
         """Blocks a ``process_queued_events(blockwise=True)`` window may span and still equal a relay after every block."""

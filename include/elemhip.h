@@ -124,6 +124,28 @@ int elemhip_process_blocks_pcm(elemhip_t*, const float* const* in, size_t nIn,
                                float* const* planar,                    /* NULL, or nStreams*channels_per_stream planar float arrays: the very samples that were packed */
                                size_t numFrames, int64_t sampleTime, const elemhip_pcm_spec*, elemhip_pcm_channel_stats* stats /* NULL or one per channel */);
 
+/* EXTENSION (no counterpart in the reference): the same render FED with interleaved PCM, unpacked on the GPU in front of the first
+ * render level of every launch set (elementary_amd/csrc/pcm_unpack.hip; the arithmetic: pcm_unpack.h). The nInStreams *
+ * channels_per_stream input channels arrive as nInStreams streams of numFrames * channels_per_stream samples; sample (frame, g) of
+ * stream s is input channel s * channels_per_stream + g. The layout is that of the output streams above.
+ *   format  1: little-endian int16, value * 2^-15   2: 3 bytes per sample, little-endian two's complement, packed, value * 2^-23
+ *           3: float32, bits unchanged (NaN payloads and infinities included). Both integer conversions are exact in float32, and
+ *           packing the result without dither gives the codes back.
+ *   a short tail (numFrames no multiple of the block size) is zero-padded, as for planar input
+ *   outSpec NULL: the output as planar floats only — `planar` = nPlanar arrays of numFrames frames, as elemhip_process_blocks_host
+ *           fills them; outStreams / nOutStreams / stats are ignored
+ *   outSpec set:  the delivery of elemhip_process_blocks_pcm — outStreams, nOutStreams, stats as there, `planar` NULL or nOutStreams *
+ *           outSpec->channels_per_stream arrays that receive the very samples that were packed (nPlanar is ignored)
+ * The floats a graph sees, and so every output sample, are bit for bit those of the planar entry points given the decoded input.
+ * Codes: 8 for an unknown input (or output) format, channels_per_stream == 0, NULL streams / spec with nInStreams > 0; 103 when
+ * nInStreams * channels_per_stream exceeds 32 host inputs or the output side exceeds the output bus (1024); 101 on a dry handle. A
+ * failing call renders nothing. */
+typedef struct elemhip_pcm_in_spec { uint32_t format, channels_per_stream; } elemhip_pcm_in_spec;
+int elemhip_process_blocks_pcm_io(elemhip_t*, const void* const* inStreams, size_t nInStreams, const elemhip_pcm_in_spec* inSpec,
+                                  void* const* outStreams, size_t nOutStreams, const elemhip_pcm_spec* outSpec, /* NULL: planar floats only */
+                                  float* const* planar, size_t nPlanar,    /* with outSpec NULL: the nPlanar output channels */
+                                  size_t numFrames, int64_t sampleTime, elemhip_pcm_channel_stats* stats);
+
 /* bool addSharedResource(name, unique_ptr<SharedResource>)       Runtime.h:83,461-465 (insert-only) */
 int    elemhip_add_shared_resource(elemhip_t*, const char* name, const float* const* channels, size_t nCh, size_t nSamples);
 /* void pruneSharedResources()                                    Runtime.h:89,467-471 */

@@ -126,6 +126,19 @@ public:
         return rc;
     }
 
+    // EXTENSION: the block loop fed with interleaved PCM, unpacked on the GPU (elemhip_process_blocks_pcm_io): nInStreams streams of
+    // numFrames * inSpec.channels_per_stream samples. `outSpec` null: `planar` = nPlanar planar float arrays (processBlocksHost's
+    // output); else processBlocksPcm's delivery into `outStreams`, `planar` null or the floats that were packed.
+    int processBlocksPcmIo(const void* const* inStreams, size_t nInStreams, elemhip_pcm_in_spec const& inSpec, void* const* outStreams,
+                           size_t nOutStreams, const elemhip_pcm_spec* outSpec, float** planar, size_t nPlanar, size_t numFrames,
+                           elemhip_pcm_channel_stats* stats = nullptr, void* userData = nullptr) {
+        const int64_t t = userData ? *static_cast<int64_t*>(userData) : implicitTime;
+        const int rc = elemhip_process_blocks_pcm_io(h, inStreams, nInStreams, &inSpec, outStreams, nOutStreams, outSpec, planar, nPlanar,
+                                                     numFrames, t, stats);
+        if (!userData) implicitTime += (int64_t)numFrames;
+        return rc;
+    }
+
     // bool addSharedResource(name, unique_ptr<SharedResource>)         Runtime.h:83 — planar float channels
     bool addSharedResource(std::string const& name, const float* const* channels, size_t nCh, size_t nSamples) {
         return elemhip_add_shared_resource(h, name.c_str(), channels, nCh, nSamples) != 0;
