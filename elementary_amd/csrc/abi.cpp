@@ -142,6 +142,24 @@ int elemhip_process_blocks_pcm_io(elemhip_t* h, const void* const* inStreams, si
                                         reinterpret_cast<Engine::PcmChannelStats*>(stats));
 }
 
+int elemhip_loudness_read(elemhip_t* h, elemhip_loudness_info* info, double* meanSquares, size_t capacity, double* truePeak, float* samplePeak) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    Engine::LoudnessInfo li{};
+    const int rc = h->engine.loudnessRead(&li, meanSquares, capacity, truePeak, samplePeak);
+    if (info) { info->channels = li.channels; info->hop = li.hop; info->sub_blocks = li.subBlocks; info->frames = li.frames; }
+    return rc;
+}
+
+int elemhip_loudness_reset(elemhip_t* h) { return h ? h->engine.loudnessReset() : elemhip::kInvalidInstructionFormat; }
+
+int elemhip_loudness_gate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
+    if (!out || (channels && subBlocks && !meanSquares)) return elemhip::kInvalidInstructionFormat;
+    const loudness::Gated g = loudness::gate(meanSquares, channels, subBlocks, weights);
+    out->integrated = g.integrated; out->momentary_max = g.momentaryMax; out->short_term_max = g.shortTermMax;
+    out->blocks = g.blocks; out->gated_blocks = g.gatedBlocks;
+    return elemhip::kOk;
+}
+
 int elemhip_add_shared_resource(elemhip_t* h, const char* name, const float* const* ch, size_t nCh, size_t nSamples) {
     if (!h || !name) return 0;
     return h->engine.addSharedResource(name, ch, nCh, nSamples) ? 1 : 0;

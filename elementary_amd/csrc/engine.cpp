@@ -187,6 +187,7 @@ Engine::~Engine() {
     if (dPcmRowBase) (void)hipFree(dPcmRowBase);
     for (int k = 0; k < 2; ++k) { if (hPcmIn[k]) (void)hipHostFree(hPcmIn[k]); if (dPcmIn[k]) (void)hipFree(dPcmIn[k]); }
     if (dPcmInRowBase) (void)hipFree(dPcmInRowBase);
+    loudnessFree();
     if (ioStream) (void)hipStreamDestroy(ioStream);
     if (relayStream) { (void)hipStreamSynchronize(relayStream); (void)hipStreamDestroy(relayStream); }
     if (evRelay) (void)hipEventDestroy(evRelay);
@@ -513,6 +514,14 @@ int Engine::setOption(const std::string& key, double value) {
     // the same for capture / mc.capture nodes made FROM NOW ON: a ring that keeps that many blocks of takes and a per-block log of what a
     // relay after every block would have seen (capture_replay.h). 0: the reference's bitceil(sr) frames and a relay window of one block.
     if (key == "capture_history_blocks") { captureHistoryBlocks = (uint32_t)std::max(0, std::min((int)kEventLogEntries, (int)value)); return kOk; }
+    // loudness.h: BS.1770 sub-block mean squares and true peak of every launch set of the host-buffer render calls, on the GPU. Turning
+    // it on resets the meter; off (the default) not one launch or byte differs.
+    if (key == "loudness_meter") {
+        const bool on = value != 0.0;
+        if (on && !dry) { loudness::make_plan(sampleRate, loudPlan); const int rc = loudnessResetLocked(0); if (rc != kOk) return rc; }
+        loudnessOn = on;
+        return kOk;
+    }
     if (key == "batch_blocks") { batchBlocks = std::max(1, std::min(1024, (int)value)); return kOk; }      // blocks per multi-block launch (1 = off)
     if (key == "debug_build_delay_ms") { debugBuildDelayMs = std::max(0, (int)value); return kOk; }   // tests: stretches the unlocked part of a plan build
     if (key == "plan_cache") { planCache = std::max(0, std::min(2, (int)value)); islandCache.clear(); islandShapeCache.clear(); return kOk; }

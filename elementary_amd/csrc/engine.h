@@ -26,6 +26,7 @@
 #include "device.h"
 #include "json.h"
 #include "jit.h"
+#include "loudness.h"
 
 namespace elemhip {
 
@@ -230,6 +231,16 @@ public:
     struct PcmSource { uint32_t format, channelsPerStream; const void* const* streams; size_t nStreams; };
     int processBlocksPcmIo(const PcmSource& src, void* const* outStreams, size_t nOutStreams, const PcmSpec* outSpec, float* const* planar,
                            size_t nPlanar, size_t numFrames, int64_t sampleTime, PcmChannelStats* stats);
+    // Option "loudness_meter" (loudness.h): every launch set of processBlocksHost / processBlocksPcm / processBlocksPcmIo is metered
+    // where its output lies in HBM (loudness.hip), float or PCM delivery alike; where those calls render host block by host block the
+    // header's scalar loop meters the floats on the host. process() and the device-resident processBlocks() are NOT metered. The
+    // programme is the frames those calls delivered, in call order, since the last reset; its channel count is that of the first
+    // metered call (a call with another count starts a new programme).
+    struct LoudnessInfo { uint32_t channels, hop; uint64_t subBlocks, frames; };
+    // meanSquares: [channel][subBlocks] (capacity in doubles; too small: the info is filled and kInvalidPropertyValue returned);
+    // truePeak (zero-padded tail included, the carried state is not disturbed) / samplePeak: one per channel; any pointer may be null
+    int loudnessRead(LoudnessInfo* info, double* meanSquares, size_t capacity, double* truePeak, float* samplePeak);
+    int loudnessReset();
     // render `numBlocks` blocks with a HIP event pair around every kernel launch; msOut[l] = mean
     // duration of launch level l (l < numLevels), msOut[numLevels] = epilogue. Returns levels + 1.
     int timeLaunches(size_t nOut, size_t numBlocks, float* msOut, size_t cap);
@@ -381,6 +392,20 @@ private:
     size_t pcmInBytes = 0;
     uint16_t* dPcmInRowBase = nullptr; uint32_t pcmInTableGroup = 0, pcmInRowDwords = 0;
     int ensurePcmInStaging(size_t bytes, uint32_t group);
+    // loudness meter (option "loudness_meter"): carried state per channel on the device, the segment scratch of a set, and per half the
+    // sums of the sub-blocks the set completed (they leave with the set's D2H)
+    bool loudnessOn = false;
+    loudness::Plan loudPlan{};
+    uint32_t loudChannels = 0;             // channels of the programme (0: none yet)
+    uint64_t loudFrames = 0;               // programme frames metered so far
+    std::vector<std::vector<double>> loudSeries;      // [channel]: mean squares of the completed sub-blocks
+    loudness::ChannelState* dLoudState = nullptr; size_t loudStateCap = 0;
+    double* dLoudSeg = nullptr; double* dLoudEnergy = nullptr; size_t loudSegCap = 0, loudSegChannels = 0;
+    double* dLoudOut[2] = {nullptr, nullptr}; double* hLoudOut[2] = {nullptr, nullptr}; size_t loudOutStride = 0, loudOutChannels = 0;
+    uint32_t loudCountOf[2] = {0, 0};      // sub-blocks the set in each half completed
+    int ensureLoudness(size_t channels, size_t setFrames);      // (`mu` held, both streams idle)
+    int loudnessResetLocked(size_t channels);
+    void loudnessFree();
     int growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], size_t& have, size_t want);
     int ensureRowTable(uint16_t*& dev, uint32_t& haveGroup, uint32_t& dwords, uint32_t group);
     // the set loop of processBlocksHost / processBlocksPcm (`pcm` null: planar floats only)

@@ -1261,6 +1261,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
     const bool wantFloat = nOut > 0 && out != nullptr;
     const uint32_t pcmG = pcm ? pcm->spec.channelsPerStream : 1u, pcmFmt = pcm ? pcm->spec.format : 0u;
     const size_t pcmB = pcm ? pcm_pack::sample_bytes(pcmFmt) : 0;
+    const bool meter = loudnessOn && nOut > 0;       // option "loudness_meter": the delivered frames of every set go through the meter
     // whole HOST blocks, like the reference's block loop (a host block = hostBlockSize / blockSize engine blocks)
     const size_t hb = (size_t)hostBlockSize;
     bool tapSlices = hb % bs != 0;          // ragged slices (a host block that no k divides evenly): launch sets hold whole engine blocks
@@ -1273,11 +1274,23 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         std::vector<float> tailIn, tailOut;
         std::vector<uint8_t*> sp(pcm ? pcm->nStreams : 0);
         std::vector<const unsigned char*> srcAt(src ? src->nStreams : 0);
+        // the meter's carried state comes to the host for the call: the floats are here, the header's scalar loop meters them
+        std::vector<loudness::ChannelState> meterState(meter ? nOut : 0);
+        auto meterSync = [&](bool toHost) -> int {
+            RenderGuard lock(*this);
+            if (hipSetDevice(device) != hipSuccess) return kHipError;
+            if (toHost) { const int rc = ensureLoudness(nOut, 0); if (rc != kOk) return rc; }
+            HIP_OK(hipStreamSynchronize(stream));
+            if (toHost) HIP_OK(hipMemcpy(meterState.data(), dLoudState, nOut * sizeof(loudness::ChannelState), hipMemcpyDeviceToHost));
+            else HIP_OK(hipMemcpy(dLoudState, meterState.data(), nOut * sizeof(loudness::ChannelState), hipMemcpyHostToDevice));
+            return kOk;
+        };
+        if (meter) { const int rc = meterSync(true); if (rc != kOk) return rc; }
         for (size_t f0 = 0; f0 < numFrames; f0 += hb) {
             const size_t nf = std::min(hb, numFrames - f0);
             for (size_t c = 0; c < nIn; ++c) ip[c] = src ? nullptr : in[c] + f0;
             for (size_t c = 0; c < nOut; ++c) op[c] = wantFloat ? out[c] + f0 : nullptr;
-            if (nf < hb || pcm) {
+            if (nf < hb || pcm || meter) {
                 // the last, partly filled host block is still a whole block to the engine (offline-renderer/index.ts:104-131: inputs
                 // padded with zeros, the frames beyond the caller's arrays dropped); a PCM call renders every host block here
                 tailOut.assign(nOut * hb, 0.0f);
@@ -1294,8 +1307,14 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 for (size_t c = 0; c < nIn; ++c) { std::memcpy(tailIn.data() + c * hb, in[c] + f0, nf * sizeof(float)); ip[c] = tailIn.data() + c * hb; }
             }
             const int rc = process(ip.data(), nIn, op.data(), nOut, hb, sampleTime + (int64_t)f0);
-            if (rc != kOk) return rc;
-            if ((nf < hb || pcm) && wantFloat) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + f0, tailOut.data() + c * hb, nf * sizeof(float));
+            if (rc != kOk) { if (meter) (void)meterSync(false); return rc; }
+            if (meter) {
+                std::lock_guard<std::mutex> lock(mu);
+                for (size_t c = 0; c < nOut; ++c)
+                    loudness::meter_host(loudPlan, meterState[c], tailOut.data() + c * hb, nf, loudFrames, [&](double ms) { loudSeries[c].push_back(ms); });
+                loudFrames += nf;
+            }
+            if ((nf < hb || pcm || meter) && wantFloat) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + f0, tailOut.data() + c * hb, nf * sizeof(float));
             if (pcm) {
                 // the floats are on the host: the header's scalar loop packs them — the kernel's functions, the kernel's bits
                 for (size_t s = 0; s < pcm->nStreams; ++s) sp[s] = static_cast<uint8_t*>(pcm->streams[s]) + f0 * pcmG * pcmB;
@@ -1303,7 +1322,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                                     sampleTime + (int64_t)f0, sp.data(), pcm->peakBits.data(), pcm->over.data(), pcm->nonfinite.data());
             }
         }
-        return kOk;
+        return meter ? meterSync(false) : kOk;
     }
     const size_t numBlocks = ((numFrames + hb - 1) / hb) * (hb / bs);
     if (numBlocks == 0) return kOk;
@@ -1325,6 +1344,10 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         }
         if (pcm) {
             rc = ensurePcmStaging(pcm->nStreams * (size_t)pcm_pack::stream_stride(setBlocks * bs, pcmG, pcmFmt) + nOut * sizeof(pcm_pack::ChannelStats), pcmG);
+            if (rc != kOk) return rc;
+        }
+        if (meter) {
+            rc = ensureLoudness(nOut, setBlocks * bs);
             if (rc != kOk) return rc;
         }
     }
@@ -1367,7 +1390,13 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             pcm->over[c] += st[c].over; pcm->nonfinite[c] += st[c].nonfinite;
         }
     };
-    auto deliver = [&](size_t k) { if (wantFloat) scatter(k); if (pcm) deliverPcm(k); };
+    auto deliverLoudness = [&](size_t k) {   // the sums of the sub-blocks set k completed -> the programme's series
+        const double* sums = hLoudOut[k & 1];
+        std::lock_guard<std::mutex> lock(mu);
+        for (size_t c = 0; c < nOut; ++c)
+            for (uint32_t j = 0; j < loudCountOf[k & 1]; ++j) loudSeries[c].push_back(sums[c * loudOutStride + j] / (double)loudPlan.hop);
+    };
+    auto deliver = [&](size_t k) { if (wantFloat) scatter(k); if (pcm) deliverPcm(k); if (meter) deliverLoudness(k); };
     int result = kOk;
     size_t issued = 0, scattered = 0;
     // a failing HIP call ends the loop; the tail below drains both streams, releases what was deferred and reports the code —
@@ -1450,10 +1479,25 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 HOST_TRY(launch_pcm_pack(stream, a, pcmFmt));
                 pcmCopy = statsOff + nOut * sizeof(pcm_pack::ChannelStats);
             }
+            if (meter) {
+                // the meter's kernels behind the set's last level too, next to the pack kernel: they read the same block. The state they
+                // carry lives on the device; the sums of the sub-blocks this set completes go to this half's small region, drained like
+                // the packed half by the D2H of set k - 2.
+                const size_t valid = std::min(nb * bs, numFrames - b0 * bs);
+                LoudnessArgs a{};
+                a.src = dStageOut[half]; a.state = dLoudState; a.segState = dLoudSeg; a.segEnergy = dLoudEnergy; a.out = dLoudOut[half];
+                a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nOut; a.validFrames = (uint32_t)valid;
+                a.numSegs = loudness::segment_count((uint32_t)valid, loudPlan.L); a.segCap = (uint32_t)loudSegCap; a.outStride = (uint32_t)loudOutStride;
+                a.q0 = (uint32_t)(loudFrames % loudPlan.hop); a.plan = loudPlan;
+                loudCountOf[half] = loudness::subblocks_complete(a.q0, a.validFrames, loudPlan.hop);
+                HOST_TRY(launch_loudness(stream, a));
+                loudFrames += valid;
+            }
             HOST_TRY(hipEventRecord(evRendered[half], stream));
             HOST_TRY(hipStreamWaitEvent(ioStream, evRendered[half], 0));
             if (wantFloat || !pcm) { if (nOut) HOST_TRY(hipMemcpyAsync(hStageOut[half], dStageOut[half], nb * nOut * bs * sizeof(float), hipMemcpyDeviceToHost, ioStream)); }
             if (pcm) HOST_TRY(hipMemcpyAsync(hPcm[half], dPcm[half], pcmCopy, hipMemcpyDeviceToHost, ioStream));
+            if (meter && loudCountOf[half]) HOST_TRY(hipMemcpyAsync(hLoudOut[half], dLoudOut[half], nOut * loudOutStride * sizeof(double), hipMemcpyDeviceToHost, ioStream));
             HOST_TRY(hipEventRecord(evOut[half], ioStream));
             issued = k + 1;
         }
@@ -1476,6 +1520,8 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         if (hipGetLastError() != hipSuccess && result == kOk) result = kHipError;
         if (profUsed) profCollect();
         freeDeferred();
+        // a metered call that failed may have advanced the carried state past sets whose sums never arrived: the programme starts anew
+        if (meter && result != kOk) (void)loudnessResetLocked(loudChannels);
     }
     return result;
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 #include "device.h"
 #include "pcm_pack.h"
+#include "loudness.h"
 
 namespace elemhip {
 
@@ -89,6 +90,18 @@ struct PcmUnpackArgs {
     uint32_t        blockSize, numChannels, G, numStreams, validFrames, numBlocks, tilesPerBlock, rowDwords;   // frames behind validFrames: zero
 };
 hipError_t launch_pcm_unpack(hipStream_t s, const PcmUnpackArgs& a, uint32_t format);
+// ---- loudness meter (loudness.hip): behind a launch set's last level, loudness.h ----
+struct LoudnessArgs {
+    const float*    src;            // the set's output, [block][numChannels][blockSize]
+    loudness::ChannelState* state;  // [numChannels], carried from set to set
+    double*         segState;       // [numChannels][segCap][4]: pass one's end states, then the scan's start states
+    double*         segEnergy;      // [numChannels][segCap][2]: pass two's sums
+    double*         out;            // [numChannels][outStride]: the sums of the sub-blocks this set completed
+    uint32_t        blockSize, numChannels, validFrames, numSegs, segCap, outStride;
+    uint32_t        q0;             // the programme's frame count at the set's start, mod hop
+    loudness::Plan  plan;
+};
+hipError_t launch_loudness(hipStream_t s, const LoudnessArgs& a);
 hipError_t launch_bus_sum(hipStream_t s, float* dst, const float* const* partials, uint32_t count, size_t n);   // dst = ((p0 + p1) + p2) + ... (rank order)
 
 } // namespace elemhip

@@ -21,12 +21,15 @@ class OfflineRenderer:
 
     def initialize(self, num_input_channels: int = 0, num_output_channels: int = 2, sample_rate: float = 44100,
                    block_size: int = 512, virtual_file_system: Optional[Dict[str, np.ndarray]] = None,
-                   event_history_blocks: int = 0, capture_history_blocks: int = 0) -> None:
+                   event_history_blocks: int = 0, capture_history_blocks: int = 0, loudness_meter: bool = False) -> None:
         """``event_history_blocks`` (no counterpart in the reference; 0 = off): engine option of the same name — `scope` and `fft`
         nodes keep a device ring long enough for a relay window of that many blocks, so ``process`` still renders launch sets of
         that size with such a listener attached (engines without ``set_option`` relay after every block anyway).
         ``capture_history_blocks`` (likewise): the same for `capture` and `mc.capture` nodes — a device ring that keeps that many
-        blocks of takes and a per-block log from which the blockwise relay places every take at the block where the gate fell."""
+        blocks of takes and a per-block log from which the blockwise relay places every take at the block where the gate fell.
+        ``loudness_meter`` (likewise; off by default): engine option of the same name — every launch set that ``process`` (in engine
+        calls of many blocks), ``process_pcm``, ``process_pcm_io``, ``write_wav`` and ``process_wav`` render is metered on the GPU:
+        BS.1770 sub-block energies and true peak, read with ``loudness()``."""
         self.num_in = int(num_input_channels)
         self.num_out = int(num_output_channels)
         self.block_size = int(block_size)
@@ -36,6 +39,9 @@ class OfflineRenderer:
             self._rt.set_option("event_history_blocks", int(event_history_blocks))
         if capture_history_blocks and hasattr(self._rt, "set_option"):
             self._rt.set_option("capture_history_blocks", int(capture_history_blocks))
+        self._loudness = bool(loudness_meter)
+        if self._loudness:
+            self._rt.set_option("loudness_meter", 1)
         self._time = 0
         for k, v in (virtual_file_system or {}).items():
             self._rt.add_shared_resource(k, v)
@@ -168,11 +174,45 @@ class OfflineRenderer:
         planar = np.concatenate([p[2] for p in parts], axis=1) if want_float else None
         return streams, stats, planar
 
+    def loudness(self, weights=None, programmes=None):
+        """What the loudness meter (``initialize(loudness_meter=True)``) has measured since the renderer was made or
+        ``loudness_reset()``: ``{'integrated_lufs', 'momentary_max_lufs', 'short_term_max_lufs',
+        'true_peak_dbtp', 'frames', 'sub_blocks'}`` (EBU R 128 gating; ``-inf`` where nothing passes the gates; the true peak is the
+        largest of the programme's channels). ``weights``: one per output channel (default 1.0). ``programmes``: a list of lists of
+        channel indices, each metered as a programme of its own (a list of results comes back); default one programme of all channels."""
+        from . import loudness as ld
+        if not self._loudness:
+            raise RuntimeError("the loudness meter is off: initialize(loudness_meter=True)")
+        got = self._rt.loudness_read()
+        w = np.ones(got["channels"], dtype=np.float64) if weights is None else np.asarray(weights, dtype=np.float64)
+
+        def one(chs):
+            chs = [int(c) for c in chs]
+            g = ld.gate(got["mean_squares"][chs], w[chs])
+            return {"integrated_lufs": g["integrated"], "momentary_max_lufs": g["momentary_max"], "short_term_max_lufs": g["short_term_max"],
+                    "true_peak_dbtp": ld.dbtp(max([float(got["true_peak"][c]) for c in chs], default=0.0)),
+                    "frames": got["frames"], "sub_blocks": got["sub_blocks"]}
+        if programmes is None:
+            return one(range(got["channels"]))
+        return [one(chs) for chs in programmes]
+
+    def loudness_reset(self) -> None:
+        """A new programme for the loudness meter: time 0, zero filter state, no peaks."""
+        self._rt.loudness_reset()
+
+    def _with_loudness(self, stats):
+        if self._loudness and stats is not None:
+            got = self.loudness()
+            stats = dict(stats, integrated_lufs=got["integrated_lufs"], true_peak_dbtp=got["true_peak_dbtp"])
+        return stats
+
     def write_wav(self, path, inputs: Sequence[np.ndarray], num_frames: int, fmt="s16", channels_per_stream: Optional[int] = None,
                   dither_seed: Optional[int] = None, chunk_frames: int = 1 << 20):
         """Render ``num_frames`` frames into RIFF/WAVE files, ``chunk_frames`` (rounded to whole blocks) per engine call: one file per
         stream of ``channels_per_stream`` channels (default: all output channels in one file). ``path``: the file's name, or — for
-        more than one stream — a list of names or a name with ``{}`` for the stream number. Returns the statistics of the render."""
+        more than one stream — a list of names or a name with ``{}`` for the stream number. Returns the statistics of the render; with the loudness
+        meter on they carry ``integrated_lufs`` and ``true_peak_dbtp`` as well — ``loudness()`` of the meter's programme so far (call
+        ``loudness_reset()`` first for figures of this file alone)."""
         from .wav import WavWriter
         G = self.num_out if channels_per_stream is None else int(channels_per_stream)
         S = self.num_out // max(G, 1)
@@ -203,7 +243,7 @@ class OfflineRenderer:
         finally:
             for wtr in writers:
                 wtr.close()
-        return stats
+        return self._with_loudness(stats)
 
     def process_pcm_io(self, in_streams: Sequence[np.ndarray], in_fmt, num_frames: Optional[int] = None, out_fmt=None,
                        num_streams: Optional[int] = None, channels_per_stream: Optional[int] = None, dither_seed: Optional[int] = None,
@@ -259,7 +299,8 @@ class OfflineRenderer:
         cross the host as they lie in the files and are converted on the GPU in both directions. ``in_paths``: one name or a list —
         the files' channels become the input channels in file order (files of one format, one channel count and the renderer's
         sample rate). ``out_paths`` / ``channels_per_stream``: as ``write_wav``'s ``path``. ``num_frames``: frames to render, default
-        the (longest) input's length; longer than that — a reverb's tail — renders the rest from silence. Returns the statistics."""
+        the (longest) input's length; longer than that — a reverb's tail — renders the rest from silence. Returns the statistics
+        (with the loudness meter on: ``integrated_lufs`` and ``true_peak_dbtp`` of the meter's programme so far included, as ``write_wav``)."""
         from .wav import WavReader, WavWriter
         ins = [str(in_paths)] if isinstance(in_paths, (str, bytes)) or hasattr(in_paths, "__fspath__") else [str(p) for p in in_paths]
         G = self.num_out if channels_per_stream is None else int(channels_per_stream)
@@ -303,7 +344,7 @@ class OfflineRenderer:
         finally:
             for x in readers + writers:
                 x.close()
-        return stats
+        return self._with_loudness(stats)
 
     def update_virtual_file_system(self, vfs: Dict[str, np.ndarray]) -> None:
         for k, v in vfs.items():

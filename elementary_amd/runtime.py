@@ -65,6 +65,13 @@ def load_library() -> C.CDLL:
         lib.elemhip_describe_plan.restype = C.c_size_t
         lib.elemhip_sum_buses.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t]
         lib.elemhip_sum_buses.restype = C.c_int
+        _dp = C.POINTER(C.c_double)
+        lib.elemhip_loudness_read.argtypes = [C.c_void_p, C.POINTER(_LoudnessInfo), _dp, C.c_size_t, _dp, C.POINTER(C.c_float)]
+        lib.elemhip_loudness_read.restype = C.c_int
+        lib.elemhip_loudness_reset.argtypes = [C.c_void_p]
+        lib.elemhip_loudness_reset.restype = C.c_int
+        lib.elemhip_loudness_gate.argtypes = [_dp, C.c_size_t, C.c_size_t, _dp, C.POINTER(_LoudnessResult)]
+        lib.elemhip_loudness_gate.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -79,6 +86,15 @@ class _PcmInSpec(C.Structure):
 
 class _PcmChannelStats(C.Structure):
     _fields_ = [("peak", C.c_float), ("reserved", C.c_uint32), ("over", C.c_uint64), ("nonfinite", C.c_uint64)]
+
+
+class _LoudnessInfo(C.Structure):
+    _fields_ = [("channels", C.c_uint32), ("hop", C.c_uint32), ("sub_blocks", C.c_uint64), ("frames", C.c_uint64)]
+
+
+class _LoudnessResult(C.Structure):
+    _fields_ = [("integrated", C.c_double), ("momentary_max", C.c_double), ("short_term_max", C.c_double),
+                ("blocks", C.c_uint64), ("gated_blocks", C.c_uint64)]
 
 
 PCM_FORMATS = {"s16": 1, "s24": 2, "f32": 3}
@@ -278,6 +294,40 @@ class Runtime(CRuntime):
         if sample_time is None:
             self.sample_time += ((n + self.block_size - 1) // self.block_size) * self.block_size
         return result
+
+    def loudness_read(self) -> Dict[str, Any]:
+        """``elemhip_loudness_read`` (option ``loudness_meter``): the programme metered so far — ``{'channels', 'sub_blocks', 'hop',
+        'frames', 'mean_squares': float64 [channels, sub_blocks], 'true_peak': float64 [channels] (linear, the zero-padded tail
+        included), 'sample_peak': float32 [channels]}``. A read does not disturb a programme that continues."""
+        import numpy as np
+        info = _LoudnessInfo()
+        rc = self._lib.elemhip_loudness_read(self._h, C.byref(info), None, 0, None, None)
+        ch = n = 0
+        for _ in range(8):
+            if rc != 0:
+                break
+            ch, n = int(info.channels), int(info.sub_blocks)
+            ms = np.zeros((ch, n), dtype=np.float64)
+            tp, sp = np.zeros(max(1, ch), dtype=np.float64), np.zeros(max(1, ch), dtype=np.float32)
+            rc = self._lib.elemhip_loudness_read(self._h, C.byref(info), ms.ctypes.data_as(C.POINTER(C.c_double)), ms.size,
+                                                 tp.ctypes.data_as(C.POINTER(C.c_double)), sp.ctypes.data_as(C.POINTER(C.c_float)))
+            if rc != 6 or (int(info.channels), int(info.sub_blocks)) == (ch, n):
+                break
+            rc = 0          # (another thread rendered in between: the info is filled, size the buffers again)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_loudness_read failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return {"channels": ch, "sub_blocks": n, "hop": int(info.hop), "frames": int(info.frames), "mean_squares": ms,
+                "true_peak": tp[:ch], "sample_peak": sp[:ch]}
+
+    def loudness_reset(self) -> None:
+        """``elemhip_loudness_reset``: a new programme (time 0, zero filter state, no peaks)."""
+        rc = self._lib.elemhip_loudness_reset(self._h)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_loudness_reset failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
 
     def event_window_blocks(self) -> int:
         """Blocks a ``process_queued_events(blockwise=True)`` window may span and still equal a relay after every block."""

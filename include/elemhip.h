@@ -146,6 +146,31 @@ int elemhip_process_blocks_pcm_io(elemhip_t*, const void* const* inStreams, size
                                   float* const* planar, size_t nPlanar,    /* with outSpec NULL: the nPlanar output channels */
                                   size_t numFrames, int64_t sampleTime, elemhip_pcm_channel_stats* stats);
 
+/* EXTENSION (no counterpart in the reference): ITU-R BS.1770-4 / EBU R 128 metering of offline renders on the GPU
+ * (elementary_amd/csrc/loudness.hip; the arithmetic: loudness.h). After elemhip_set_option(h, "loudness_meter", 1) every launch set of
+ * elemhip_process_blocks_host, elemhip_process_blocks_pcm and elemhip_process_blocks_pcm_io is metered behind its last render level,
+ * float or PCM delivery alike: per output channel the K-weighted mean square of every 100 ms sub-block (hop = round(sampleRate / 10)
+ * frames) and the 4x-oversampled true peak. elemhip_process and the device-resident elemhip_process_blocks are NOT metered.
+ * The programme is the frames those calls DELIVERED (numFrames each, not the zero padding of a last block), in call order, since the
+ * option was turned on or elemhip_loudness_reset; its channel count is that of the first metered call (a call with another count
+ * starts a new programme, and so does a metered call that fails). The state is carried on the device from set to set and call to call; a non-finite sample meters as 0.
+ *   elemhip_loudness_read   info: channels, completed sub-blocks, hop, programme frames. meanSquares (NULL, or `capacity` doubles):
+ *                           the series [channel][sub_blocks]; code 6 when capacity < channels * sub_blocks (info is filled: call
+ *                           again). truePeak (NULL or one per channel): max |y| over the whole oversampled programme INCLUDING its
+ *                           zero-padded tail, linear; the tail is evaluated on the host from a copy of the carried state, so a
+ *                           programme may go on after a read. samplePeak (NULL or one per channel): max |x|. Codes: 101 on a dry
+ *                           handle, 6 while the option is off.
+ *   elemhip_loudness_reset  a new programme: time 0, zero filter state, no peaks
+ *   elemhip_loudness_gate   pure host arithmetic, no handle: 400 ms blocks (4 sub-blocks, hop 1), block loudness -0.691 + 10 log10
+ *                           sum_c weights[c] * ms_c (weights NULL: 1.0 each), absolute gate -70 LUFS, relative gate -10 LU under the
+ *                           mean of the absolutely gated blocks. integrated is -inf when no block passes; momentary_max over the
+ *                           400 ms blocks, short_term_max over windows of 30 sub-blocks (-inf when there is none). */
+typedef struct elemhip_loudness_info { uint32_t channels, hop; uint64_t sub_blocks, frames; } elemhip_loudness_info;
+typedef struct elemhip_loudness_result { double integrated, momentary_max, short_term_max; uint64_t blocks, gated_blocks; } elemhip_loudness_result;
+int elemhip_loudness_read(elemhip_t*, elemhip_loudness_info* info, double* meanSquares, size_t capacity, double* truePeak, float* samplePeak);
+int elemhip_loudness_reset(elemhip_t*);
+int elemhip_loudness_gate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out);
+
 /* bool addSharedResource(name, unique_ptr<SharedResource>)       Runtime.h:83,461-465 (insert-only) */
 int    elemhip_add_shared_resource(elemhip_t*, const char* name, const float* const* channels, size_t nCh, size_t nSamples);
 /* void pruneSharedResources()                                    Runtime.h:89,467-471 */
@@ -250,7 +275,8 @@ int  elemhip_sum_buses(int deviceOrdinal, void* hipStream, float* dst, const flo
  * waits for them), "spec_blocks" / "host_out_direct" (elemhip_process through the specialised kernels / output written straight
  * into pinned host memory), "use_graph" / "graph_blocks" (per-block launch path replayed from a hipGraph), "stateless_rows",
  * "mixer_split", "pipeline_copies", "merge_phases", "pack_islands" / "pack_max" / "cu_count" (lane-packing of isomorphic
- * islands), "event_history_blocks" / "capture_history_blocks" (above, at elemhip_event_window_blocks), "profile_launches", "time_batch". Unknown keys return code 6. */
+ * islands), "event_history_blocks" / "capture_history_blocks" (above, at elemhip_event_window_blocks), "loudness_meter" (above, at
+ * elemhip_loudness_read), "profile_launches", "time_batch". Unknown keys return code 6. */
 int  elemhip_set_option(elemhip_t*, const char* key, double value);
 
 #ifdef __cplusplus

@@ -139,6 +139,17 @@ public:
         return rc;
     }
 
+    // EXTENSION: the loudness meter (elemhip_loudness_read / _reset / _gate; setOption("loudness_meter", 1) turns it on): BS.1770
+    // sub-block mean squares [channel][sub_blocks] and true peaks of everything processBlocksHost / processBlocksPcm /
+    // processBlocksPcmIo delivered since the last reset. process() and processBlocks() are not metered.
+    int loudnessRead(elemhip_loudness_info* info, double* meanSquares, size_t capacity, double* truePeak = nullptr, float* samplePeak = nullptr) {
+        return elemhip_loudness_read(h, info, meanSquares, capacity, truePeak, samplePeak);
+    }
+    int loudnessReset() { return elemhip_loudness_reset(h); }
+    static int loudnessGate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
+        return elemhip_loudness_gate(meanSquares, channels, subBlocks, weights, out);
+    }
+
     // bool addSharedResource(name, unique_ptr<SharedResource>)         Runtime.h:83 — planar float channels
     bool addSharedResource(std::string const& name, const float* const* channels, size_t nCh, size_t nSamples) {
         return elemhip_add_shared_resource(h, name.c_str(), channels, nCh, nSamples) != 0;
