@@ -152,6 +152,21 @@ int elemhip_loudness_read(elemhip_t* h, elemhip_loudness_info* info, double* mea
 
 int elemhip_loudness_reset(elemhip_t* h) { return h ? h->engine.loudnessReset() : elemhip::kInvalidInstructionFormat; }
 
+int elemhip_resample_frames(elemhip_t* h, size_t numFrames, size_t* out) { return h ? h->engine.resampleFrames(numFrames, out) : elemhip::kInvalidInstructionFormat; }
+
+int elemhip_resample_read(elemhip_t* h, elemhip_resample_info* info) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    Engine::ResampleInfo ri{};
+    const int rc = h->engine.resampleRead(&ri);
+    if (info && rc == elemhip::kOk) {
+        info->up = ri.up; info->down = ri.down; info->taps = ri.taps; info->latency_frames = ri.latencyFrames;
+        info->frames_in = ri.framesIn; info->frames_out = ri.framesOut;
+    }
+    return rc;
+}
+
+int elemhip_resample_reset(elemhip_t* h) { return h ? h->engine.resampleReset() : elemhip::kInvalidInstructionFormat; }
+
 int elemhip_loudness_gate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
     if (!out || (channels && subBlocks && !meanSquares)) return elemhip::kInvalidInstructionFormat;
     const loudness::Gated g = loudness::gate(meanSquares, channels, subBlocks, weights);

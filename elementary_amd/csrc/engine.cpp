@@ -188,6 +188,7 @@ Engine::~Engine() {
     for (int k = 0; k < 2; ++k) { if (hPcmIn[k]) (void)hipHostFree(hPcmIn[k]); if (dPcmIn[k]) (void)hipFree(dPcmIn[k]); }
     if (dPcmInRowBase) (void)hipFree(dPcmInRowBase);
     loudnessFree();
+    resampleFree();
     if (ioStream) (void)hipStreamDestroy(ioStream);
     if (relayStream) { (void)hipStreamSynchronize(relayStream); (void)hipStreamDestroy(relayStream); }
     if (evRelay) (void)hipEventDestroy(evRelay);
@@ -518,10 +519,13 @@ int Engine::setOption(const std::string& key, double value) {
     // it on resets the meter; off (the default) not one launch or byte differs.
     if (key == "loudness_meter") {
         const bool on = value != 0.0;
-        if (on && !dry) { loudness::make_plan(sampleRate, loudPlan); const int rc = loudnessResetLocked(0); if (rc != kOk) return rc; }
+        if (on && !dry) { loudness::make_plan(deliveryRate(), loudPlan); const int rc = loudnessResetLocked(0); if (rc != kOk) return rc; }      // (it meters what is delivered)
         loudnessOn = on;
         return kOk;
     }
+    // resample.h: the host-buffer render calls deliver at this rate (Hz, integral like the engine's; 0 or the engine's rate: off),
+    // converted on the GPU behind every launch set. Setting it starts a new programme — the meter's too, at the delivery rate.
+    if (key == "resample_rate") return setResampleRate(value);
     if (key == "batch_blocks") { batchBlocks = std::max(1, std::min(1024, (int)value)); return kOk; }      // blocks per multi-block launch (1 = off)
     if (key == "debug_build_delay_ms") { debugBuildDelayMs = std::max(0, (int)value); return kOk; }   // tests: stretches the unlocked part of a plan build
     if (key == "plan_cache") { planCache = std::max(0, std::min(2, (int)value)); islandCache.clear(); islandShapeCache.clear(); return kOk; }

@@ -27,6 +27,7 @@
 #include "json.h"
 #include "jit.h"
 #include "loudness.h"
+#include "resample.h"
 
 namespace elemhip {
 
@@ -241,6 +242,18 @@ public:
     // truePeak (zero-padded tail included, the carried state is not disturbed) / samplePeak: one per channel; any pointer may be null
     int loudnessRead(LoudnessInfo* info, double* meanSquares, size_t capacity, double* truePeak, float* samplePeak);
     int loudnessReset();
+    // Option "resample_rate" (resample.h; 0 or the engine's own rate: off): the frames processBlocksHost / processBlocksPcm /
+    // processBlocksPcmIo deliver — planar floats, packed streams, what the meter meters — are the render converted to that rate behind
+    // every launch set's last level (resample.hip); where those calls render host block by host block the header's scalar loop converts
+    // the floats on the host. `numFrames` stays the RENDERED count; the arrays and streams receive resampleFrames(numFrames) frames.
+    // process() and the device-resident processBlocks() are NOT resampled. The programme is the frames those calls rendered, in call
+    // order, since the option was set or the last reset; its clock lives on the host, the last H input frames of every channel on
+    // the device. Its channel count is that of the first call: a call with another count is refused (reset first). A call that
+    // fails starts a new programme.
+    struct ResampleInfo { uint32_t up, down, taps, latencyFrames; uint64_t framesIn, framesOut; };
+    int resampleFrames(size_t numFrames, size_t* out);       // frames the next host-buffer call of numFrames delivers (off: numFrames)
+    int resampleRead(ResampleInfo* info);
+    int resampleReset();
     // render `numBlocks` blocks with a HIP event pair around every kernel launch; msOut[l] = mean
     // duration of launch level l (l < numLevels), msOut[numLevels] = epilogue. Returns levels + 1.
     int timeLaunches(size_t nOut, size_t numBlocks, float* msOut, size_t cap);
@@ -406,6 +419,23 @@ private:
     int ensureLoudness(size_t channels, size_t setFrames);      // (`mu` held, both streams idle)
     int loudnessResetLocked(size_t channels);
     void loudnessFree();
+    // delivery-rate conversion (option "resample_rate"): the tables and two copies of the carried frames on the device (a set's kernel
+    // reads one, its history step writes the other), per half the converted set; the programme's clock on the host
+    bool resampleOn = false;
+    double resampleRate = 0.0;             // the delivery rate (0: off)
+    resample::Plan resPlan{};
+    std::vector<float> resTable; std::vector<int32_t> resRowBase;                 // host copies: the scalar loop's
+    float* dResTable = nullptr; int32_t* dResRowBase = nullptr;
+    float* dResHist[2] = {nullptr, nullptr}; size_t resHistChannels = 0; int resHistCur = 0;
+    float* dRes[2] = {nullptr, nullptr}; size_t resFloats = 0;
+    uint32_t resChannels = 0;              // channels of the programme (0: none yet)
+    uint64_t resFramesIn = 0, resFramesOut = 0;
+    uint32_t resValidOf[2] = {0, 0}; uint64_t resOffsetOf[2] = {0, 0};            // per half: the set's delivered frames, and where in the call's arrays they go
+    double deliveryRate() const { return resampleOn ? resampleRate : sampleRate; }
+    int setResampleRate(double hz);                              // (`mu` held)
+    int ensureResample(size_t channels, size_t outBlocksCap);   // (`mu` held, both streams idle)
+    int resampleResetLocked(size_t channels);
+    void resampleFree();
     int growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], size_t& have, size_t want);
     int ensureRowTable(uint16_t*& dev, uint32_t& haveGroup, uint32_t& dwords, uint32_t group);
     // the set loop of processBlocksHost / processBlocksPcm (`pcm` null: planar floats only)

@@ -1262,6 +1262,10 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
     const uint32_t pcmG = pcm ? pcm->spec.channelsPerStream : 1u, pcmFmt = pcm ? pcm->spec.format : 0u;
     const size_t pcmB = pcm ? pcm_pack::sample_bytes(pcmFmt) : 0;
     const bool meter = loudnessOn && nOut > 0;       // option "loudness_meter": the delivered frames of every set go through the meter
+    // option "resample_rate": what is delivered — floats, packed streams, the meter's frames — is the render converted to the delivery
+    // rate; the pack kernel's time (the dither's key) is then the programme's OUTPUT frame index
+    const bool resamp = resampleOn && nOut > 0;
+    const resample::Plan rp = resPlan;
     // whole HOST blocks, like the reference's block loop (a host block = hostBlockSize / blockSize engine blocks)
     const size_t hb = (size_t)hostBlockSize;
     bool tapSlices = hb % bs != 0;          // ragged slices (a host block that no k divides evenly): launch sets hold whole engine blocks
@@ -1286,11 +1290,25 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             return kOk;
         };
         if (meter) { const int rc = meterSync(true); if (rc != kOk) return rc; }
+        // the converter's carried frames come to the host for the call as well: the header's scalar loop converts, the same bits
+        std::vector<float> resHist(resamp ? nOut * (size_t)rp.H : 0), resOut;
+        auto resSync = [&](bool toHost) -> int {
+            RenderGuard lock(*this);
+            if (hipSetDevice(device) != hipSuccess) return kHipError;
+            if (toHost) { const int rc = ensureResample(nOut, 0); if (rc != kOk) return rc; }
+            HIP_OK(hipStreamSynchronize(stream));
+            if (toHost) HIP_OK(hipMemcpy(resHist.data(), dResHist[resHistCur], resHist.size() * sizeof(float), hipMemcpyDeviceToHost));
+            else HIP_OK(hipMemcpy(dResHist[resHistCur], resHist.data(), resHist.size() * sizeof(float), hipMemcpyHostToDevice));
+            return kOk;
+        };
+        auto resFail = [&]() { if (resamp) { RenderGuard lock(*this); (void)resampleResetLocked(0); } };
+        if (resamp) { const int rc = resSync(true); if (rc != kOk) return rc; }
+        size_t outOff = 0;                      // delivered frames of this call so far
         for (size_t f0 = 0; f0 < numFrames; f0 += hb) {
             const size_t nf = std::min(hb, numFrames - f0);
             for (size_t c = 0; c < nIn; ++c) ip[c] = src ? nullptr : in[c] + f0;
             for (size_t c = 0; c < nOut; ++c) op[c] = wantFloat ? out[c] + f0 : nullptr;
-            if (nf < hb || pcm || meter) {
+            if (nf < hb || pcm || meter || resamp) {
                 // the last, partly filled host block is still a whole block to the engine (offline-renderer/index.ts:104-131: inputs
                 // padded with zeros, the frames beyond the caller's arrays dropped); a PCM call renders every host block here
                 tailOut.assign(nOut * hb, 0.0f);
@@ -1307,26 +1325,44 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 for (size_t c = 0; c < nIn; ++c) { std::memcpy(tailIn.data() + c * hb, in[c] + f0, nf * sizeof(float)); ip[c] = tailIn.data() + c * hb; }
             }
             const int rc = process(ip.data(), nIn, op.data(), nOut, hb, sampleTime + (int64_t)f0);
-            if (rc != kOk) { if (meter) (void)meterSync(false); return rc; }
+            if (rc != kOk) { if (meter) (void)meterSync(false); resFail(); return rc; }
+            // what is delivered of this host block: its nf frames, or their conversion
+            const float* got = tailOut.data();
+            size_t gotStride = hb, nd = nf, at = f0;
+            int64_t gotTime = sampleTime + (int64_t)f0;
+            if (resamp) {
+                std::lock_guard<std::mutex> lock(mu);
+                nd = (size_t)(resample::outputs_before(rp, resFramesIn + nf) - resample::outputs_before(rp, resFramesIn));
+                gotStride = std::max<size_t>(nd, 1);
+                resOut.resize(nOut * gotStride);
+                for (size_t c = 0; c < nOut; ++c)
+                    (void)resample::resample_host(rp, resTable.data(), resRowBase.data(), resHist.data() + c * rp.H, tailOut.data() + c * hb, nf, resFramesIn,
+                                                  resOut.data() + c * gotStride);
+                got = resOut.data(); at = outOff; gotTime = (int64_t)resFramesOut;
+                resFramesIn += nf; resFramesOut += nd;
+            }
             if (meter) {
                 std::lock_guard<std::mutex> lock(mu);
                 for (size_t c = 0; c < nOut; ++c)
-                    loudness::meter_host(loudPlan, meterState[c], tailOut.data() + c * hb, nf, loudFrames, [&](double ms) { loudSeries[c].push_back(ms); });
-                loudFrames += nf;
+                    loudness::meter_host(loudPlan, meterState[c], got + c * gotStride, nd, loudFrames, [&](double ms) { loudSeries[c].push_back(ms); });
+                loudFrames += nd;
             }
-            if ((nf < hb || pcm || meter) && wantFloat) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + f0, tailOut.data() + c * hb, nf * sizeof(float));
+            if ((nf < hb || pcm || meter || resamp) && wantFloat) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + at, got + c * gotStride, nd * sizeof(float));
             if (pcm) {
                 // the floats are on the host: the header's scalar loop packs them — the kernel's functions, the kernel's bits
-                for (size_t s = 0; s < pcm->nStreams; ++s) sp[s] = static_cast<uint8_t*>(pcm->streams[s]) + f0 * pcmG * pcmB;
-                pcm_pack::pack_host(pcmFmt, pcmG, (uint32_t)pcm->nStreams, pcm->spec.dither != 0u, pcm->spec.seed, tailOut.data(), hb, nf,
-                                    sampleTime + (int64_t)f0, sp.data(), pcm->peakBits.data(), pcm->over.data(), pcm->nonfinite.data());
+                for (size_t s = 0; s < pcm->nStreams; ++s) sp[s] = static_cast<uint8_t*>(pcm->streams[s]) + at * pcmG * pcmB;
+                pcm_pack::pack_host(pcmFmt, pcmG, (uint32_t)pcm->nStreams, pcm->spec.dither != 0u, pcm->spec.seed, got, gotStride, nd,
+                                    gotTime, sp.data(), pcm->peakBits.data(), pcm->over.data(), pcm->nonfinite.data());
             }
+            outOff += nd;
         }
-        return meter ? meterSync(false) : kOk;
+        int rc = meter ? meterSync(false) : kOk;
+        if (resamp) { const int rr = resSync(false); if (rc == kOk) rc = rr; if (rc != kOk) resFail(); }
+        return rc;
     }
     const size_t numBlocks = ((numFrames + hb - 1) / hb) * (hb / bs);
     if (numBlocks == 0) return kOk;
-    size_t setBlocks;
+    size_t setBlocks, outCapFrames = 0, outCapBlocks = 0;     // what a set delivers at most: frames, and whole blocks of the converted half
     {
         RenderGuard lock(*this);
         if (hipSetDevice(device) != hipSuccess) return kHipError;
@@ -1336,18 +1372,24 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         // launch sets hold whole HOST blocks: a newer render sequence is adopted at a set boundary (enqueueBlocks), and the reference
         // swaps sequences at host-block boundaries only (Runtime.h:277-285)
         if (hb > bs) setBlocks = std::min(numBlocks, std::max(hb / bs, setBlocks / (hb / bs) * (hb / bs)));
-        int rc = ensureHostStaging(setBlocks * std::max<size_t>(nOut, 1) * bs, setBlocks * std::max<size_t>(nIn, 1) * bs);
+        outCapFrames = resamp ? (size_t)resample::ceil_div((uint64_t)(setBlocks * bs) * rp.L, rp.M) + 1 : setBlocks * bs;
+        outCapBlocks = (outCapFrames + bs - 1) / bs;
+        int rc = ensureHostStaging(std::max(setBlocks, outCapBlocks) * std::max<size_t>(nOut, 1) * bs, setBlocks * std::max<size_t>(nIn, 1) * bs);
         if (rc != kOk) return rc;
+        if (resamp) {
+            rc = ensureResample(nOut, outCapBlocks);
+            if (rc != kOk) return rc;
+        }
         if (src) {
             rc = ensurePcmInStaging(src->nStreams * (size_t)pcm_pack::stream_stride(setBlocks * bs, srcG, srcFmt), srcG);
             if (rc != kOk) return rc;
         }
         if (pcm) {
-            rc = ensurePcmStaging(pcm->nStreams * (size_t)pcm_pack::stream_stride(setBlocks * bs, pcmG, pcmFmt) + nOut * sizeof(pcm_pack::ChannelStats), pcmG);
+            rc = ensurePcmStaging(pcm->nStreams * (size_t)pcm_pack::stream_stride(outCapFrames, pcmG, pcmFmt) + nOut * sizeof(pcm_pack::ChannelStats), pcmG);
             if (rc != kOk) return rc;
         }
         if (meter) {
-            rc = ensureLoudness(nOut, setBlocks * bs);
+            rc = ensureLoudness(nOut, outCapFrames);
             if (rc != kOk) return rc;
         }
     }
@@ -1375,8 +1417,18 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             }
         });
     };
+    auto scatterConverted = [&](size_t k) {     // the same for a converted set: its frames go where the call's earlier sets ended
+        const size_t valid = resValidOf[k & 1], at = (size_t)resOffsetOf[k & 1], nb = (valid + bs - 1) / bs;
+        const float* src = hStageOut[k & 1];
+        spread(nb * nOut * bs * sizeof(float), nb, [&](size_t t, size_t threads) {
+            for (size_t b = nb * t / threads; b < nb * (t + 1) / threads; ++b) {
+                const size_t n = std::min(bs, valid - b * bs);
+                for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + at + b * bs, src + (b * nOut + c) * bs, n * sizeof(float));
+            }
+        });
+    };
     auto deliverPcm = [&](size_t k) {  // pinned packed half -> the caller's streams (one contiguous stretch per stream), statistics summed
-        const size_t valid = pcm->validOf[k & 1], f0 = k * setBlocks * bs;
+        const size_t valid = pcm->validOf[k & 1], f0 = resamp ? (size_t)resOffsetOf[k & 1] : k * setBlocks * bs;
         const size_t stride = (size_t)pcm_pack::stream_stride(valid, pcmG, pcmFmt), len = valid * pcmG * pcmB;
         const unsigned char* src = hPcm[k & 1];
         spread(pcm->nStreams * len, len / 4096 + 1, [&](size_t t, size_t threads) {
@@ -1396,9 +1448,9 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         for (size_t c = 0; c < nOut; ++c)
             for (uint32_t j = 0; j < loudCountOf[k & 1]; ++j) loudSeries[c].push_back(sums[c * loudOutStride + j] / (double)loudPlan.hop);
     };
-    auto deliver = [&](size_t k) { if (wantFloat) scatter(k); if (pcm) deliverPcm(k); if (meter) deliverLoudness(k); };
+    auto deliver = [&](size_t k) { if (wantFloat) { if (resamp) scatterConverted(k); else scatter(k); } if (pcm) deliverPcm(k); if (meter) deliverLoudness(k); };
     int result = kOk;
-    size_t issued = 0, scattered = 0;
+    size_t issued = 0, scattered = 0, outOff = 0;
     // a failing HIP call ends the loop; the tail below drains both streams, releases what was deferred and reports the code —
     // `out` then holds the sets scattered so far (whole launch sets, in order), nothing is left in flight
 #define HOST_TRY(call) { if ((call) != hipSuccess) { std::fprintf(stderr, "[elemhip] %s failed: %s\n", #call, hipGetErrorString(hipGetLastError())); result = kHipError; break; } }
@@ -1462,17 +1514,37 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 const uint64_t per = hb / bs, base = st.blocksRendered - nb;
                 for (uint64_t e = per; e <= nb; e += per) { if (hostBlockEnds.size() >= 65536) hostBlockEnds.pop_front(); hostBlockEnds.push_back(base + e); }
             }
+            // what the set delivers: its valid frames where the levels left them, or their conversion
+            const float* got = dStageOut[half];
+            size_t valid = std::min(nb * bs, numFrames - b0 * bs), gotBlocks = nb;
+            int64_t gotTime = sampleTime + (int64_t)(b0 * bs);
+            if (resamp) {
+                // the converter behind the set's last level, in front of the pack kernel and the meter, on the same stream: it reads the
+                // block that is still warm in L2 and one copy of the carried frames, its history step writes the other copy. The converted
+                // half was drained by the D2H of set k - 2 (evOut above).
+                ResampleArgs a{};
+                a.src = dStageOut[half]; a.dst = dRes[half]; a.histIn = dResHist[resHistCur]; a.histOut = dResHist[resHistCur ^ 1];
+                a.table = dResTable; a.rowBase = dResRowBase; a.t0 = resFramesIn; a.n0 = resFramesOut;
+                a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nOut; a.validIn = (uint32_t)valid;
+                a.validOut = (uint32_t)(resample::outputs_before(rp, resFramesIn + valid) - resFramesOut);
+                a.outBlocks = (uint32_t)((a.validOut + bs - 1) / bs); a.outBlocksCap = (uint32_t)outCapBlocks; a.plan = rp;
+                HOST_TRY(launch_resample(stream, a));
+                resHistCur ^= 1;
+                resValidOf[half] = a.validOut; resOffsetOf[half] = outOff;
+                got = dRes[half]; gotBlocks = a.outBlocks; gotTime = (int64_t)resFramesOut;
+                resFramesIn += valid; resFramesOut += a.validOut;
+                valid = a.validOut; outOff += valid;
+            }
             size_t pcmCopy = 0;
             if (pcm) {
                 // the pack kernel behind the set's last level, on the same stream: the output block is still warm in L2. Its packed
                 // half was drained by the D2H of set k - 2 (evOut above).
-                const size_t valid = std::min(nb * bs, numFrames - b0 * bs);
                 const size_t stride = (size_t)pcm_pack::stream_stride(valid, pcmG, pcmFmt), statsOff = pcm->nStreams * stride;
                 pcm->validOf[half] = (uint32_t)valid;
                 HOST_TRY(hipMemsetAsync(dPcm[half] + statsOff, 0, nOut * sizeof(pcm_pack::ChannelStats), stream));
                 PcmPackArgs a{};
-                a.src = dStageOut[half]; a.dst = dPcm[half]; a.stats = reinterpret_cast<pcm_pack::ChannelStats*>(dPcm[half] + statsOff);
-                a.rowBase = dPcmRowBase; a.time0 = sampleTime + (int64_t)(b0 * bs); a.streamStride = stride;
+                a.src = got; a.dst = dPcm[half]; a.stats = reinterpret_cast<pcm_pack::ChannelStats*>(dPcm[half] + statsOff);
+                a.rowBase = dPcmRowBase; a.time0 = gotTime; a.streamStride = stride;
                 a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nOut; a.G = pcmG; a.numStreams = (uint32_t)pcm->nStreams;
                 a.validFrames = (uint32_t)valid; a.tilesPerBlock = pcm_pack::tiles_per_block((uint32_t)bs, pcmG); a.rowDwords = pcmRowDwords;
                 a.dither = pcm->spec.dither ? 1u : 0u; a.seed = pcm->spec.seed;
@@ -1483,9 +1555,8 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 // the meter's kernels behind the set's last level too, next to the pack kernel: they read the same block. The state they
                 // carry lives on the device; the sums of the sub-blocks this set completes go to this half's small region, drained like
                 // the packed half by the D2H of set k - 2.
-                const size_t valid = std::min(nb * bs, numFrames - b0 * bs);
                 LoudnessArgs a{};
-                a.src = dStageOut[half]; a.state = dLoudState; a.segState = dLoudSeg; a.segEnergy = dLoudEnergy; a.out = dLoudOut[half];
+                a.src = got; a.state = dLoudState; a.segState = dLoudSeg; a.segEnergy = dLoudEnergy; a.out = dLoudOut[half];
                 a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nOut; a.validFrames = (uint32_t)valid;
                 a.numSegs = loudness::segment_count((uint32_t)valid, loudPlan.L); a.segCap = (uint32_t)loudSegCap; a.outStride = (uint32_t)loudOutStride;
                 a.q0 = (uint32_t)(loudFrames % loudPlan.hop); a.plan = loudPlan;
@@ -1495,7 +1566,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             }
             HOST_TRY(hipEventRecord(evRendered[half], stream));
             HOST_TRY(hipStreamWaitEvent(ioStream, evRendered[half], 0));
-            if (wantFloat || !pcm) { if (nOut) HOST_TRY(hipMemcpyAsync(hStageOut[half], dStageOut[half], nb * nOut * bs * sizeof(float), hipMemcpyDeviceToHost, ioStream)); }
+            if (wantFloat || !pcm) { if (nOut && gotBlocks) HOST_TRY(hipMemcpyAsync(hStageOut[half], got, gotBlocks * nOut * bs * sizeof(float), hipMemcpyDeviceToHost, ioStream)); }
             if (pcm) HOST_TRY(hipMemcpyAsync(hPcm[half], dPcm[half], pcmCopy, hipMemcpyDeviceToHost, ioStream));
             if (meter && loudCountOf[half]) HOST_TRY(hipMemcpyAsync(hLoudOut[half], dLoudOut[half], nOut * loudOutStride * sizeof(double), hipMemcpyDeviceToHost, ioStream));
             HOST_TRY(hipEventRecord(evOut[half], ioStream));
@@ -1522,6 +1593,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         freeDeferred();
         // a metered call that failed may have advanced the carried state past sets whose sums never arrived: the programme starts anew
         if (meter && result != kOk) (void)loudnessResetLocked(loudChannels);
+        if (resamp && result != kOk) (void)resampleResetLocked(0);      // likewise: the clock may be ahead of what was delivered
     }
     return result;
 }

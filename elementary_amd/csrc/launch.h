@@ -4,6 +4,7 @@
 #include "device.h"
 #include "pcm_pack.h"
 #include "loudness.h"
+#include "resample.h"
 
 namespace elemhip {
 
@@ -102,6 +103,19 @@ struct LoudnessArgs {
     loudness::Plan  plan;
 };
 hipError_t launch_loudness(hipStream_t s, const LoudnessArgs& a);
+// ---- delivery-rate conversion (resample.hip): behind a launch set's last level, in front of the pack kernel and the meter, resample.h ----
+struct ResampleArgs {
+    const float*    src;            // the set's output, [block][numChannels][blockSize]: validIn frames at the engine's rate
+    float*          dst;            // [outBlocks][numChannels][blockSize]: validOut frames at the delivery rate, zeros up to the last block's end
+    const float*    histIn;         // [numChannels][plan.H]: the programme's frames in front of the set, oldest first
+    float*          histOut;        // the other copy: receives the frames in front of the NEXT set
+    const float*    table;          // resample::make_tables: [plan.T][plan.L]
+    const int32_t*  rowBase;        // [plan.L]
+    uint64_t        t0, n0;         // the programme's input / output frame index at the set's start
+    uint32_t        blockSize, numChannels, validIn, validOut, outBlocks, outBlocksCap;
+    resample::Plan  plan;
+};
+hipError_t launch_resample(hipStream_t s, const ResampleArgs& a);
 hipError_t launch_bus_sum(hipStream_t s, float* dst, const float* const* partials, uint32_t count, size_t n);   // dst = ((p0 + p1) + p2) + ... (rank order)
 
 } // namespace elemhip

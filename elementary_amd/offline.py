@@ -21,7 +21,8 @@ class OfflineRenderer:
 
     def initialize(self, num_input_channels: int = 0, num_output_channels: int = 2, sample_rate: float = 44100,
                    block_size: int = 512, virtual_file_system: Optional[Dict[str, np.ndarray]] = None,
-                   event_history_blocks: int = 0, capture_history_blocks: int = 0, loudness_meter: bool = False) -> None:
+                   event_history_blocks: int = 0, capture_history_blocks: int = 0, loudness_meter: bool = False,
+                   output_sample_rate: Optional[float] = None) -> None:
         """``event_history_blocks`` (no counterpart in the reference; 0 = off): engine option of the same name — `scope` and `fft`
         nodes keep a device ring long enough for a relay window of that many blocks, so ``process`` still renders launch sets of
         that size with such a listener attached (engines without ``set_option`` relay after every block anyway).
@@ -29,7 +30,12 @@ class OfflineRenderer:
         blocks of takes and a per-block log from which the blockwise relay places every take at the block where the gate fell.
         ``loudness_meter`` (likewise; off by default): engine option of the same name — every launch set that ``process`` (in engine
         calls of many blocks), ``process_pcm``, ``process_pcm_io``, ``write_wav`` and ``process_wav`` render is metered on the GPU:
-        BS.1770 sub-block energies and true peak, read with ``loudness()``."""
+        BS.1770 sub-block energies and true peak, read with ``loudness()``.
+        ``output_sample_rate`` (likewise; None or ``sample_rate`` itself: off): engine option ``resample_rate`` — the engine renders at
+        ``sample_rate`` and ``process`` (whose output buffers then hold the DELIVERED frames: ``ceil(rendered * up / down)`` of them),
+        ``process_pcm`` and ``process_pcm_io`` deliver at this rate, converted on the GPU by a windowed-sinc filter whose latency is
+        ``resample()['latency_frames']`` output frames; ``write_wav`` and ``process_wav`` write files at this rate with that latency
+        taken out. Rendering at 4 x 44100 and delivering 44100 is oversampling. An engine without the option raises ``RuntimeError``."""
         self.num_in = int(num_input_channels)
         self.num_out = int(num_output_channels)
         self.block_size = int(block_size)
@@ -42,6 +48,16 @@ class OfflineRenderer:
         self._loudness = bool(loudness_meter)
         if self._loudness:
             self._rt.set_option("loudness_meter", 1)
+        self.output_sample_rate = self.sample_rate
+        self._resample = output_sample_rate is not None and float(output_sample_rate) != self.sample_rate
+        if self._resample:
+            if not hasattr(self._rt, "set_option") or not hasattr(self._rt, "resample_read"):
+                raise RuntimeError("this engine cannot deliver at another sample rate (option resample_rate)")
+            try:
+                self._rt.set_option("resample_rate", float(output_sample_rate))
+            except RuntimeError as e:
+                raise RuntimeError(f"this engine cannot deliver {self.sample_rate:g} Hz renders at {float(output_sample_rate):g} Hz") from e
+            self.output_sample_rate = float(output_sample_rate)
         self._time = 0
         for k, v in (virtual_file_system or {}).items():
             self._rt.add_shared_resource(k, v)
@@ -74,12 +90,17 @@ class OfflineRenderer:
         total = len(outputs[0])
         host_batch = getattr(self._rt, "process_blocks_host", None)
         window = getattr(self._rt, "event_window_blocks", None)
-        if host_batch is not None and window is not None and any(self._listeners.values()) and total > bs:
+        if self._resample:
+            # the output buffers hold DELIVERED frames: render the inputs' length, or — without inputs — what fills the buffers
+            info = self._rt.resample_read()
+            total = max([len(b) for b in inputs], default=-((-total * info["down"]) // info["up"]))
+        if host_batch is not None and window is not None and any(self._listeners.values()) and (total > bs or self._resample):
             # listeners to serve: the reference relays events after EVERY block (index.ts:112-122). The engine keeps per-block readout
             # logs, so the block loop still runs as launch sets — `event_window_blocks()` blocks per engine call (1024 with meters and
             # snapshots only, fewer with a scope ring, one with a capture node made without history) — and the BLOCKWISE relay after each call hands the
             # listeners every block's events in block order, as the per-block loop would have
             w = max(1, int(window())) * bs
+            at = 0                                   # delivered frames so far
             for k in range(0, total, w):
                 m = min(w, total - k)
                 x = None
@@ -94,11 +115,12 @@ class OfflineRenderer:
                     for cb in self._listeners.get(kind, []):
                         cb(payload)
                 for i, buf in enumerate(outputs):
-                    mm = min(m, len(buf) - k)
+                    mm = min(y.shape[1], len(buf) - at)
                     if mm > 0:
-                        buf[k:k + mm] = y[i, :mm]
+                        buf[at:at + mm] = y[i, :mm]
+                at += y.shape[1]
             return
-        if host_batch is not None and not any(self._listeners.values()) and total > bs:
+        if host_batch is not None and not any(self._listeners.values()) and (total > bs or self._resample):
             # no event listeners to serve between blocks: the whole block loop in one engine call
             # (elemhip_process_blocks_host: launch sets staged through pinned double buffers); the event queues are drained
             # once afterwards, as the per-block loop's relay (index.ts:118-122) would have kept them drained — a listener
@@ -113,9 +135,11 @@ class OfflineRenderer:
             self._time += ((total + bs - 1) // bs) * bs
             self._rt.process_queued_events()
             for i, buf in enumerate(outputs):
-                m = min(total, len(buf))
+                m = min(y.shape[1], len(buf))
                 buf[:m] = y[i, :m]
             return
+        if self._resample:
+            raise RuntimeError("this engine cannot deliver at another sample rate (no process_blocks_host)")
         for k in range(0, total, bs):
             block_in = None
             if self.num_in:
@@ -196,6 +220,28 @@ class OfflineRenderer:
             return one(range(got["channels"]))
         return [one(chs) for chs in programmes]
 
+    def resample(self) -> Dict[str, int]:
+        """The converter's plan and clock (``initialize(output_sample_rate=...)``): ``{'up', 'down', 'taps', 'latency_frames',
+        'frames_in', 'frames_out'}``."""
+        if not self._resample:
+            raise RuntimeError("delivery at another rate is off: initialize(output_sample_rate=...)")
+        return self._rt.resample_read()
+
+    def resample_reset(self) -> None:
+        """A new programme for the converter: time 0, silence in front of it."""
+        self._rt.resample_reset()
+
+    def _file_span(self, num_frames: int):
+        """A file of a converted render: (frames to render, delivered frames to drop in front, frames the file holds). The filter's
+        latency Do is taken out, so frame n of the file is the render at time n * down / up: ceil(Do down / up) further frames are
+        rendered, the first Do delivered frames dropped, ceil(num_frames up / down) kept. A new programme starts."""
+        if not self._resample:
+            return int(num_frames), 0, int(num_frames)
+        self._rt.resample_reset()
+        info = self._rt.resample_read()
+        up, down, lat = info["up"], info["down"], info["latency_frames"]
+        return int(num_frames) + -((-lat * down) // up), lat, -((-int(num_frames) * up) // down)
+
     def loudness_reset(self) -> None:
         """A new programme for the loudness meter: time 0, zero filter state, no peaks."""
         self._rt.loudness_reset()
@@ -226,16 +272,21 @@ class OfflineRenderer:
             paths = [str(path).format(s) for s in range(S)]
         if len(paths) != S:
             raise ValueError(f"{S} streams need {S} paths")
-        bs, total = self.block_size, int(num_frames)
+        bs = self.block_size
+        total, skip, keep = self._file_span(num_frames)
         chunk = max(bs, (int(chunk_frames) // bs) * bs)
-        writers = [WavWriter(p, fmt if isinstance(fmt, str) else {1: "s16", 2: "s24", 3: "f32"}[int(fmt)], G, self.sample_rate) for p in paths]
+        writers = [WavWriter(p, fmt if isinstance(fmt, str) else {1: "s16", 2: "s24", 3: "f32"}[int(fmt)], G, self.output_sample_rate) for p in paths]
         stats = None
         try:
             for k in range(0, total, chunk):
                 m = min(chunk, total - k)
                 streams, st, _ = self.process_pcm([np.asarray(b)[k:k + m] for b in inputs], S, G, m, fmt, dither_seed=dither_seed)
+                drop = min(skip, len(streams[0])) if streams else 0
+                take = min(keep, (len(streams[0]) if streams else 0) - drop)
+                skip -= drop
+                keep -= take
                 for wtr, a in zip(writers, streams):
-                    wtr.write(a)
+                    wtr.write(a[drop:drop + take])
                 if stats is None:
                     stats = st
                 else:
@@ -328,15 +379,19 @@ class OfflineRenderer:
             if sum(r.channels for r in readers) != self.num_in:
                 raise ValueError(f"Invalid input data; expected {self.num_in} channels in all.")
             bs = self.block_size
-            total = int(num_frames) if num_frames is not None else max([r.frames for r in readers], default=0)
+            total, skip, keep = self._file_span(int(num_frames) if num_frames is not None else max([r.frames for r in readers], default=0))
             chunk = max(bs, (int(chunk_frames) // bs) * bs)
-            writers = [WavWriter(p, fmt, G, self.sample_rate) for p in outs]
+            writers = [WavWriter(p, fmt, G, self.output_sample_rate) for p in outs]
             in_fmt = readers[0].fmt if readers else "s16"
             for k in range(0, total, chunk):
                 m = min(chunk, total - k)
                 streams, st, _ = self.process_pcm_io([r.read(m) for r in readers], in_fmt, m, fmt, S, G, dither_seed=dither_seed)
+                drop = min(skip, len(streams[0])) if streams else 0
+                take = min(keep, (len(streams[0]) if streams else 0) - drop)
+                skip -= drop
+                keep -= take
                 for wtr, a in zip(writers, streams):
-                    wtr.write(a)
+                    wtr.write(a[drop:drop + take])
                 if stats is None:
                     stats = st
                 else:

@@ -72,6 +72,12 @@ def load_library() -> C.CDLL:
         lib.elemhip_loudness_reset.restype = C.c_int
         lib.elemhip_loudness_gate.argtypes = [_dp, C.c_size_t, C.c_size_t, _dp, C.POINTER(_LoudnessResult)]
         lib.elemhip_loudness_gate.restype = C.c_int
+        lib.elemhip_resample_frames.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.elemhip_resample_frames.restype = C.c_int
+        lib.elemhip_resample_read.argtypes = [C.c_void_p, C.POINTER(_ResampleInfo)]
+        lib.elemhip_resample_read.restype = C.c_int
+        lib.elemhip_resample_reset.argtypes = [C.c_void_p]
+        lib.elemhip_resample_reset.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -90,6 +96,11 @@ class _PcmChannelStats(C.Structure):
 
 class _LoudnessInfo(C.Structure):
     _fields_ = [("channels", C.c_uint32), ("hop", C.c_uint32), ("sub_blocks", C.c_uint64), ("frames", C.c_uint64)]
+
+
+class _ResampleInfo(C.Structure):
+    _fields_ = [("up", C.c_uint32), ("down", C.c_uint32), ("taps", C.c_uint32), ("latency_frames", C.c_uint32),
+                ("frames_in", C.c_uint64), ("frames_out", C.c_uint64)]
 
 
 class _LoudnessResult(C.Structure):
@@ -157,7 +168,8 @@ class Runtime(CRuntime):
         """``elemhip_process_blocks_host``: the offline caller's whole block loop over HOST arrays.
 
         ``inputs``: float32 ``[num_inputs, num_frames]`` (or None); returns / fills ``out``: float32
-        ``[num_outputs, num_frames]`` (C-contiguous rows). ``ceil(num_frames / block_size)`` full blocks are rendered.
+        ``[num_outputs, num_frames]`` (C-contiguous rows). ``ceil(num_frames / block_size)`` full blocks are rendered. With option
+        ``resample_rate`` on, ``num_frames`` stays the rendered count and the rows hold ``resample_frames(num_frames)`` frames.
         """
         import numpy as np
         from ._cabi import _ptr_array
@@ -171,9 +183,10 @@ class Runtime(CRuntime):
                 num_frames = a.shape[1]
         if num_frames is None:
             num_frames = out.shape[1]
+        n_out = self.resample_frames(num_frames)
         if out is None:
-            out = np.empty((num_outputs, int(num_frames)), dtype=np.float32)
-        assert out.dtype == np.float32 and out.shape[0] == num_outputs and out.shape[1] >= num_frames and out.strides[1] == 4
+            out = np.empty((num_outputs, n_out), dtype=np.float32)
+        assert out.dtype == np.float32 and out.shape[0] == num_outputs and out.shape[1] >= n_out and out.strides[1] == 4
         st = self.sample_time if sample_time is None else int(sample_time)
         rc = self._lib.elemhip_process_blocks_host(self._h, _ptr_array(rows), len(rows),
                                                    _ptr_array([out[i] for i in range(num_outputs)]), num_outputs, int(num_frames), st)
@@ -208,9 +221,10 @@ class Runtime(CRuntime):
         if num_frames is None:
             raise ValueError("num_frames is needed without inputs")
         n, S, G, code = int(num_frames), int(num_streams), int(channels_per_stream), pcm_format(fmt)
-        shape, dtype = {1: ((n, G), np.int16), 2: ((n, G, 3), np.uint8)}.get(code, ((n, G), np.float32))
+        nd = self.resample_frames(n)          # frames delivered (option "resample_rate"; n while it is off)
+        shape, dtype = {1: ((nd, G), np.int16), 2: ((nd, G, 3), np.uint8)}.get(code, ((nd, G), np.float32))
         streams = [np.zeros(shape, dtype=dtype) for _ in range(S)]
-        planar = np.zeros((S * G, n), dtype=np.float32) if want_float else None
+        planar = np.zeros((S * G, nd), dtype=np.float32) if want_float else None
         stats = (_PcmChannelStats * max(1, S * G))()
         spec = _PcmSpec(code, G, 0 if dither_seed is None else 1, 0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFF)
         sp = (C.c_void_p * max(1, S))(*[C.c_void_p(a.ctypes.data) for a in streams])
@@ -266,18 +280,19 @@ class Runtime(CRuntime):
         ip = (C.c_void_p * max(1, len(ins)))(*[C.c_void_p(a.ctypes.data) for a in ins])
         in_spec = _PcmInSpec(in_code, in_g)
         st = self.sample_time if sample_time is None else int(sample_time)
+        nd = self.resample_frames(n)          # frames delivered (option "resample_rate"; n while it is off)
         if out_fmt is None:
             if num_outputs is None:
                 raise ValueError("num_outputs is needed for planar float output")
-            out = np.empty((int(num_outputs), n), dtype=np.float32)
+            out = np.empty((int(num_outputs), nd), dtype=np.float32)
             rc = self._lib.elemhip_process_blocks_pcm_io(self._h, ip, len(ins), C.byref(in_spec), None, 0, None,
                                                          _ptr_array([out[i] for i in range(int(num_outputs))]), int(num_outputs), n, st, None)
             result = out
         else:
             S, G, code = int(num_streams), int(channels_per_stream), pcm_format(out_fmt)
-            shape, dtype = {1: ((n, G), np.int16), 2: ((n, G, 3), np.uint8)}.get(code, ((n, G), np.float32))
+            shape, dtype = {1: ((nd, G), np.int16), 2: ((nd, G, 3), np.uint8)}.get(code, ((nd, G), np.float32))
             streams = [np.zeros(shape, dtype=dtype) for _ in range(S)]
-            planar = np.zeros((S * G, n), dtype=np.float32) if want_float else None
+            planar = np.zeros((S * G, nd), dtype=np.float32) if want_float else None
             stats = (_PcmChannelStats * max(1, S * G))()
             spec = _PcmSpec(code, G, 0 if dither_seed is None else 1, 0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFF)
             sp = (C.c_void_p * max(1, S))(*[C.c_void_p(a.ctypes.data) for a in streams])
@@ -326,6 +341,35 @@ class Runtime(CRuntime):
         rc = self._lib.elemhip_loudness_reset(self._h)
         if rc != 0:
             err = ElemHipError(f"elemhip_loudness_reset failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+
+    def resample_frames(self, num_frames: int) -> int:
+        """``elemhip_resample_frames``: the frames the next ``process_blocks_host`` / ``_pcm`` / ``_pcm_io`` call of ``num_frames``
+        rendered frames delivers — ``num_frames`` itself while option ``resample_rate`` is off."""
+        got = C.c_size_t(0)
+        rc = self._lib.elemhip_resample_frames(self._h, int(num_frames), C.byref(got))
+        if rc != 0:
+            raise ElemHipError(f"elemhip_resample_frames failed: {describe(rc)} (code {rc})")
+        return int(got.value)
+
+    def resample_read(self) -> Dict[str, Any]:
+        """``elemhip_resample_read`` (option ``resample_rate``): ``{'up', 'down', 'taps', 'latency_frames', 'frames_in',
+        'frames_out'}`` — delivery rate / engine rate = up / down in lowest terms, taps per output, the filter's latency in OUTPUT
+        frames, and the programme's clock: frames rendered and frames delivered since the option was set or the last reset."""
+        info = _ResampleInfo()
+        rc = self._lib.elemhip_resample_read(self._h, C.byref(info))
+        if rc != 0:
+            err = ElemHipError(f"elemhip_resample_read failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return {k: int(getattr(info, k)) for k, _ in _ResampleInfo._fields_}
+
+    def resample_reset(self) -> None:
+        """``elemhip_resample_reset``: a new programme (time 0, silence in front of it)."""
+        rc = self._lib.elemhip_resample_reset(self._h)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_resample_reset failed: {describe(rc)} (code {rc})")
             err.code = rc
             raise err
 

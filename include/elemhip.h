@@ -171,6 +171,28 @@ int elemhip_loudness_read(elemhip_t*, elemhip_loudness_info* info, double* meanS
 int elemhip_loudness_reset(elemhip_t*);
 int elemhip_loudness_gate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out);
 
+/* EXTENSION (no counterpart in the reference): delivery at another sample rate, converted on the GPU (elementary_amd/csrc/resample.hip;
+ * the arithmetic: resample.h). After elemhip_set_option(h, "resample_rate", hz) — hz integral like the engine's rate; 0 or the engine's
+ * own rate: off, the default — elemhip_process_blocks_host, elemhip_process_blocks_pcm and elemhip_process_blocks_pcm_io deliver the
+ * render converted from the engine's rate fin to hz by a Kaiser-windowed sinc (32 zero crossings a side at the lower rate, pass band
+ * +-0.001 dB to 0.9 of the lower Nyquist, -96 dB from 1.1 of it), behind every launch set's last render level: planar floats, packed
+ * streams (the dither is keyed on the programme's OUTPUT frame index then, not on sampleTime) and what the loudness meter meters, whose
+ * hop follows the delivery rate. numFrames stays the RENDERED count; the arrays and streams of such a call must hold
+ * elemhip_resample_frames(numFrames) frames. With up / down = hz / fin in lowest terms, the programme — the frames those calls rendered,
+ * in call order, since the option was set or elemhip_resample_reset — delivers exactly ceil(t * up / down) frames for its first t, so a
+ * call that renders [t0, t1) delivers [ceil(t0 up / down), ceil(t1 up / down)): however a render is cut into calls and launch sets, the
+ * same bytes. Output n is the render at time (n - latency_frames) * down / up; frames in front of the programme are silence.
+ * elemhip_process and the device-resident elemhip_process_blocks are NOT converted. The programme's channel count is that of its first
+ * call; a call with another count returns 6 (reset first); a call that fails starts a new programme. Code 6 for a rate without a plan:
+ * not integral, up > 1024, more than 1024 taps (down / up > 16), or up / down > 8.
+ *   elemhip_resample_frames  frames the next host-buffer call of numFrames will deliver (numFrames while the option is off)
+ *   elemhip_resample_read    the plan and the programme's clock; code 6 while the option is off
+ *   elemhip_resample_reset   a new programme: time 0, silence in front of it; code 6 while the option is off */
+typedef struct elemhip_resample_info { uint32_t up, down, taps, latency_frames; uint64_t frames_in, frames_out; } elemhip_resample_info;
+int elemhip_resample_frames(elemhip_t*, size_t numFrames, size_t* out);
+int elemhip_resample_read(elemhip_t*, elemhip_resample_info* info);
+int elemhip_resample_reset(elemhip_t*);
+
 /* bool addSharedResource(name, unique_ptr<SharedResource>)       Runtime.h:83,461-465 (insert-only) */
 int    elemhip_add_shared_resource(elemhip_t*, const char* name, const float* const* channels, size_t nCh, size_t nSamples);
 /* void pruneSharedResources()                                    Runtime.h:89,467-471 */
@@ -276,7 +298,7 @@ int  elemhip_sum_buses(int deviceOrdinal, void* hipStream, float* dst, const flo
  * into pinned host memory), "use_graph" / "graph_blocks" (per-block launch path replayed from a hipGraph), "stateless_rows",
  * "mixer_split", "pipeline_copies", "merge_phases", "pack_islands" / "pack_max" / "cu_count" (lane-packing of isomorphic
  * islands), "event_history_blocks" / "capture_history_blocks" (above, at elemhip_event_window_blocks), "loudness_meter" (above, at
- * elemhip_loudness_read), "profile_launches", "time_batch". Unknown keys return code 6. */
+ * elemhip_loudness_read), "resample_rate" (above, at elemhip_resample_frames), "profile_launches", "time_batch". Unknown keys return code 6. */
 int  elemhip_set_option(elemhip_t*, const char* key, double value);
 
 #ifdef __cplusplus

@@ -146,6 +146,11 @@ public:
         return elemhip_loudness_read(h, info, meanSquares, capacity, truePeak, samplePeak);
     }
     int loudnessReset() { return elemhip_loudness_reset(h); }
+    // EXTENSION: delivery at another sample rate (setOption("resample_rate", hz)): the host-buffer render calls then fill
+    // resampleFrames(numFrames) frames
+    int resampleFrames(size_t numFrames, size_t* out) { return elemhip_resample_frames(h, numFrames, out); }
+    int resampleRead(elemhip_resample_info* info) { return elemhip_resample_read(h, info); }
+    int resampleReset() { return elemhip_resample_reset(h); }
     static int loudnessGate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
         return elemhip_loudness_gate(meanSquares, channels, subBlocks, weights, out);
     }
