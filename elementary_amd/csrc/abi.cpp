@@ -167,6 +167,19 @@ int elemhip_resample_read(elemhip_t* h, elemhip_resample_info* info) {
 
 int elemhip_resample_reset(elemhip_t* h) { return h ? h->engine.resampleReset() : elemhip::kInvalidInstructionFormat; }
 
+int elemhip_limiter_read(elemhip_t* h, elemhip_limiter_info* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    Engine::LimiterInfo li{};
+    const int rc = h->engine.limiterRead(&li, maxReduction, limitedFrames, capacity);
+    if (info && rc == elemhip::kOk) {
+        info->lookahead_frames = li.lookaheadFrames; info->latency_frames = li.latencyFrames; info->release_frames = li.releaseFrames;
+        info->link = li.link; info->groups = li.groups; info->reserved = 0u; info->frames = li.frames;
+    }
+    return rc;
+}
+
+int elemhip_limiter_reset(elemhip_t* h) { return h ? h->engine.limiterReset() : elemhip::kInvalidInstructionFormat; }
+
 int elemhip_loudness_gate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
     if (!out || (channels && subBlocks && !meanSquares)) return elemhip::kInvalidInstructionFormat;
     const loudness::Gated g = loudness::gate(meanSquares, channels, subBlocks, weights);

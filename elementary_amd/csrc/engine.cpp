@@ -189,6 +189,7 @@ Engine::~Engine() {
     if (dPcmInRowBase) (void)hipFree(dPcmInRowBase);
     loudnessFree();
     resampleFree();
+    limiterFree();
     if (ioStream) (void)hipStreamDestroy(ioStream);
     if (relayStream) { (void)hipStreamSynchronize(relayStream); (void)hipStreamDestroy(relayStream); }
     if (evRelay) (void)hipEventDestroy(evRelay);
@@ -526,6 +527,9 @@ int Engine::setOption(const std::string& key, double value) {
     // resample.h: the host-buffer render calls deliver at this rate (Hz, integral like the engine's; 0 or the engine's rate: off),
     // converted on the GPU behind every launch set. Setting it starts a new programme — the meter's too, at the delivery rate.
     if (key == "resample_rate") return setResampleRate(value);
+    // limiter.h: a static gain and a look-ahead true-peak limiter on what those calls deliver, behind the converter. Turning it on, or
+    // changing a parameter while it is on, starts a new programme; off (the default) not one launch, allocation or byte differs.
+    if (key.compare(0, 7, "limiter") == 0) return setLimiterOption(key, value);
     if (key == "batch_blocks") { batchBlocks = std::max(1, std::min(1024, (int)value)); return kOk; }      // blocks per multi-block launch (1 = off)
     if (key == "debug_build_delay_ms") { debugBuildDelayMs = std::max(0, (int)value); return kOk; }   // tests: stretches the unlocked part of a plan build
     if (key == "plan_cache") { planCache = std::max(0, std::min(2, (int)value)); islandCache.clear(); islandShapeCache.clear(); return kOk; }

@@ -28,6 +28,7 @@
 #include "jit.h"
 #include "loudness.h"
 #include "resample.h"
+#include "limiter.h"
 
 namespace elemhip {
 
@@ -254,6 +255,15 @@ public:
     int resampleFrames(size_t numFrames, size_t* out);       // frames the next host-buffer call of numFrames delivers (off: numFrames)
     int resampleRead(ResampleInfo* info);
     int resampleReset();
+    // Options "limiter" and "limiter_*" (limiter.h; off by default): a static gain and a look-ahead true-peak limiter on what the
+    // host-buffer render calls deliver, behind the converter and in front of the pack kernel and the meter (limiter.hip; the header's
+    // scalar loop where those calls render host block by host block). Frames in = frames out, delayed by latencyFrames. The programme
+    // is the frames those calls delivered since the option was turned on, a parameter changed or the last reset; its channel count is
+    // that of the first call (a multiple of `link`): a call with another count is refused. A call that fails starts a new programme.
+    struct LimiterInfo { uint32_t lookaheadFrames, latencyFrames, releaseFrames, link, groups; uint64_t frames; };
+    // maxReduction[group] (the largest d behind a delivered gain, 0 .. 1) / limitedFrames[group] (frames with g < 1): `capacity` entries each
+    int limiterRead(LimiterInfo* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity);
+    int limiterReset();
     // render `numBlocks` blocks with a HIP event pair around every kernel launch; msOut[l] = mean
     // duration of launch level l (l < numLevels), msOut[numLevels] = epilogue. Returns levels + 1.
     int timeLaunches(size_t nOut, size_t numBlocks, float* msOut, size_t cap);
@@ -436,6 +446,23 @@ private:
     int ensureResample(size_t channels, size_t outBlocksCap);   // (`mu` held, both streams idle)
     int resampleResetLocked(size_t channels);
     void resampleFree();
+    // the limiter (options "limiter", "limiter_*"): two copies of the carried state on the device (a set's kernels read one, its history
+    // step writes the other), the statistics, the per-set scratch and per half the limited set; the programme's clock on the host
+    bool limiterOn = false;
+    double limCeilingDb = -1.0, limGainDb = 0.0, limLookaheadMs = 1.5, limReleaseMs = 500.0, limLink = 0.0;
+    limiter::Plan limPlan{};
+    loudness::Plan limMeter{};             // the delivery rate's interpolator: the detector
+    unsigned char* dLimState[2] = {nullptr, nullptr}; size_t limStateCap = 0; int limCur = 0;
+    limiter::GroupStats* dLimStats = nullptr; size_t limStatsCap = 0;
+    double* dLimFrames = nullptr; double* dLimTiles = nullptr; size_t limFrameCap = 0, limTileCap = 0, limScratchGroups = 0;
+    float* dLim[2] = {nullptr, nullptr}; size_t limFloats = 0;
+    uint32_t limChannels = 0;              // channels of the programme (0: none yet)
+    uint64_t limFrames = 0;
+    int setLimiterOption(const std::string& key, double value);      // (`mu` held)
+    int limiterReplan(double rate, bool apply);                      // the plan at `rate` from the current parameters (`mu` held)
+    int ensureLimiter(size_t channels, size_t outBlocksCap, size_t setFrames);   // (`mu` held, both streams idle)
+    int limiterResetLocked(size_t channels);
+    void limiterFree();
     int growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], size_t& have, size_t want);
     int ensureRowTable(uint16_t*& dev, uint32_t& haveGroup, uint32_t& dwords, uint32_t group);
     // the set loop of processBlocksHost / processBlocksPcm (`pcm` null: planar floats only)

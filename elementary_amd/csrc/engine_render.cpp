@@ -1266,6 +1266,10 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
     // rate; the pack kernel's time (the dither's key) is then the programme's OUTPUT frame index
     const bool resamp = resampleOn && nOut > 0;
     const resample::Plan rp = resPlan;
+    // option "limiter": the delivered frames — converted or not — go through the gain and the limiter before they are packed, metered
+    // and copied; frames in = frames out, so neither the dither's key nor any count changes
+    const bool limit = limiterOn && nOut > 0;
+    const limiter::Plan lmp = limPlan;
     // whole HOST blocks, like the reference's block loop (a host block = hostBlockSize / blockSize engine blocks)
     const size_t hb = (size_t)hostBlockSize;
     bool tapSlices = hb % bs != 0;          // ragged slices (a host block that no k divides evenly): launch sets hold whole engine blocks
@@ -1303,12 +1307,36 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         };
         auto resFail = [&]() { if (resamp) { RenderGuard lock(*this); (void)resampleResetLocked(0); } };
         if (resamp) { const int rc = resSync(true); if (rc != kOk) return rc; }
+        // and so does the limiter's state: the header's scalar loop limits, the same bits
+        std::vector<unsigned char> limState;
+        std::vector<limiter::GroupStats> limStats;
+        std::vector<float> limOut;
+        auto limSync = [&](bool toHost) -> int {
+            RenderGuard lock(*this);
+            if (hipSetDevice(device) != hipSuccess) return kHipError;
+            if (toHost) {
+                const int rc = ensureLimiter(nOut, 0, 0);
+                if (rc != kOk) return rc;
+                limState.resize(limiter::state_bytes(lmp, (uint32_t)nOut)); limStats.resize(limiter::group_count(lmp, (uint32_t)nOut));
+            }
+            HIP_OK(hipStreamSynchronize(stream));
+            if (toHost) {
+                HIP_OK(hipMemcpy(limState.data(), dLimState[limCur], limState.size(), hipMemcpyDeviceToHost));
+                HIP_OK(hipMemcpy(limStats.data(), dLimStats, limStats.size() * sizeof(limiter::GroupStats), hipMemcpyDeviceToHost));
+            } else {
+                HIP_OK(hipMemcpy(dLimState[limCur], limState.data(), limState.size(), hipMemcpyHostToDevice));
+                HIP_OK(hipMemcpy(dLimStats, limStats.data(), limStats.size() * sizeof(limiter::GroupStats), hipMemcpyHostToDevice));
+            }
+            return kOk;
+        };
+        auto limFail = [&]() { if (limit) { RenderGuard lock(*this); (void)limiterResetLocked(0); } };
+        if (limit) { const int rc = limSync(true); if (rc != kOk) { resFail(); if (meter) (void)meterSync(false); return rc; } }
         size_t outOff = 0;                      // delivered frames of this call so far
         for (size_t f0 = 0; f0 < numFrames; f0 += hb) {
             const size_t nf = std::min(hb, numFrames - f0);
             for (size_t c = 0; c < nIn; ++c) ip[c] = src ? nullptr : in[c] + f0;
             for (size_t c = 0; c < nOut; ++c) op[c] = wantFloat ? out[c] + f0 : nullptr;
-            if (nf < hb || pcm || meter || resamp) {
+            if (nf < hb || pcm || meter || resamp || limit) {
                 // the last, partly filled host block is still a whole block to the engine (offline-renderer/index.ts:104-131: inputs
                 // padded with zeros, the frames beyond the caller's arrays dropped); a PCM call renders every host block here
                 tailOut.assign(nOut * hb, 0.0f);
@@ -1325,7 +1353,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 for (size_t c = 0; c < nIn; ++c) { std::memcpy(tailIn.data() + c * hb, in[c] + f0, nf * sizeof(float)); ip[c] = tailIn.data() + c * hb; }
             }
             const int rc = process(ip.data(), nIn, op.data(), nOut, hb, sampleTime + (int64_t)f0);
-            if (rc != kOk) { if (meter) (void)meterSync(false); resFail(); return rc; }
+            if (rc != kOk) { if (meter) (void)meterSync(false); resFail(); limFail(); return rc; }
             // what is delivered of this host block: its nf frames, or their conversion
             const float* got = tailOut.data();
             size_t gotStride = hb, nd = nf, at = f0;
@@ -1341,13 +1369,20 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 got = resOut.data(); at = outOff; gotTime = (int64_t)resFramesOut;
                 resFramesIn += nf; resFramesOut += nd;
             }
+            if (limit && nd) {
+                std::lock_guard<std::mutex> lock(mu);
+                limOut.resize(nOut * gotStride);
+                limiter::limiter_host(limMeter, lmp, (uint32_t)nOut, limState.data(), limStats.data(), got, gotStride, nd, limFrames, limOut.data(), gotStride);
+                got = limOut.data();
+                limFrames += nd;
+            }
             if (meter) {
                 std::lock_guard<std::mutex> lock(mu);
                 for (size_t c = 0; c < nOut; ++c)
                     loudness::meter_host(loudPlan, meterState[c], got + c * gotStride, nd, loudFrames, [&](double ms) { loudSeries[c].push_back(ms); });
                 loudFrames += nd;
             }
-            if ((nf < hb || pcm || meter || resamp) && wantFloat) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + at, got + c * gotStride, nd * sizeof(float));
+            if ((nf < hb || pcm || meter || resamp || limit) && wantFloat) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + at, got + c * gotStride, nd * sizeof(float));
             if (pcm) {
                 // the floats are on the host: the header's scalar loop packs them — the kernel's functions, the kernel's bits
                 for (size_t s = 0; s < pcm->nStreams; ++s) sp[s] = static_cast<uint8_t*>(pcm->streams[s]) + at * pcmG * pcmB;
@@ -1358,6 +1393,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         }
         int rc = meter ? meterSync(false) : kOk;
         if (resamp) { const int rr = resSync(false); if (rc == kOk) rc = rr; if (rc != kOk) resFail(); }
+        if (limit) { const int rl = limSync(false); if (rc == kOk) rc = rl; if (rc != kOk) limFail(); }
         return rc;
     }
     const size_t numBlocks = ((numFrames + hb - 1) / hb) * (hb / bs);
@@ -1378,6 +1414,10 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         if (rc != kOk) return rc;
         if (resamp) {
             rc = ensureResample(nOut, outCapBlocks);
+            if (rc != kOk) return rc;
+        }
+        if (limit) {
+            rc = ensureLimiter(nOut, outCapBlocks, outCapFrames);
             if (rc != kOk) return rc;
         }
         if (src) {
@@ -1535,6 +1575,20 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 resFramesIn += valid; resFramesOut += a.validOut;
                 valid = a.validOut; outOff += valid;
             }
+            if (limit && valid) {
+                // the limiter behind the converter, in front of the pack kernel and the meter, on the same stream: it reads one copy of
+                // its carried state, its history step writes the other. The limited half was drained by the D2H of set k - 2 (evOut above).
+                LimiterArgs a{};
+                a.src = got; a.dst = dLim[half]; a.stateIn = dLimState[limCur]; a.stateOut = dLimState[limCur ^ 1]; a.stats = dLimStats;
+                a.frames = dLimFrames; a.tiles = dLimTiles; a.n0 = limFrames;
+                a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nOut; a.validFrames = (uint32_t)valid;
+                a.outBlocks = (uint32_t)gotBlocks; a.outBlocksCap = (uint32_t)outCapBlocks; a.frameCap = (uint32_t)limFrameCap; a.tileCap = (uint32_t)limTileCap;
+                a.plan = lmp; a.meter = limMeter;
+                HOST_TRY(launch_limiter(stream, a));
+                limCur ^= 1;
+                got = dLim[half];
+                limFrames += valid;
+            }
             size_t pcmCopy = 0;
             if (pcm) {
                 // the pack kernel behind the set's last level, on the same stream: the output block is still warm in L2. Its packed
@@ -1594,6 +1648,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         // a metered call that failed may have advanced the carried state past sets whose sums never arrived: the programme starts anew
         if (meter && result != kOk) (void)loudnessResetLocked(loudChannels);
         if (resamp && result != kOk) (void)resampleResetLocked(0);      // likewise: the clock may be ahead of what was delivered
+        if (limit && result != kOk) (void)limiterResetLocked(0);
     }
     return result;
 }

@@ -18,6 +18,7 @@ int Engine::setResampleRate(double hz) {
     const bool on = hz != 0.0 && hz != sampleRate, was = resampleOn;
     resample::Plan plan{};
     if (on && !resample::make_plan(sampleRate, hz, plan)) return kInvalidPropertyValue;
+    if (limiterOn && limiterReplan(on ? hz : sampleRate, false) != kOk) return kInvalidPropertyValue;      // (no limiter plan at that rate: nothing changes)
     if (!dry) {
         if (hipSetDevice(device) != hipSuccess) return kHipError;
         HIP_OK(hipStreamSynchronize(stream));
@@ -39,6 +40,8 @@ int Engine::setResampleRate(double hz) {
     }
     // the meter meters what is delivered: its plan follows the delivery rate, whichever option was set first
     if (loudnessOn && !dry && (on || was)) { loudness::make_plan(deliveryRate(), loudPlan); const int rc = loudnessResetLocked(0); if (rc != kOk) return rc; }
+    // so does the limiter's: it limits what is delivered
+    if (limiterOn && (on || was)) { const int rc = limiterReplan(deliveryRate(), true); if (rc != kOk) return rc; }
     return kOk;
 }
 

@@ -5,6 +5,7 @@
 #include "pcm_pack.h"
 #include "loudness.h"
 #include "resample.h"
+#include "limiter.h"
 
 namespace elemhip {
 
@@ -116,6 +117,21 @@ struct ResampleArgs {
     resample::Plan  plan;
 };
 hipError_t launch_resample(hipStream_t s, const ResampleArgs& a);
+// ---- true-peak limiter (limiter.hip): behind the converter, in front of the pack kernel and the meter, limiter.h ----
+struct LimiterArgs {
+    const float*    src;            // the set's delivered frames, [block][numChannels][blockSize]: validFrames of them
+    float*          dst;            // [outBlocks][numChannels][blockSize]: the limited frames, zeros up to the last block's end
+    const unsigned char* stateIn;   // limiter::state_bytes: M | d | frames in front of the set
+    unsigned char*  stateOut;       // the other copy: receives the state in front of the NEXT set
+    limiter::GroupStats* stats;     // [groups], accumulated over the programme
+    double*         frames;         // [groups][frameCap] scratch: dm, then d
+    double*         tiles;          // [groups][tileCap] scratch: the tiles' maxima, then M in front of each tile
+    uint64_t        n0;             // the programme's frame index at the set's start
+    uint32_t        blockSize, numChannels, validFrames, outBlocks, outBlocksCap, frameCap, tileCap, pad;
+    limiter::Plan   plan;
+    loudness::Plan  meter;          // the delivery rate's: its interpolator is the detector
+};
+hipError_t launch_limiter(hipStream_t s, const LimiterArgs& a);
 hipError_t launch_bus_sum(hipStream_t s, float* dst, const float* const* partials, uint32_t count, size_t n);   // dst = ((p0 + p1) + p2) + ... (rank order)
 
 } // namespace elemhip

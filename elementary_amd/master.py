@@ -1,0 +1,70 @@
+"""``master_wav`` — a RIFF/WAVE file brought to a delivery spec ("-14 LUFS, -1 dBTP") on the GPU, in two passes over a pass-through
+graph: the first meters the input (BS.1770 integrated loudness and true peak), the second applies ``target - measured`` dB of static
+gain and the look-ahead true-peak limiter and meters what it writes. No sample is scaled or limited on the host."""
+from __future__ import annotations
+
+from typing import Any, Callable, Dict
+
+import numpy as np
+
+from . import el
+from .offline import OfflineRenderer
+from .wav import WavReader
+
+
+def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, target_lufs: float = -14.0, ceiling_dbtp: float = -1.0,
+               fmt: str = "s24", block_size: int = 512, **limiter) -> Dict[str, Any]:
+    """``in_path`` -> ``out_path`` (format ``fmt``, the input's rate and channel count) at ``target_lufs`` integrated loudness under a
+    true-peak ceiling of ``ceiling_dbtp``. ``limiter``: further limiter parameters (``lookahead_ms``, ``release_ms``, ``link``).
+    Returns ``{'input_lufs', 'input_true_peak_dbtp', 'output_lufs', 'output_true_peak_dbtp', 'gain_db', 'max_reduction_db',
+    'limited_frames', 'over', 'nonfinite'}``. Where the limiter worked the output is quieter than the target by what it took away; the
+    output's metered true peak may exceed the ceiling slightly (``OfflineRenderer.initialize``). An input that passes no loudness
+    gate (silence) raises ``ValueError``: there is no gain that brings it to a target.
+
+    Both passes meter on the same grid: the limiter delays its output by ``latency_frames``, so the first pass puts as many frames of
+    silence in front of the input — the second pass's figures then differ from the first's by the gain and the limiter alone."""
+    unknown = set(limiter) - {"lookahead_ms", "release_ms", "link"}
+    if unknown:
+        raise ValueError(f"unknown limiter parameters: {sorted(unknown)}")
+    with WavReader(str(in_path)) as r:
+        rate, channels, frames, in_fmt = float(r.sample_rate), int(r.channels), int(r.frames), r.fmt
+
+    def renderer(**kw):
+        core = OfflineRenderer(engine_factory)
+        core.initialize(num_input_channels=channels, num_output_channels=channels, sample_rate=rate, block_size=int(block_size),
+                        loudness_meter=True, **kw)
+        core.render(*[el.in_({"channel": c}) for c in range(channels)])
+        # the roots fade in over 20 ms of engine time: let that pass on silence, then start the meter's programme
+        warm = -(-int(0.05 * rate) // int(block_size)) * int(block_size)
+        core.process_pcm_io([silence(warm)], in_fmt, warm)
+        core.loudness_reset()
+        return core
+
+    def silence(n):
+        shape, dtype = {"s16": ((n, channels), np.int16), "s24": ((n, channels, 3), np.uint8)}.get(in_fmt, ((n, channels), np.float32))
+        return np.zeros(shape, dtype=dtype)
+
+    params = dict(limiter, ceiling_dbtp=float(ceiling_dbtp))
+    # the limiter's latency at this rate, from a plan of the same parameters
+    probe = renderer(limiter=dict(params, gain_db=0.0))
+    latency = probe.limiter()["latency_frames"]
+    del probe
+    first = renderer()
+    first.process_pcm_io([silence(latency)], in_fmt, latency)
+    with WavReader(str(in_path)) as r:
+        done = 0
+        while done < frames:
+            m = min(1 << 20, frames - done)
+            first.process_pcm_io([r.read(m)], in_fmt, m)
+            done += m
+    measured = first.loudness()
+    if not np.isfinite(measured["integrated_lufs"]):
+        raise ValueError("the input passes no loudness gate: no gain brings it to a target")
+    gain_db = float(target_lufs) - float(measured["integrated_lufs"])
+    second = renderer(limiter=dict(params, gain_db=gain_db))
+    stats = second.process_wav(str(in_path), str(out_path), fmt)
+    lim = second.limiter()
+    return {"input_lufs": float(measured["integrated_lufs"]), "input_true_peak_dbtp": float(measured["true_peak_dbtp"]),
+            "output_lufs": float(stats["integrated_lufs"]), "output_true_peak_dbtp": float(stats["true_peak_dbtp"]), "gain_db": gain_db,
+            "max_reduction_db": float(lim["max_reduction_db"]), "max_reduction": float(np.max(lim["max_reduction"], initial=0.0)),
+            "limited_frames": int(np.sum(lim["limited_frames"])), "over": int(np.sum(stats["over"])), "nonfinite": int(np.sum(stats["nonfinite"]))}

@@ -22,7 +22,7 @@ class OfflineRenderer:
     def initialize(self, num_input_channels: int = 0, num_output_channels: int = 2, sample_rate: float = 44100,
                    block_size: int = 512, virtual_file_system: Optional[Dict[str, np.ndarray]] = None,
                    event_history_blocks: int = 0, capture_history_blocks: int = 0, loudness_meter: bool = False,
-                   output_sample_rate: Optional[float] = None) -> None:
+                   output_sample_rate: Optional[float] = None, limiter=None) -> None:
         """``event_history_blocks`` (no counterpart in the reference; 0 = off): engine option of the same name — `scope` and `fft`
         nodes keep a device ring long enough for a relay window of that many blocks, so ``process`` still renders launch sets of
         that size with such a listener attached (engines without ``set_option`` relay after every block anyway).
@@ -35,7 +35,14 @@ class OfflineRenderer:
         ``sample_rate`` and ``process`` (whose output buffers then hold the DELIVERED frames: ``ceil(rendered * up / down)`` of them),
         ``process_pcm`` and ``process_pcm_io`` deliver at this rate, converted on the GPU by a windowed-sinc filter whose latency is
         ``resample()['latency_frames']`` output frames; ``write_wav`` and ``process_wav`` write files at this rate with that latency
-        taken out. Rendering at 4 x 44100 and delivering 44100 is oversampling. An engine without the option raises ``RuntimeError``."""
+        taken out. Rendering at 4 x 44100 and delivering 44100 is oversampling. An engine without the option raises ``RuntimeError``.
+        ``limiter`` (likewise; None or False: off): ``True`` for the defaults or a dict with any of ``ceiling_dbtp`` (-1), ``gain_db``
+        (0), ``lookahead_ms`` (1.5), ``release_ms`` (500) and ``link`` (channels per linked group; 0: all) — engine options ``limiter``
+        and ``limiter_*``: a static gain and a look-ahead true-peak limiter on the GPU on everything ``process`` (in engine calls of
+        many blocks), ``process_pcm`` and ``process_pcm_io`` deliver, behind the converter and in front of the PCM packing and the
+        meter, with a latency of ``limiter()['latency_frames']`` delivered frames; ``write_wav`` and ``process_wav`` take that latency
+        out. The delivered sample peak stays under the ceiling; the metered true peak of the output may exceed it slightly (about
+        0.1 dB at a look-ahead of one frame, 0.004 dB at 66). An engine without the option raises ``RuntimeError``."""
         self.num_in = int(num_input_channels)
         self.num_out = int(num_output_channels)
         self.block_size = int(block_size)
@@ -58,6 +65,20 @@ class OfflineRenderer:
             except RuntimeError as e:
                 raise RuntimeError(f"this engine cannot deliver {self.sample_rate:g} Hz renders at {float(output_sample_rate):g} Hz") from e
             self.output_sample_rate = float(output_sample_rate)
+        self._limiter = limiter is not None and limiter is not False
+        if self._limiter:
+            if not hasattr(self._rt, "set_option") or not hasattr(self._rt, "limiter_read"):
+                raise RuntimeError("this engine has no limiter (option limiter)")
+            params = {} if limiter is True else dict(limiter)
+            unknown = set(params) - {"ceiling_dbtp", "gain_db", "lookahead_ms", "release_ms", "link"}
+            if unknown:
+                raise ValueError(f"unknown limiter parameters: {sorted(unknown)}")
+            try:
+                for k, v in params.items():
+                    self._rt.set_option("limiter_" + k, float(v))
+                self._rt.set_option("limiter", 1)
+            except RuntimeError as e:
+                raise RuntimeError(f"this engine cannot limit with {params} at {self.output_sample_rate:g} Hz") from e
         self._time = 0
         for k, v in (virtual_file_system or {}).items():
             self._rt.add_shared_resource(k, v)
@@ -80,6 +101,9 @@ class OfflineRenderer:
         return self._rt.renderer.create_ref(kind, props, children)
 
     def process(self, inputs: Sequence[np.ndarray], outputs: Sequence[np.ndarray]) -> None:
+        """The reference's block loop. With ``initialize(limiter=...)`` the buffers hold the LIMITED frames, the limiter's latency
+        included: frame n is the gained and limited render at n - latency_frames, silence first (renders longer than one block only;
+        an engine without ``process_blocks_host`` cannot limit)."""
         if len(inputs) != self.num_in:
             raise ValueError(f"Invalid input data; expected {self.num_in} buffers.")
         if len(outputs) != self.num_out:
@@ -94,7 +118,7 @@ class OfflineRenderer:
             # the output buffers hold DELIVERED frames: render the inputs' length, or — without inputs — what fills the buffers
             info = self._rt.resample_read()
             total = max([len(b) for b in inputs], default=-((-total * info["down"]) // info["up"]))
-        if host_batch is not None and window is not None and any(self._listeners.values()) and (total > bs or self._resample):
+        if host_batch is not None and window is not None and any(self._listeners.values()) and (total > bs or self._resample or self._limiter):
             # listeners to serve: the reference relays events after EVERY block (index.ts:112-122). The engine keeps per-block readout
             # logs, so the block loop still runs as launch sets — `event_window_blocks()` blocks per engine call (1024 with meters and
             # snapshots only, fewer with a scope ring, one with a capture node made without history) — and the BLOCKWISE relay after each call hands the
@@ -120,7 +144,7 @@ class OfflineRenderer:
                         buf[at:at + mm] = y[i, :mm]
                 at += y.shape[1]
             return
-        if host_batch is not None and not any(self._listeners.values()) and (total > bs or self._resample):
+        if host_batch is not None and not any(self._listeners.values()) and (total > bs or self._resample or self._limiter):
             # no event listeners to serve between blocks: the whole block loop in one engine call
             # (elemhip_process_blocks_host: launch sets staged through pinned double buffers); the event queues are drained
             # once afterwards, as the per-block loop's relay (index.ts:118-122) would have kept them drained — a listener
@@ -140,6 +164,8 @@ class OfflineRenderer:
             return
         if self._resample:
             raise RuntimeError("this engine cannot deliver at another sample rate (no process_blocks_host)")
+        if self._limiter and host_batch is None:
+            raise RuntimeError("this engine cannot limit (no process_blocks_host)")
         for k in range(0, total, bs):
             block_in = None
             if self.num_in:
@@ -162,7 +188,8 @@ class OfflineRenderer:
         """``process`` delivered as interleaved PCM packed on the GPU (``Runtime.process_blocks_pcm``, same arguments apart from the
         engine): returns ``(streams, stats, planar)``. With listeners attached the render walks ``event_window_blocks()`` windows
         with the blockwise relay between them, as ``process`` does; every window is packed at its absolute time, so the bytes are
-        those of one call."""
+        those of one call. With ``initialize(limiter=...)`` the streams hold the limited frames with the limiter's latency in them:
+        frame n is the limited render at n - latency_frames."""
         if len(inputs) != self.num_in:
             raise ValueError(f"Invalid input data; expected {self.num_in} buffers.")
         if int(num_streams) * int(channels_per_stream) != self.num_out:
@@ -231,15 +258,37 @@ class OfflineRenderer:
         """A new programme for the converter: time 0, silence in front of it."""
         self._rt.resample_reset()
 
+    def limiter(self) -> Dict[str, Any]:
+        """The limiter's plan and statistics (``initialize(limiter=...)``): ``{'lookahead_frames', 'latency_frames', 'release_frames',
+        'link', 'groups', 'frames', 'max_reduction', 'limited_frames'}`` — the last two one per linked group — and
+        ``'max_reduction_db'``, the deepest gain reduction of any group in dB (0.0: never limited)."""
+        if not getattr(self, "_limiter", False):
+            raise RuntimeError("the limiter is off: initialize(limiter=...)")
+        got = self._rt.limiter_read()
+        worst = float(np.max(got["max_reduction"], initial=0.0))
+        got["max_reduction_db"] = 0.0 if worst <= 0.0 else float("inf") if worst >= 1.0 else -20.0 * float(np.log10(1.0 - worst))
+        return got
+
+    def limiter_reset(self) -> None:
+        """A new programme for the limiter: frame 0, silence in front of it, statistics zero."""
+        self._rt.limiter_reset()
+
     def _file_span(self, num_frames: int):
-        """A file of a converted render: (frames to render, delivered frames to drop in front, frames the file holds). The filter's
-        latency Do is taken out, so frame n of the file is the render at time n * down / up: ceil(Do down / up) further frames are
-        rendered, the first Do delivered frames dropped, ceil(num_frames up / down) kept. A new programme starts."""
-        if not self._resample:
+        """A file of a converted and / or limited render: (frames to render, delivered frames to drop in front, frames the file
+        holds). The converter's latency Do and the limiter's D + 6, both in delivered frames, are taken out together, so frame n of
+        the file is the (limited) render at time n * down / up: ceil((Do + D + 6) down / up) further frames are rendered, the first
+        Do + D + 6 delivered frames dropped, ceil(num_frames up / down) kept. New programmes start."""
+        limiting = getattr(self, "_limiter", False)
+        if not self._resample and not limiting:
             return int(num_frames), 0, int(num_frames)
-        self._rt.resample_reset()
-        info = self._rt.resample_read()
-        up, down, lat = info["up"], info["down"], info["latency_frames"]
+        up, down, lat = 1, 1, 0
+        if self._resample:
+            self._rt.resample_reset()
+            info = self._rt.resample_read()
+            up, down, lat = info["up"], info["down"], info["latency_frames"]
+        if limiting:
+            self._rt.limiter_reset()
+            lat += self._rt.limiter_read()["latency_frames"]
         return int(num_frames) + -((-lat * down) // up), lat, -((-int(num_frames) * up) // down)
 
     def loudness_reset(self) -> None:
@@ -250,6 +299,8 @@ class OfflineRenderer:
         if self._loudness and stats is not None:
             got = self.loudness()
             stats = dict(stats, integrated_lufs=got["integrated_lufs"], true_peak_dbtp=got["true_peak_dbtp"])
+        if getattr(self, "_limiter", False) and stats is not None:
+            stats = dict(stats, limiter_max_reduction_db=self.limiter()["max_reduction_db"])
         return stats
 
     def write_wav(self, path, inputs: Sequence[np.ndarray], num_frames: int, fmt="s16", channels_per_stream: Optional[int] = None,
@@ -258,7 +309,7 @@ class OfflineRenderer:
         stream of ``channels_per_stream`` channels (default: all output channels in one file). ``path``: the file's name, or — for
         more than one stream — a list of names or a name with ``{}`` for the stream number. Returns the statistics of the render; with the loudness
         meter on they carry ``integrated_lufs`` and ``true_peak_dbtp`` as well — ``loudness()`` of the meter's programme so far (call
-        ``loudness_reset()`` first for figures of this file alone)."""
+        ``loudness_reset()`` first for figures of this file alone); with the limiter on, ``limiter_max_reduction_db`` of this file."""
         from .wav import WavWriter
         G = self.num_out if channels_per_stream is None else int(channels_per_stream)
         S = self.num_out // max(G, 1)
@@ -303,7 +354,9 @@ class OfflineRenderer:
         ``in_streams`` are arrays in stream layout (``WavReader.read``, or what ``process_pcm`` returns) that together hold the
         ``num_input_channels`` input channels; a stream shorter than ``num_frames`` is padded with silence. ``out_fmt`` None: returns
         float32 ``[num_output_channels, num_frames]``; else ``(streams, stats, planar)`` as ``process_pcm`` does. With listeners attached
-        the render walks ``event_window_blocks()`` windows with the blockwise relay between them, as ``process`` does."""
+        the render walks ``event_window_blocks()`` windows with the blockwise relay between them, as ``process`` does. With
+        ``initialize(limiter=...)`` what comes back is limited and carries the limiter's latency: frame n is the limited render at
+        n - latency_frames."""
         pcm_io = getattr(self._rt, "process_blocks_pcm_io", None)
         if pcm_io is None:
             raise RuntimeError("this engine takes no PCM input (process_blocks_pcm_io)")
@@ -351,7 +404,8 @@ class OfflineRenderer:
         the files' channels become the input channels in file order (files of one format, one channel count and the renderer's
         sample rate). ``out_paths`` / ``channels_per_stream``: as ``write_wav``'s ``path``. ``num_frames``: frames to render, default
         the (longest) input's length; longer than that — a reverb's tail — renders the rest from silence. Returns the statistics
-        (with the loudness meter on: ``integrated_lufs`` and ``true_peak_dbtp`` of the meter's programme so far included, as ``write_wav``)."""
+        (with the loudness meter on: ``integrated_lufs`` and ``true_peak_dbtp`` of the meter's programme so far included, as ``write_wav``;
+        with the limiter on: ``limiter_max_reduction_db`` of this file)."""
         from .wav import WavReader, WavWriter
         ins = [str(in_paths)] if isinstance(in_paths, (str, bytes)) or hasattr(in_paths, "__fspath__") else [str(p) for p in in_paths]
         G = self.num_out if channels_per_stream is None else int(channels_per_stream)

@@ -78,6 +78,10 @@ def load_library() -> C.CDLL:
         lib.elemhip_resample_read.restype = C.c_int
         lib.elemhip_resample_reset.argtypes = [C.c_void_p]
         lib.elemhip_resample_reset.restype = C.c_int
+        lib.elemhip_limiter_read.argtypes = [C.c_void_p, C.POINTER(_LimiterInfo), _dp, C.POINTER(C.c_uint64), C.c_size_t]
+        lib.elemhip_limiter_read.restype = C.c_int
+        lib.elemhip_limiter_reset.argtypes = [C.c_void_p]
+        lib.elemhip_limiter_reset.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -101,6 +105,11 @@ class _LoudnessInfo(C.Structure):
 class _ResampleInfo(C.Structure):
     _fields_ = [("up", C.c_uint32), ("down", C.c_uint32), ("taps", C.c_uint32), ("latency_frames", C.c_uint32),
                 ("frames_in", C.c_uint64), ("frames_out", C.c_uint64)]
+
+
+class _LimiterInfo(C.Structure):
+    _fields_ = [("lookahead_frames", C.c_uint32), ("latency_frames", C.c_uint32), ("release_frames", C.c_uint32), ("link", C.c_uint32),
+                ("groups", C.c_uint32), ("reserved", C.c_uint32), ("frames", C.c_uint64)]
 
 
 class _LoudnessResult(C.Structure):
@@ -370,6 +379,34 @@ class Runtime(CRuntime):
         rc = self._lib.elemhip_resample_reset(self._h)
         if rc != 0:
             err = ElemHipError(f"elemhip_resample_reset failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+
+    def limiter_read(self) -> Dict[str, Any]:
+        """``elemhip_limiter_read`` (option ``limiter``): the plan — ``lookahead_frames`` D, ``latency_frames`` D + 6,
+        ``release_frames``, ``link`` (channels per linked group; 0: all), ``groups`` (0 before the programme's first call) — the
+        programme's ``frames`` and, per group, ``max_reduction`` (float64: the largest reduction behind a delivered gain, 0 .. 1) and
+        ``limited_frames`` (uint64: frames delivered with a gain below 1)."""
+        import numpy as np
+        info = _LimiterInfo()
+        rc = self._lib.elemhip_limiter_read(self._h, C.byref(info), None, None, 0)
+        groups = int(info.groups)
+        red, lim = np.zeros(groups, dtype=np.float64), np.zeros(groups, dtype=np.uint64)
+        if rc == 0 and groups:
+            rc = self._lib.elemhip_limiter_read(self._h, C.byref(info), red.ctypes.data_as(C.POINTER(C.c_double)), lim.ctypes.data_as(C.POINTER(C.c_uint64)), groups)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_limiter_read failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        got = {k: int(getattr(info, k)) for k, _ in _LimiterInfo._fields_ if k != "reserved"}
+        got["max_reduction"], got["limited_frames"] = red, lim
+        return got
+
+    def limiter_reset(self) -> None:
+        """``elemhip_limiter_reset``: a new programme (frame 0, silence in front of it, statistics zero)."""
+        rc = self._lib.elemhip_limiter_reset(self._h)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_limiter_reset failed: {describe(rc)} (code {rc})")
             err.code = rc
             raise err
 

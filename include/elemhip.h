@@ -193,6 +193,27 @@ int elemhip_resample_frames(elemhip_t*, size_t numFrames, size_t* out);
 int elemhip_resample_read(elemhip_t*, elemhip_resample_info* info);
 int elemhip_resample_reset(elemhip_t*);
 
+/* EXTENSION (no counterpart in the reference): a static gain and a look-ahead true-peak limiter on the GPU (elementary_amd/csrc/limiter.hip;
+ * the arithmetic: limiter.h). After elemhip_set_option(h, "limiter", 1) what elemhip_process_blocks_host, elemhip_process_blocks_pcm and
+ * elemhip_process_blocks_pcm_io deliver — planar floats, packed streams, what the loudness meter meters — has passed, behind the
+ * delivery-rate converter, through y[n] = g[n] G x[n - D - 6]: G = 10^(limiter_gain_db / 20), D = round(limiter_lookahead_ms * rate /
+ * 1000) with 1 <= D <= 1024, and a gain g <= 1 per group of "limiter_link" consecutive channels (0: all) that holds the 4x-interpolated
+ * peak of G x (the meter's interpolator) under C = 10^(limiter_ceiling_dbtp / 20): the reduction each peak asks for, held over D + 7
+ * frames, released linearly in gain over limiter_release_ms for a full-scale reduction, smoothed by a mean over D + 1 frames. Frames
+ * in = frames out; latency_frames = D + 6 frames of silence come first. The delivered SAMPLE peak stays under C; the metered true peak
+ * of the output may exceed it slightly (the gain moves inside the interpolator's span: about 0.1 dB at D = 1, 0.004 dB at D = 66).
+ * The programme — the frames those calls delivered, in call order, since the option was turned on, a parameter changed while it is on,
+ * "resample_rate" was set or elemhip_limiter_reset — is limited the same however it is cut into calls and launch sets: the same bytes.
+ * Its channel count is that of its first call and a multiple of limiter_link, else code 6; a call that fails starts a new programme.
+ * Parameters (code 6 outside their range, or where they leave no plan at the delivery rate): limiter_ceiling_dbtp -40 .. 0 (-1),
+ * limiter_gain_db -60 .. 60 (0), limiter_lookahead_ms (1.5), limiter_release_ms (500; at least one frame), limiter_link (0).
+ *   elemhip_limiter_read   the plan and the programme's frame count; per group (`capacity` entries each, either may be null) the largest
+ *                          reduction d behind a delivered gain (0 .. 1) and the frames with g < 1; code 6 while the option is off
+ *   elemhip_limiter_reset  a new programme: frame 0, silence in front of it, statistics zero; code 6 while the option is off */
+typedef struct elemhip_limiter_info { uint32_t lookahead_frames, latency_frames, release_frames, link, groups, reserved; uint64_t frames; } elemhip_limiter_info;
+int elemhip_limiter_read(elemhip_t*, elemhip_limiter_info* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity);
+int elemhip_limiter_reset(elemhip_t*);
+
 /* bool addSharedResource(name, unique_ptr<SharedResource>)       Runtime.h:83,461-465 (insert-only) */
 int    elemhip_add_shared_resource(elemhip_t*, const char* name, const float* const* channels, size_t nCh, size_t nSamples);
 /* void pruneSharedResources()                                    Runtime.h:89,467-471 */
@@ -298,7 +319,8 @@ int  elemhip_sum_buses(int deviceOrdinal, void* hipStream, float* dst, const flo
  * into pinned host memory), "use_graph" / "graph_blocks" (per-block launch path replayed from a hipGraph), "stateless_rows",
  * "mixer_split", "pipeline_copies", "merge_phases", "pack_islands" / "pack_max" / "cu_count" (lane-packing of isomorphic
  * islands), "event_history_blocks" / "capture_history_blocks" (above, at elemhip_event_window_blocks), "loudness_meter" (above, at
- * elemhip_loudness_read), "resample_rate" (above, at elemhip_resample_frames), "profile_launches", "time_batch". Unknown keys return code 6. */
+ * elemhip_loudness_read), "resample_rate" (above, at elemhip_resample_frames), "limiter" /
+ * "limiter_*" (above, at elemhip_limiter_read), "profile_launches", "time_batch". Unknown keys return code 6. */
 int  elemhip_set_option(elemhip_t*, const char* key, double value);
 
 #ifdef __cplusplus

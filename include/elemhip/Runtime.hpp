@@ -151,6 +151,11 @@ public:
     int resampleFrames(size_t numFrames, size_t* out) { return elemhip_resample_frames(h, numFrames, out); }
     int resampleRead(elemhip_resample_info* info) { return elemhip_resample_read(h, info); }
     int resampleReset() { return elemhip_resample_reset(h); }
+    // EXTENSION: gain and true-peak limiter on what the host-buffer render calls deliver (setOption("limiter", 1), "limiter_*")
+    int limiterRead(elemhip_limiter_info* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity) {
+        return elemhip_limiter_read(h, info, maxReduction, limitedFrames, capacity);
+    }
+    int limiterReset() { return elemhip_limiter_reset(h); }
     static int loudnessGate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
         return elemhip_loudness_gate(meanSquares, channels, subBlocks, weights, out);
     }
