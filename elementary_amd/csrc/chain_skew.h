@@ -6,18 +6,20 @@
 // the four lanes of a quad hold the group's 16 frames between them, and ONE 16-byte store per lane writes the group where
 // the unskewed loop issues four (a store costs the lone recurrence wave per INSTRUCTION, not per byte or per lane).
 //
-//   step of the block    0 ........ n-1 | n .. n+11
-//   skew 0               frames 0 .. n-1 | holds
-//   skew k               holds for 4k steps (head), then frames 0 .. n-1, the last 4k of them in the tail
+//   step of the block    0 ........ n-1
+//   skew 0               frames 0 .. n-1
+//   skew k               holds for 4k steps (head), then frames 0 .. n-1-4k
 //
-// Head: in group 0 a lane of skew k sits out the first 4k steps (its state is the block's initial state). Tail: after the
-// last group it runs 4k more steps, so that every lane of a quad ends the block with the member's final state. The operands
-// of step s are loaded per lane, 16 bytes at a time, 16k bytes in front of the unskewed address; in the head and the tail
-// that address is clamped into the operand's block buffer (what a clamped load returns is never used: its steps are the ones
-// the predicates switch off).
+// Head: in group 0 a lane of skew k sits out the first 4k steps (its state is the block's initial state). The operands of
+// step s are loaded per lane, 16 bytes at a time, 16k bytes in front of the unskewed address; in the head that address is
+// clamped into the operand's block buffer (what a clamped load returns is never used: its steps are the ones the predicate
+// switches off). After the last group every frame is stored and the lane of skew 0 holds the member's final state: every
+// lane takes the state registers of state_lane(lane), the first lane of its quad. (Until r08 the lanes of skew k ran 4k more
+// predicated steps there, the tail, on three more clamped loads per operand, to arrive at the same bits; kTailSteps and
+// tail_active describe that schedule, and tests/native/chain_skew_host.cpp still emulates it as the reference for this one.)
 //
-// Written as plain index arithmetic for host and device alike: tests/native/chain_skew_host.cpp emulates the loop with these
-// functions and checks frames, final states and load offsets without a GPU.
+// Written as plain index arithmetic for host and device alike: tests/native/chain_skew_host.cpp and chain_carry_host.cpp
+// emulate the loop with these functions and check frames, final states and load offsets without a GPU.
 #ifndef ELEMHIP_CHAIN_SKEW_H
 #define ELEMHIP_CHAIN_SKEW_H
 #ifndef __HIPCC_RTC__        // (the run-time compiler has no host headers: jit.cpp declares the fixed-width names)
@@ -35,7 +37,7 @@ namespace chain_skew {
 constexpr uint32_t kGroup = 16;        // frames per group (chain_loop_d CHG)
 constexpr uint32_t kQuad = 4;          // lanes per member = frames per 16-byte piece
 constexpr uint32_t kMaxCount = 16;     // members of a task that fit a 64-lane wave
-constexpr uint32_t kTailSteps = 12;    // steps after the last group (skew 3 runs all of them)
+constexpr uint32_t kTailSteps = 12;    // steps of the former tail (skew 3 ran all of them)
 
 // the task shapes the schedule covers
 CSKEW_FD bool applies(uint32_t count) { return count >= 1u && count <= kMaxCount; }
@@ -56,12 +58,15 @@ CSKEW_FD uint32_t store_bias(uint32_t k) { return 4u * ((kGroup - kQuad) - kQuad
 
 // head: does a lane of skew k execute step j (0 .. 15) of group 0?
 CSKEW_FD bool head_active(uint32_t k, uint32_t j) { return j >= kQuad * k; }
-// tail: does it execute step j (0 .. 11) after the last group?
+// the former tail: the steps j (0 .. 11) after the last group that a lane of skew k was still short of. Skew 0: none.
 CSKEW_FD bool tail_active(uint32_t k, uint32_t j) { return j < kQuad * k; }
+// after the last group: the lane whose state registers a lane takes (a mirror quad is four copies of one state)
+CSKEW_FD uint32_t state_lane(uint32_t lane) { return lane - lane % kQuad; }
+constexpr int kStateQuadPerm = 0x00;   // the DPP control that reads state_lane: quad_perm:[0,0,0,0]
 
 // Byte offset, inside the operand's block buffer of n frames, of the 16-byte piece q (0 .. 3) of group g that a lane of skew k
-// loads: frames 16g + 4q - 4k .. +3. Group n / 16 is the tail's. Clamped into [0, 4n - 16]; only head (g = 0) and tail pieces
-// ever hit a bound, and exactly those whose steps head_active / tail_active switch off.
+// loads: frames 16g + 4q - 4k .. +3. Clamped into [0, 4n - 16]; only head pieces (g = 0) ever hit a bound, and exactly those
+// whose steps head_active switches off. (Group n / 16 was the former tail's, clamped at the upper bound.)
 CSKEW_FD uint32_t load_offset(uint32_t g, uint32_t q, uint32_t k, uint32_t n) {
     return 4u * (kGroup * g + kQuad * q) < 16u * k ? 0u
          : (4u * (kGroup * g + kQuad * q) - 16u * k > 4u * n - 16u ? 4u * n - 16u : 4u * (kGroup * g + kQuad * q) - 16u * k);

@@ -1196,6 +1196,21 @@ __device__ __forceinline__ void sout_put(const SOut& o, uint32_t t, float y) {  
     if (o.isG) ((gfp)((char __attribute__((address_space(1)))*)o.arena + o.goff))[t] = y; else lds[o.lds + t] = y;
 }
 
+// A recurrence's step together with the registers it carries from frame to frame. The step lambda captures them by reference;
+// `each(g)` calls g(reg) for every one of them, so that a loop can move the state between lanes (chain_loop_q does, behind the
+// last group of a block). The other loops only call the step.
+template <typename F, typename E>
+struct ChainStep {
+    F f; E each;
+    template <int N> __device__ __forceinline__ float operator()(const float (&x)[N]) { return f(x); }
+};
+template <typename F, typename E>
+__device__ __forceinline__ ChainStep<F, E> chain_step(F f, E each) { return ChainStep<F, E>{f, each}; }
+template <typename T> struct IsChainStep { static constexpr bool value = false; };
+template <typename F, typename E> struct IsChainStep<ChainStep<F, E>> { static constexpr bool value = true; };
+template <typename T> struct IsChainStep<T&> : IsChainStep<T> {};
+template <typename T> struct IsChainStep<const T> : IsChainStep<T> {};
+
 // Chunked chain with the broadcast-cell mask CM known at compile time: cell operands are plain
 // loop-invariant scalars (no loads, no register copies), buffer operands are streamed with two
 // ds_read_b128 per 8 frames, one chunk ahead of the dependent arithmetic (ping-pong registers).
@@ -1269,12 +1284,19 @@ __device__ __forceinline__ void chain_store_piece_lds(const v4f_& a, uint32_t ad
                  : "v"(a), "v"(addr), "s"(mask), "i"(OFF)
                  : "memory");
 }
+// every lane takes the register of chain_skew::state_lane(lane), its quad's first lane (one v_mov_b32 with a DPP quad permute; all
+// 64 lanes are enabled)
+__device__ __forceinline__ void quad_first(uint32_t& v) { v = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, chain_skew::kStateQuadPerm, 0xF, 0xF, false); }
+__device__ __forceinline__ void quad_first(float& v) { uint32_t u = f2u(v); quad_first(u); v = u2f(u); }
+
 // Taken by chain_loop_d when the task is laid out in quads, every streamed operand comes from the arena and the block is the
 // kernel's own (a multiple of the span). Per lane the instruction stream of a steady group is the unskewed loop's minus three of
-// its four stores; the lane's skew lives in its VGPR offsets alone. Group 0 of a block (the head) and the up to 12 steps behind the
-// last group (the tail) are peeled: their steps are predicated per lane, their loads clamped into the operand's block buffer —
-// global loads are not range-checked by anything. The last span issues only the tail's loads (three pieces per operand) where the
-// unskewed loop re-reads a whole span that nothing uses.
+// its four stores; the lane's skew lives in its VGPR offsets alone. Group 0 of a block (the head) is peeled: its steps are
+// predicated per lane, its loads clamped into the operand's block buffer — global loads are not range-checked by anything. Behind
+// the last group every frame of the block is stored and the lane of skew 0 holds the member's final state; the three lagging lanes
+// of its quad take that state from it (quad_first) where they used to run up to 12 more predicated steps on three more clamped
+// loads per operand (~50 issue slots and 3 memory instructions per block of the lone wave, for bits the quad already held). The
+// last span issues no loads at all.
 template <int NIN, uint32_t CM, int DEPTH, typename Step>
 __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut out, Step&& step) {
     constexpr int NS0 = NIN - __builtin_popcount(CM & ((1u << NIN) - 1u));
@@ -1294,7 +1316,7 @@ __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut ou
 #define CHAIN_OPAQUE_OFFSETS() do { asm volatile("" : "+v"(ooff)); _Pragma("unroll") for (int k_ = 0; k_ < NIN; ++k_) asm volatile("" : "+v"(ioff[k_])); } while (0)
     const unsigned long long smask = chain_skew::store_mask(out.cnt);
     typedef const char __attribute__((address_space(1)))* gccp;
-    // a steady group: D-th of the span at byte offset soff of the block (never group 0, never the tail's)
+    // a steady group: D-th of the span at byte offset soff of the block (never group 0)
     auto load = [&](uint32_t soff, auto Dc, float (&x)[NS][CHG]) {
         constexpr int D = decltype(Dc)::value;
         int s_ = 0;
@@ -1310,7 +1332,7 @@ __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut ou
             }
         }
     };
-    // group G (0: the head's, n / 16: the tail's), pieces [0, NQ): every piece at its own clamped offset
+    // group G (0: the head's), pieces [0, NQ): every piece at its own clamped offset
     auto load_edge = [&](uint32_t G, auto NQc, float (&x)[NS][CHG]) {
         constexpr int NQ = decltype(NQc)::value;
         int s_ = 0;
@@ -1372,10 +1394,7 @@ __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut ou
         static_for<0, DEPTH>([&](auto Dc) {
             constexpr int D = decltype(Dc)::value;
             run(X[D], soff, Dc, IntC<(HEAD && D == 0) ? 1 : 0>{});
-            if constexpr (NS0 > 0) {
-                if constexpr (!LAST) load(soff + span * 4u, Dc, X[D]);
-                else if constexpr (D == 0) load_edge(n / (uint32_t)CHG, IntC<(int)chain_skew::kTailSteps / 4>{}, X[0]);
-            }
+            if constexpr (NS0 > 0 && !LAST) load(soff + span * 4u, Dc, X[D]);
         });
     };
     constexpr int NSPAN = (int)(n / span);
@@ -1393,14 +1412,11 @@ __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut ou
         for (uint32_t t0 = span; t0 + span < n; t0 += span) span_body(t0 * 4u, IntC<0>{}, IntC<0>{});
         span_body((n - span) * 4u, IntC<0>{}, IntC<1>{});
     }
-    // TAIL: the lanes of skew k catch up their last 4k frames (nothing is stored: every frame of the block already is)
-    wait_group(X[0], IntC<(int)chain_skew::kTailSteps>{});
-#pragma unroll
-    for (int j = 0; j < (int)chain_skew::kTailSteps; ++j) {
-        float xs[NIN];
-        operands(X[0], j, xs);
-        if (chain_skew::tail_active(skew, (uint32_t)j)) (void)step(xs);
-    }
+    // No tail: the lane of skew 0 has none to run (it stepped frame n - 1 in the last group), so it holds the member's final state,
+    // and the lanes of skew k take it from there where they would step their last 4k frames to the same bits. A mirror lane's quad
+    // is four unskewed copies of the last member: it reads its own value back.
+    static_assert(!chain_skew::tail_active(0u, 0u), "skew 0 ends the last group with the final state");
+    step.each([](auto& s) { quad_first(s); });
 #undef CHAIN_OPAQUE_OFFSETS
 }
 // DEPTH = groups in flight per streamed operand (16 VGPRs each).
@@ -1417,7 +1433,8 @@ __device__ __forceinline__ void chain_loop_d(const SIn (&in)[NIN], const SOut ou
     // VGPR offset — for a store the extra lanes' offset is out of range and the hardware drops it: no EXEC change, no branch,
     // straight-line code in which the compiler's wait counts for the prefetched loads stay exact — the span's position in
     // the scalar offset, the frame inside the span in the 12-bit immediate.
-    if constexpr (ELEMHIP_SPEC_BLOCK % (DEPTH * CHG) == 0 && NIN <= 3) {
+    // (every recurrence that spec_stateful lays out in quads names its carried registers: a plain lambda stays on the loop below)
+    if constexpr (ELEMHIP_SPEC_BLOCK % (DEPTH * CHG) == 0 && NIN <= 3 && IsChainStep<Step>::value) {
         if (out.quad && n == (uint32_t)ELEMHIP_SPEC_BLOCK) {
             bool allG = true;                                // (folds: the operand kinds are compile-time facts of the task)
 #pragma unroll
@@ -1746,19 +1763,19 @@ __device__ __forceinline__ void ser_phasor(const Ctx& c, const Member& m, uint32
     if ((cm & 1u) && in[0].cval * rsr >= 0.0f && phase >= 0.0f) {
         // constant non-negative step: next >= 0, so next - floor(next) is exactly v_fract_f32(next)
         const SIn st[1] = {sin_const(in[0].cval * rsr)};
-        chain_blocks_m<1, 1u>(c, st, sout_of(c, m), [&](const float (&x)[1]) {
+        chain_blocks_m<1, 1u>(c, st, sout_of(c, m), chain_step([&](const float (&x)[1]) {
             const float y = phase;
             phase = __builtin_amdgcn_fractf(phase + x[0]);
             return y;
-        });
+        }, [&](auto&& g) { g(phase); }));
     } else {
-        chain_blocks_c<CMT, 1>(c, in, cm, sout_of(c, m), [&](const float (&x)[1]) {
+        chain_blocks_c<CMT, 1>(c, in, cm, sout_of(c, m), chain_step([&](const float (&x)[1]) {
             const float stepv = x[0] * rsr;
             const float y = phase;
             const float next = phase + stepv;
             phase = next - floorf(next);
             return y;
-        });
+        }, [&](auto&& g) { g(phase); }));
     }
     r[rec::S0] = f2u(phase);
 }
@@ -1770,14 +1787,14 @@ __device__ __forceinline__ void ser_sphasor(const Ctx& c, const Member& m, uint3
     const SIn in[2] = {sin_of(c, opnd_lane(c, m, 0)), sin_of(c, opnd_lane(c, m, 1))};
     float phase = u2f(r[rec::S0]), lastIn = u2f(r[rec::S1]);
     const float rsr = 1.0f / c.srF;
-    chain_blocks_c<CMT, 2>(c, in, cm, sout_of(c, m), [&](const float (&x)[2]) {
+    chain_blocks_c<CMT, 2>(c, in, cm, sout_of(c, m), chain_step([&](const float (&x)[2]) {
         if (change_tick(lastIn, x[1]) > 0.5f) phase = 0.0f;
         const float stepv = x[0] * rsr;
         const float y = phase;
         const float next = phase + stepv;
         phase = next - floorf(next);
         return y;
-    });
+    }, [&](auto&& g) { g(phase); g(lastIn); }));
     r[rec::S0] = f2u(phase); r[rec::S1] = f2u(lastIn);
 }
 
@@ -1788,7 +1805,8 @@ __device__ __forceinline__ void ser_pole(const Ctx& c, const Member& m, uint32_t
     if (member_nin(c, m) < 2) return szero(m, c.n);
     const SIn in[2] = {sin_of(c, opnd_lane(c, m, 0)), sin_of(c, opnd_lane(c, m, 1))};
     float z = u2f(r[rec::S0]);
-    chain_blocks_c<CMT, 2>(c, in, cm, sout_of(c, m), [&](const float (&x)[2]) { z = x[1] + x[0] * z; return z; });
+    chain_blocks_c<CMT, 2>(c, in, cm, sout_of(c, m), chain_step([&](const float (&x)[2]) { z = x[1] + x[0] * z; return z; },
+                                                                [&](auto&& g) { g(z); }));
     r[rec::S0] = f2u(z);
 }
 
@@ -1799,12 +1817,12 @@ __device__ __forceinline__ void ser_env(const Ctx& c, const Member& m, uint32_t 
     if (member_nin(c, m) < 3) return szero(m, c.n);
     const SIn in[3] = {sin_of(c, opnd_lane(c, m, 0)), sin_of(c, opnd_lane(c, m, 1)), sin_of(c, opnd_lane(c, m, 2))};
     float z = u2f(r[rec::S0]);
-    chain_blocks_c<CMT, 3>(c, in, cm, sout_of(c, m), [&](const float (&x)[3]) {
+    chain_blocks_c<CMT, 3>(c, in, cm, sout_of(c, m), chain_step([&](const float (&x)[3]) {
         const float vn = fabsf(x[2]);
         if (fabsf(vn) > z) z = x[0] * (z - vn) + vn;
         else               z = x[1] * (z - vn) + vn;
         return z;
-    });
+    }, [&](auto&& g) { g(z); }));
     r[rec::S0] = f2u(z);
 }
 
@@ -1844,11 +1862,11 @@ __device__ __forceinline__ void ser_counter(const Ctx& c, const Member& m, uint3
     if (member_nin(c, m) < 1) return szero(m, c.n);
     const SIn in[1] = {sin_of(c, opnd_lane(c, m, 0))};
     float count = u2f(r[rec::S0]);
-    chain_blocks_c<CMT, 1>(c, in, cm, sout_of(c, m), [&](const float (&x)[1]) {
+    chain_blocks_c<CMT, 1>(c, in, cm, sout_of(c, m), chain_step([&](const float (&x)[1]) {
         if ((1.0f - x[0]) <= FLT_EPSILON) { const float y = count; count = count + 1.0f; return y; }
         count = 0.0f;
         return 0.0f;
-    });
+    }, [&](auto&& g) { g(count); }));
     r[rec::S0] = f2u(count);
 }
 
@@ -1858,11 +1876,11 @@ __device__ __forceinline__ void ser_accum(const Ctx& c, const Member& m, uint32_
     if (member_nin(c, m) < 2) return szero(m, c.n);
     const SIn in[2] = {sin_of(c, opnd_lane(c, m, 0)), sin_of(c, opnd_lane(c, m, 1))};
     float total = u2f(r[rec::S0]), lastIn = u2f(r[rec::S1]);
-    chain_blocks_c<CMT, 2>(c, in, cm, sout_of(c, m), [&](const float (&x)[2]) {
+    chain_blocks_c<CMT, 2>(c, in, cm, sout_of(c, m), chain_step([&](const float (&x)[2]) {
         if (change_tick(lastIn, x[1]) > 0.5f) total = 0.0f;
         total += x[0];
         return total;
-    });
+    }, [&](auto&& g) { g(total); g(lastIn); }));
     r[rec::S0] = f2u(total); r[rec::S1] = f2u(lastIn);
 }
 
@@ -1872,11 +1890,11 @@ __device__ __forceinline__ void ser_latch(const Ctx& c, const Member& m, uint32_
     if (member_nin(c, m) < 2) return szero(m, c.n);
     const SIn in[2] = {sin_of(c, opnd_lane(c, m, 0)), sin_of(c, opnd_lane(c, m, 1))};
     float z = u2f(r[rec::S0]), hold = u2f(r[rec::S1]);
-    chain_blocks_c<CMT, 2>(c, in, cm, sout_of(c, m), [&](const float (&x)[2]) {
+    chain_blocks_c<CMT, 2>(c, in, cm, sout_of(c, m), chain_step([&](const float (&x)[2]) {
         if (fabsf(z) <= FLT_EPSILON && x[0] > FLT_EPSILON) hold = x[1];
         z = x[0];
         return hold;
-    });
+    }, [&](auto&& g) { g(z); g(hold); }));
     r[rec::S0] = f2u(z); r[rec::S1] = f2u(hold);
 }
 
@@ -1887,11 +1905,11 @@ __device__ __forceinline__ void ser_maxhold(const Ctx& c, const Member& m, uint3
     const SIn in[2] = {sin_of(c, opnd_lane(c, m, 0)), sin_of(c, opnd_lane(c, m, 1))};
     const uint32_t hts = r[rec::P0];
     float lastIn = u2f(r[rec::S0]); uint32_t at = r[rec::S1]; float mx = u2f(r[rec::S2]);
-    chain_blocks_c<CMT, 2>(c, in, cm, sout_of(c, m), [&](const float (&x)[2]) {
+    chain_blocks_c<CMT, 2>(c, in, cm, sout_of(c, m), chain_step([&](const float (&x)[2]) {
         if (change_tick(lastIn, x[1]) > 0.5f || ++at >= hts) { mx = x[0]; at = 0; }
         else if (x[0] > mx) { at = 0; mx = x[0]; }
         return mx;
-    });
+    }, [&](auto&& g) { g(lastIn); g(at); g(mx); }));
     r[rec::S0] = f2u(lastIn); r[rec::S1] = at; r[rec::S2] = f2u(mx);
 }
 
@@ -2312,18 +2330,18 @@ __device__ __forceinline__ void ser_phase(const Ctx& c, const Member& m, bool bl
     if (__all(fast)) {
         // phasor: next >= 0, so next - floor(next) is exactly v_fract_f32(next); oscillator: t = phase + inc lies in [0, 2), where
         // `if (t >= 1) t -= 1` is t - floor(t) exactly as well
-        chain_blocks_m<1, 1u>(c, in, sout_of(c, m), [&](const float (&x)[1]) {
+        chain_blocks_m<1, 1u>(c, in, sout_of(c, m), chain_step([&](const float (&x)[1]) {
             const float y = phase;
             phase = __builtin_amdgcn_fractf(phase + x[0]);
             return y;
-        });
+        }, [&](auto&& g) { g(phase); }));
     } else {
-        chain_blocks_m<1, 1u>(c, in, sout_of(c, m), [&](const float (&x)[1]) {
+        chain_blocks_m<1, 1u>(c, in, sout_of(c, m), chain_step([&](const float (&x)[1]) {
             const float y = phase;
             const float t = phase + x[0];
             phase = blepLane ? (t >= 1.0f ? t - 1.0f : t) : t - floorf(t);
             return y;
-        });
+        }, [&](auto&& g) { g(phase); }));
     }
     r[rec::S0] = f2u(phase);
 }
