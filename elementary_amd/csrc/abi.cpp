@@ -167,6 +167,21 @@ int elemhip_resample_read(elemhip_t* h, elemhip_resample_info* info) {
 
 int elemhip_resample_reset(elemhip_t* h) { return h ? h->engine.resampleReset() : elemhip::kInvalidInstructionFormat; }
 
+int elemhip_input_resample_frames(elemhip_t* h, size_t numFrames, size_t* out) { return h ? h->engine.inputResampleFrames(numFrames, out) : elemhip::kInvalidInstructionFormat; }
+
+int elemhip_input_resample_read(elemhip_t* h, elemhip_resample_info* info) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    Engine::ResampleInfo ri{};
+    const int rc = h->engine.inputResampleRead(&ri);
+    if (info && rc == elemhip::kOk) {
+        info->up = ri.up; info->down = ri.down; info->taps = ri.taps; info->latency_frames = ri.latencyFrames;
+        info->frames_in = ri.framesIn; info->frames_out = ri.framesOut;
+    }
+    return rc;
+}
+
+int elemhip_input_resample_reset(elemhip_t* h) { return h ? h->engine.inputResampleReset() : elemhip::kInvalidInstructionFormat; }
+
 int elemhip_limiter_read(elemhip_t* h, elemhip_limiter_info* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity) {
     if (!h) return elemhip::kInvalidInstructionFormat;
     Engine::LimiterInfo li{};

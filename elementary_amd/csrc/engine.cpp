@@ -189,6 +189,7 @@ Engine::~Engine() {
     if (dPcmInRowBase) (void)hipFree(dPcmInRowBase);
     loudnessFree();
     resampleFree();
+    inputResampleFree();
     limiterFree();
     if (ioStream) (void)hipStreamDestroy(ioStream);
     if (relayStream) { (void)hipStreamSynchronize(relayStream); (void)hipStreamDestroy(relayStream); }
@@ -527,6 +528,9 @@ int Engine::setOption(const std::string& key, double value) {
     // resample.h: the host-buffer render calls deliver at this rate (Hz, integral like the engine's; 0 or the engine's rate: off),
     // converted on the GPU behind every launch set. Setting it starts a new programme — the meter's too, at the delivery rate.
     if (key == "resample_rate") return setResampleRate(value);
+    // resample.h, the input side: the host-buffer render calls take their inputs at this rate (Hz, integral; 0 or the engine's rate: off),
+    // converted to the engine's on the GPU in front of every launch set. Setting it starts a new input programme; nothing else changes.
+    if (key == "input_rate") return setInputRate(value);
     // limiter.h: a static gain and a look-ahead true-peak limiter on what those calls deliver, behind the converter. Turning it on, or
     // changing a parameter while it is on, starts a new programme; off (the default) not one launch, allocation or byte differs.
     if (key.compare(0, 7, "limiter") == 0) return setLimiterOption(key, value);

@@ -255,6 +255,17 @@ public:
     int resampleFrames(size_t numFrames, size_t* out);       // frames the next host-buffer call of numFrames delivers (off: numFrames)
     int resampleRead(ResampleInfo* info);
     int resampleReset();
+    // Option "input_rate" (resample.h, the input side; 0 or the engine's own rate: off): the inputs of processBlocksHost /
+    // processBlocksPcm / processBlocksPcmIo arrive at that rate — planar floats or interleaved PCM — and a kernel in front of every
+    // launch set's first level (resample_in.hip) decodes and converts them to the engine's rate where the H2D left them; where those
+    // calls render host block by host block the header's scalar loop converts on the host, the same bits. `numFrames` stays in ENGINE
+    // frames; the input arrays and streams hold inputResampleFrames(numFrames) frames. The programme is the engine frames those calls
+    // rendered with inputs, in call order, since the option was set or the last reset; its clock lives on the host, the last H decoded
+    // input frames of every channel on the device. Its channel count is that of the first call: a call with another count is refused
+    // (reset first). A call that fails starts a new programme. Independent of "resample_rate", "limiter" and "loudness_meter".
+    int inputResampleFrames(size_t numFrames, size_t* out);  // input frames the next host-buffer call of numFrames consumes (off: numFrames)
+    int inputResampleRead(ResampleInfo* info);               // (latencyFrames in engine frames, framesOut = engine frames)
+    int inputResampleReset();
     // Options "limiter" and "limiter_*" (limiter.h; off by default): a static gain and a look-ahead true-peak limiter on what the
     // host-buffer render calls deliver, behind the converter and in front of the pack kernel and the meter (limiter.hip; the header's
     // scalar loop where those calls render host block by host block). Frames in = frames out, delayed by latencyFrames. The programme
@@ -446,6 +457,20 @@ private:
     int ensureResample(size_t channels, size_t outBlocksCap);   // (`mu` held, both streams idle)
     int resampleResetLocked(size_t channels);
     void resampleFree();
+    // input-rate conversion (option "input_rate"): the tables and two copies of the carried decoded frames on the device (a set's kernel
+    // reads one, its history step writes the other); the programme's clock on the host
+    bool inResOn = false;
+    double inResRate = 0.0;                // the inputs' rate (0: off)
+    resample::Plan inPlan{};
+    std::vector<float> inTable; std::vector<int32_t> inRowBase;                   // host copies: the scalar loop's
+    float* dInTable = nullptr; int32_t* dInRowBase = nullptr;
+    float* dInHist[2] = {nullptr, nullptr}; size_t inHistChannels = 0; int inHistCur = 0;
+    uint32_t inChannels = 0;               // channels of the programme (0: none yet)
+    uint64_t inFramesIn = 0, inFramesOut = 0;                                     // inFramesIn = inputs_before(inFramesOut), always
+    int setInputRate(double hz);                                 // (`mu` held)
+    int ensureInputResample(size_t channels);                    // (`mu` held, both streams idle)
+    int inputResampleResetLocked(size_t channels);
+    void inputResampleFree();
     // the limiter (options "limiter", "limiter_*"): two copies of the carried state on the device (a set's kernels read one, its history
     // step writes the other), the statistics, the per-set scratch and per half the limited set; the programme's clock on the host
     bool limiterOn = false;

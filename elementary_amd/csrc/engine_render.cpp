@@ -1270,6 +1270,14 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
     // and copied; frames in = frames out, so neither the dither's key nor any count changes
     const bool limit = limiterOn && nOut > 0;
     const limiter::Plan lmp = limPlan;
+    // option "input_rate": the inputs — planar floats or streams — arrive at another rate and are converted to the engine's in front of
+    // the render; a call of numFrames ENGINE frames pulls the input frames [inputs_before(n0), inputs_before(n0 + numFrames)) of the
+    // programme. Planar floats count as nIn one-channel float streams: one path for both.
+    const bool inres = inResOn && nIn > 0;
+    const resample::Plan inp = inPlan;
+    const uint32_t inG = src ? srcG : 1u, inFmt = src ? srcFmt : pcm_pack::F32;
+    const size_t inStreams = src ? src->nStreams : nIn, inB = pcm_pack::sample_bytes(inFmt);
+    auto inStream = [&](size_t s) { return src ? static_cast<const unsigned char*>(src->streams[s]) : reinterpret_cast<const unsigned char*>(in[s]); };
     // whole HOST blocks, like the reference's block loop (a host block = hostBlockSize / blockSize engine blocks)
     const size_t hb = (size_t)hostBlockSize;
     bool tapSlices = hb % bs != 0;          // ragged slices (a host block that no k divides evenly): launch sets hold whole engine blocks
@@ -1331,6 +1339,20 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         };
         auto limFail = [&]() { if (limit) { RenderGuard lock(*this); (void)limiterResetLocked(0); } };
         if (limit) { const int rc = limSync(true); if (rc != kOk) { resFail(); if (meter) (void)meterSync(false); return rc; } }
+        // the input converter's carried frames likewise: unpack_host decodes, the header's scalar pull loop converts, the kernel's bits
+        std::vector<float> inHist(inres ? nIn * (size_t)inp.H : 0), inX;
+        auto inSync = [&](bool toHost) -> int {
+            RenderGuard lock(*this);
+            if (hipSetDevice(device) != hipSuccess) return kHipError;
+            if (toHost) { const int rc = ensureInputResample(nIn); if (rc != kOk) return rc; }
+            HIP_OK(hipStreamSynchronize(stream));
+            if (toHost) HIP_OK(hipMemcpy(inHist.data(), dInHist[inHistCur], inHist.size() * sizeof(float), hipMemcpyDeviceToHost));
+            else HIP_OK(hipMemcpy(dInHist[inHistCur], inHist.data(), inHist.size() * sizeof(float), hipMemcpyHostToDevice));
+            return kOk;
+        };
+        auto inFail = [&]() { if (inres) { RenderGuard lock(*this); (void)inputResampleResetLocked(0); } };
+        if (inres) { const int rc = inSync(true); if (rc != kOk) { resFail(); limFail(); if (meter) (void)meterSync(false); return rc; } }
+        size_t inOff = 0;                       // input frames of this call consumed so far
         size_t outOff = 0;                      // delivered frames of this call so far
         for (size_t f0 = 0; f0 < numFrames; f0 += hb) {
             const size_t nf = std::min(hb, numFrames - f0);
@@ -1342,7 +1364,24 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 tailOut.assign(nOut * hb, 0.0f);
                 for (size_t c = 0; c < nOut; ++c) op[c] = tailOut.data() + c * hb;
             }
-            if (src) {
+            if (inres) {
+                // the stretch this host block's nf engine frames pull, from the input cursor on: decoded where it is PCM, then converted
+                // into the block's rows (zeros behind nf)
+                std::lock_guard<std::mutex> lock(mu);
+                const size_t ni = (size_t)(resample::inputs_before(inp, inFramesOut + nf) - inFramesIn), stride = std::max<size_t>(ni, 1);
+                tailIn.assign(nIn * hb, 0.0f);
+                if (src) {
+                    inX.resize(nIn * stride);
+                    for (size_t s = 0; s < src->nStreams; ++s) srcAt[s] = inStream(s) + inOff * srcG * srcB;
+                    pcm_unpack::unpack_host(srcFmt, srcG, (uint32_t)src->nStreams, srcAt.data(), ni, inX.data(), stride, ni);
+                }
+                for (size_t c = 0; c < nIn; ++c) {
+                    (void)resample::resample_in_host(inp, inTable.data(), inRowBase.data(), inHist.data() + c * inp.H, src ? inX.data() + c * stride : in[c] + inOff,
+                                                     inFramesOut, nf, tailIn.data() + c * hb);
+                    ip[c] = tailIn.data() + c * hb;
+                }
+                inOff += ni; inFramesIn += ni; inFramesOut += nf;
+            } else if (src) {
                 // the inputs are needed on the host: the header's scalar loop unpacks them — the kernel's functions, the kernel's floats
                 tailIn.resize(nIn * hb);
                 for (size_t s = 0; s < src->nStreams; ++s) srcAt[s] = static_cast<const unsigned char*>(src->streams[s]) + f0 * srcG * srcB;
@@ -1353,7 +1392,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 for (size_t c = 0; c < nIn; ++c) { std::memcpy(tailIn.data() + c * hb, in[c] + f0, nf * sizeof(float)); ip[c] = tailIn.data() + c * hb; }
             }
             const int rc = process(ip.data(), nIn, op.data(), nOut, hb, sampleTime + (int64_t)f0);
-            if (rc != kOk) { if (meter) (void)meterSync(false); resFail(); limFail(); return rc; }
+            if (rc != kOk) { if (meter) (void)meterSync(false); resFail(); limFail(); inFail(); return rc; }
             // what is delivered of this host block: its nf frames, or their conversion
             const float* got = tailOut.data();
             size_t gotStride = hb, nd = nf, at = f0;
@@ -1394,11 +1433,14 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         int rc = meter ? meterSync(false) : kOk;
         if (resamp) { const int rr = resSync(false); if (rc == kOk) rc = rr; if (rc != kOk) resFail(); }
         if (limit) { const int rl = limSync(false); if (rc == kOk) rc = rl; if (rc != kOk) limFail(); }
+        if (inres) { const int ri = inSync(false); if (rc == kOk) rc = ri; if (rc != kOk) inFail(); }
         return rc;
     }
     const size_t numBlocks = ((numFrames + hb - 1) / hb) * (hb / bs);
     if (numBlocks == 0) return kOk;
     size_t setBlocks, outCapFrames = 0, outCapBlocks = 0;     // what a set delivers at most: frames, and whole blocks of the converted half
+    uint64_t inN = 0;                                         // option "input_rate": the programme's engine frame at the next set's start
+    size_t inOff = 0;                                         // ... and the input frames of this call consumed so far
     {
         RenderGuard lock(*this);
         if (hipSetDevice(device) != hipSuccess) return kHipError;
@@ -1420,7 +1462,16 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             rc = ensureLimiter(nOut, outCapBlocks, outCapFrames);
             if (rc != kOk) return rc;
         }
-        if (src) {
+        if (inres) {
+            // the packed halves hold the largest stretch a set can pull: ceil(frames M / L) + 1 input frames of every stream
+            const uint64_t maxIn = resample::ceil_div((uint64_t)(setBlocks * bs) * inp.M, inp.L) + 1u;
+            if (maxIn > 0xFFFFFFFFull) return kInvalidPropertyValue;      // (the kernels count a set's frames in 32 bits)
+            rc = ensureInputResample(nIn);
+            if (rc != kOk) return rc;
+            rc = growPackedHalves(hPcmIn, dPcmIn, pcmInBytes, inStreams * (size_t)pcm_pack::stream_stride(maxIn, inG, inFmt));
+            if (rc != kOk) return rc;
+            inN = inFramesOut;
+        } else if (src) {
             rc = ensurePcmInStaging(src->nStreams * (size_t)pcm_pack::stream_stride(setBlocks * bs, srcG, srcFmt), srcG);
             if (rc != kOk) return rc;
         }
@@ -1499,9 +1550,23 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         const int half = (int)(k & 1);
         // (sets hold whole host blocks, so a set starts in front of numFrames)
         const size_t srcValid = src ? std::min(nb * bs, numFrames - b0 * bs) : 0, srcStride = src ? (size_t)pcm_pack::stream_stride(srcValid, srcG, srcFmt) : 0;
+        // option "input_rate": the set's engine frames [inN, inN + inOut) pull the input frames [inT0, inT0 + inValid), which start at the
+        // call's input cursor
+        const size_t inOut = inres ? std::min(nb * bs, numFrames - b0 * bs) : 0;
+        const uint64_t inT0 = inres ? resample::inputs_before(inp, inN) : 0;
+        const size_t inValid = inres ? (size_t)(resample::inputs_before(inp, inN + inOut) - inT0) : 0;
+        const size_t inStride = inres ? (size_t)pcm_pack::stream_stride(inValid, inG, inFmt) : 0;
         if (nIn) {
             if (k >= 2) HOST_TRY(hipEventSynchronize(evIn[half]));     // the H2D of set k - 2 has left this pinned half
-            if (src) {
+            if (inres) {
+                // one contiguous stretch per stream (per planar array): the input-rate bytes and nothing more
+                const size_t len = inValid * inG * inB;
+                unsigned char* dst = hPcmIn[half];
+                spread(inStreams * len, len / 4096 + 1, [&](size_t t, size_t threads) {
+                    const size_t lo = len * t / threads, hi = len * (t + 1) / threads;
+                    for (size_t s = 0; s < inStreams; ++s) std::memcpy(dst + s * inStride + lo, inStream(s) + inOff * inG * inB + lo, hi - lo);
+                });
+            } else if (src) {
                 // one contiguous stretch per stream: the set's valid frames, as they lie in the caller's streams
                 const size_t len = srcValid * srcG * srcB;
                 unsigned char* dst = hPcmIn[half];
@@ -1512,7 +1577,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 });
             }
             float* dst = hStageIn[half];
-            for (size_t b = 0; b < nb && !src; ++b) {
+            for (size_t b = 0; b < nb && !src && !inres; ++b) {
                 const size_t f0 = (b0 + b) * bs;
                 const size_t n = f0 < numFrames ? std::min(bs, numFrames - f0) : 0;
                 for (size_t c = 0; c < nIn; ++c) {
@@ -1528,11 +1593,26 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             if (nIn) {
                 // (the copy stream is in order: this H2D runs behind the D2H of set k - 2, which waited for that set's render,
                 //  the last reader of this device half)
-                if (src) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], src->nStreams * srcStride, hipMemcpyHostToDevice, ioStream))
+                if (inres) { if (inStreams * inStride) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], inStreams * inStride, hipMemcpyHostToDevice, ioStream)); }
+                else if (src) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], src->nStreams * srcStride, hipMemcpyHostToDevice, ioStream))
                 else HOST_TRY(hipMemcpyAsync(dStageIn[half], hStageIn[half], nb * nIn * bs * sizeof(float), hipMemcpyHostToDevice, ioStream));
                 HOST_TRY(hipEventRecord(evIn[half], ioStream));
                 HOST_TRY(hipStreamWaitEvent(stream, evIn[half], 0));
-                if (src) {
+                if (inres) {
+                    // the input converter in the unpack kernel's place, and the argument below holds for it word for word: dStageIn[half]
+                    // and dPcmIn[half] are free for the same reasons, and it too writes every row of all nb blocks, zeros behind inOut.
+                    // It reads one copy of the carried frames and its history step writes the other; the kernels of set k - 1 that read
+                    // the copy now written ran earlier on this stream.
+                    ResampleInArgs a{};
+                    a.src = dPcmIn[half]; a.dst = dStageIn[half]; a.histIn = dInHist[inHistCur]; a.histOut = dInHist[inHistCur ^ 1];
+                    a.table = dInTable; a.rowBase = dInRowBase; a.t0 = inT0; a.n0 = inN; a.streamStride = inStride;
+                    a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nIn; a.G = inG; a.numStreams = (uint32_t)inStreams;
+                    a.validIn = (uint32_t)inValid; a.validOut = (uint32_t)inOut; a.numBlocks = (uint32_t)nb; a.plan = inp;
+                    HOST_TRY(launch_resample_in(stream, a, inFmt));
+                    inHistCur ^= 1;
+                    inN += inOut; inOff += inValid;
+                    inFramesOut = inN; inFramesIn = inT0 + inValid;
+                } else if (src) {
                     // the unpack kernel in front of the set's first level, on the render's stream. Both halves it touches are free:
                     // dStageIn[half] was last read by the render of set k - 2, earlier on this stream; dPcmIn[half] was last read by
                     // the unpack of set k - 2, earlier on this stream too, and the H2D that refilled it ran behind the D2H of set
@@ -1649,6 +1729,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         if (meter && result != kOk) (void)loudnessResetLocked(loudChannels);
         if (resamp && result != kOk) (void)resampleResetLocked(0);      // likewise: the clock may be ahead of what was delivered
         if (limit && result != kOk) (void)limiterResetLocked(0);
+        if (inres && result != kOk) (void)inputResampleResetLocked(0);   // and the input programme: its clock may be ahead of what was rendered
     }
     return result;
 }

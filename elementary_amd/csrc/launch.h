@@ -117,6 +117,22 @@ struct ResampleArgs {
     resample::Plan  plan;
 };
 hipError_t launch_resample(hipStream_t s, const ResampleArgs& a);
+// ---- input-rate conversion (resample_in.hip): in front of a launch set's first level, in the unpack kernel's place, resample.h ----
+struct ResampleInArgs {
+    const unsigned char* src;       // [stream] at `streamStride` bytes (a multiple of 16; the base 16-byte aligned): validIn * G samples each,
+                                    // the programme's input frames [t0, t0 + validIn)
+    float*          dst;            // the set's input, [numBlocks][numChannels][blockSize]: rows s * G + g of every block are written whole —
+                                    // validOut frames at the engine's rate, zeros up to the last block's end
+    const float*    histIn;         // [numStreams * G][plan.H]: the decoded input frames in front of t0, oldest first
+    float*          histOut;        // the other copy: receives the frames in front of the NEXT set's stretch
+    const float*    table;          // resample::make_tables: [plan.T][plan.L]
+    const int32_t*  rowBase;        // [plan.L]
+    uint64_t        t0, n0;         // the programme's input / engine frame index at the set's start: t0 = inputs_before(n0)
+    uint64_t        streamStride;
+    uint32_t        blockSize, numChannels, G, numStreams, validIn, validOut, numBlocks, pad;
+    resample::Plan  plan;           // fin = the input's rate, fout = the engine's
+};
+hipError_t launch_resample_in(hipStream_t s, const ResampleInArgs& a, uint32_t format);
 // ---- true-peak limiter (limiter.hip): behind the converter, in front of the pack kernel and the meter, limiter.h ----
 struct LimiterArgs {
     const float*    src;            // the set's delivered frames, [block][numChannels][blockSize]: validFrames of them

@@ -1,7 +1,8 @@
 // resample.h — the arithmetic and the lane schedule of the delivery-rate converter (resample.hip, Engine option "resample_rate"): a
 // polyphase Kaiser-windowed sinc that turns the frames a launch set rendered at the engine's rate `fin` into frames at the delivery
 // rate `fout`, where the set's output lies in HBM. Nothing here knows which side is the engine's: a plan is made from two integral
-// rates, so a later input-side converter takes the same header.
+// rates, and the input-rate converter (resample_in.hip, option "input_rate") takes the same plan, tables and tap sum with fin = the
+// input's rate; what that side adds — the pull schedule, its scalar loop — is the last section below.
 //
 // The plan.  g = gcd(fin, fout), L = fout / g, M = fin / g, s = min(1, L / M), half width W = Z / s input frames (Z = 32), Wc = ceil(W),
 // T = 2 Wc taps per phase, latency Do = ceil(Wc L / M) OUTPUT frames. Prototype g(t) = s sinc(s t) I0(beta sqrt(1 - (t / W)^2)) / I0(beta)
@@ -164,6 +165,65 @@ inline size_t resample_host(const Plan& p, const float* table, const int32_t* ro
     if (n >= p.H) memcpy(hist, x + (n - p.H), p.H * sizeof(float));
     else if (n) { memmove(hist, hist + n, (p.H - n) * sizeof(float)); memcpy(hist + (p.H - n), x, n * sizeof(float)); }
     return (size_t)(n1 - n0);
+}
+
+// ---- the input side: the engine pulls (resample_in.hip, Engine option "input_rate") -------------------------------------------------
+// The plan is made with fin = the input's rate and fout = the engine's. The engine renders whole calls of engine frames, so a call of
+// `numFrames` outputs that starts at the programme's output n0 consumes the inputs [inputs_before(n0), inputs_before(n0 + numFrames)):
+// inputs_before(n) is the smallest t for which output n - 1 exists, the smallest t with outputs_before(t) >= n. Output n - 1 reads no
+// index above floor((n - 1) M / L) = inputs_before(n) - 1 (see above), so nothing reads past what the call was given.
+// The smallest index an output of that call reads is centre(n0) - Wc + 1 = floor((n0 - Do) M / L) - Wc + 1, and inputs_before(n0) minus
+// that is floor((n0 - 1) M / L) - floor((n0 - Do) M / L) + Wc <= ceil((Do - 1) M / L) + Wc <= 2 Wc = T, because (Do - 1) M / L < Wc by
+// Do = ceil(Wc L / M). T <= H: the plan's H carried frames more than suffice on this side too.
+// 32-bit counts: a set's input stretch is about M / L times its engine frames, so a plan with M > kMaxGrowth L is refused here.
+RS_FD uint64_t inputs_before(const Plan& p, uint64_t n) { return n == 0u ? 0u : (n - 1u) * p.M / p.L + 1u; }
+inline bool make_plan_in(double fin, double fout, Plan& p) {
+    Plan q;
+    if (!make_plan(fin, fout, q) || q.M > (uint64_t)kMaxGrowth * q.L) return false;
+    p = q;
+    return true;
+}
+// the carried frames behind a stretch of validIn frames, slot j (oldest first); at(f) is the stretch's frame f
+template <class At>
+RS_FD float history_pull(At at, const float* old, uint32_t validIn, uint32_t H, uint32_t j) {
+    const uint64_t i = (uint64_t)validIn + j;
+    return i >= H ? at((uint32_t)(i - H)) : old[i];
+}
+// A tile of the input-side kernel = kTile consecutive engine frames of the set, one stream, C channels of it; tile_of, lane_base, skew and
+// row_floats are the ones above with n0 = the set's first engine frame. Of the row slots [0, span) the slots [lo, hi) come from the
+// set's stretch of the stream (slot i <-> frame rel0 + i of the stretch, rel0 = jlo - t0), the slots below lo from the carried frames;
+// slots from hi on lie behind the stretch, where no output of the set reaches: silence.
+struct StreamPart { uint32_t lo, hi; };
+RS_FD StreamPart stream_part(int64_t rel0, uint32_t span, uint32_t validIn) {
+    StreamPart s;
+    s.lo = rel0 >= 0 ? 0u : (-rel0 < (int64_t)span ? (uint32_t)(-rel0) : span);
+    const int64_t end = (int64_t)validIn - rel0;
+    s.hi = end <= (int64_t)s.lo ? s.lo : (end < (int64_t)span ? (uint32_t)end : span);
+    return s;
+}
+// a carried frame: the programme's frame t0 + rel, rel < 0
+RS_FD float carried_at(const float* hist, uint32_t H, int64_t rel) { return rel + (int64_t)H >= 0 ? hist[(int64_t)H + rel] : 0.0f; }
+// LDS of the input-side kernel: C padded rows, then (16-byte aligned) the image of a narrow stream's stretch — G <= C channels of up to
+// 4 bytes, so it is sized by C and never by the stream's width; a wider stream is read sample by sample and has no image
+RS_FD uint32_t in_image_offset(const Plan& p, uint32_t C) { return (C * row_floats(p) * 4u + 15u) & ~15u; }
+RS_FD uint32_t in_lds_bytes(const Plan& p, uint32_t C) { return in_image_offset(p, C) + span_max(p) * C * 4u + 32u; }
+
+// The scalar pull loop, one channel: y receives the outputs [n0, n0 + numFrames); x holds the programme's frames from
+// inputs_before(n0) on, hist the H frames in front of them (zeros at a reset) and, on return, the H frames in front of what the
+// next call takes. Returns the frames consumed.
+inline size_t resample_in_host(const Plan& p, const float* table, const int32_t* rowBase, float* hist, const float* x, uint64_t n0, size_t numFrames, float* y) {
+    const uint64_t t0 = inputs_before(p, n0);
+    const size_t n = (size_t)(inputs_before(p, n0 + numFrames) - t0);
+    for (uint64_t m = n0; m < n0 + numFrames; ++m) {
+        const int64_t rel0 = centre(p, rowBase, m) - (int64_t)p.Wc + 1 - (int64_t)t0;
+        tap_sum<1>(table + m % p.L, p.L, p.T, [&](int, uint32_t k) {
+            const int64_t j = rel0 + (int64_t)k;
+            return j >= 0 ? x[j] : (j + (int64_t)p.H >= 0 ? hist[(int64_t)p.H + j] : 0.0f);
+        }, y + (m - n0));
+    }
+    if (n >= p.H) memcpy(hist, x + (n - p.H), p.H * sizeof(float));
+    else if (n) { memmove(hist, hist + n, (p.H - n) * sizeof(float)); memcpy(hist + (p.H - n), x, n * sizeof(float)); }
+    return n;
 }
 
 } // namespace resample

@@ -13,7 +13,7 @@ from .wav import WavReader
 
 
 def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, target_lufs: float = -14.0, ceiling_dbtp: float = -1.0,
-               fmt: str = "s24", block_size: int = 512, **limiter) -> Dict[str, Any]:
+               fmt: str = "s24", block_size: int = 512, oversample: int = 1, **limiter) -> Dict[str, Any]:
     """``in_path`` -> ``out_path`` (format ``fmt``, the input's rate and channel count) at ``target_lufs`` integrated loudness under a
     true-peak ceiling of ``ceiling_dbtp``. ``limiter``: further limiter parameters (``lookahead_ms``, ``release_ms``, ``link``).
     Returns ``{'input_lufs', 'input_true_peak_dbtp', 'output_lufs', 'output_true_peak_dbtp', 'gain_db', 'max_reduction_db',
@@ -22,7 +22,15 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
     gate (silence) raises ``ValueError``: there is no gain that brings it to a target.
 
     Both passes meter on the same grid: the limiter delays its output by ``latency_frames``, so the first pass puts as many frames of
-    silence in front of the input — the second pass's figures then differ from the first's by the gain and the limiter alone."""
+    silence in front of the input — the second pass's figures then differ from the first's by the gain and the limiter alone.
+
+    ``oversample`` = k > 1: the engine runs at k times the file's rate with ``input_sample_rate`` and ``output_sample_rate`` both the
+    file's, in both passes — the file is converted up on the GPU in front of the graph and down again behind it. Nothing else
+    changes: the limiter and the meter still work on what is delivered, at the file's rate, and the output has the input's rate and
+    length. The first pass renders the converters' latencies out behind the file, so both passes still meter on one grid."""
+    k = int(oversample)
+    if k < 1:
+        raise ValueError("oversample is a whole factor of 1 or more")
     unknown = set(limiter) - {"lookahead_ms", "release_ms", "link"}
     if unknown:
         raise ValueError(f"unknown limiter parameters: {sorted(unknown)}")
@@ -31,13 +39,18 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
 
     def renderer(**kw):
         core = OfflineRenderer(engine_factory)
-        core.initialize(num_input_channels=channels, num_output_channels=channels, sample_rate=rate, block_size=int(block_size),
+        if k > 1:
+            kw = dict(kw, input_sample_rate=rate, output_sample_rate=rate)
+        core.initialize(num_input_channels=channels, num_output_channels=channels, sample_rate=rate * k, block_size=int(block_size),
                         loudness_meter=True, **kw)
         core.render(*[el.in_({"channel": c}) for c in range(channels)])
         # the roots fade in over 20 ms of engine time: let that pass on silence, then start the meter's programme
-        warm = -(-int(0.05 * rate) // int(block_size)) * int(block_size)
+        warm = -(-int(0.05 * rate * k) // int(block_size)) * int(block_size)
         core.process_pcm_io([silence(warm)], in_fmt, warm)
         core.loudness_reset()
+        if k > 1:                                  # the converters' programmes start with the meter's
+            core.input_resample_reset()
+            core.resample_reset()
         return core
 
     def silence(n):
@@ -50,13 +63,17 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
     latency = probe.limiter()["latency_frames"]
     del probe
     first = renderer()
-    first.process_pcm_io([silence(latency)], in_fmt, latency)
+    first.process_pcm_io([silence(latency)], in_fmt, latency * k)      # (every call renders a multiple of k engine frames: it consumes its frames / k)
     with WavReader(str(in_path)) as r:
         done = 0
         while done < frames:
             m = min(1 << 20, frames - done)
-            first.process_pcm_io([r.read(m)], in_fmt, m)
+            first.process_pcm_io([r.read(m)], in_fmt, m * k)
             done += m
+    if k > 1:
+        # what the second pass renders behind the file to take the converters' latencies out (OfflineRenderer._file_span)
+        tail = first.resample()["latency_frames"] + (2 * first.input_resample()["latency_frames"] + k) // (2 * k)
+        first.process_pcm_io([silence(1)], in_fmt, tail * k)
     measured = first.loudness()
     if not np.isfinite(measured["integrated_lufs"]):
         raise ValueError("the input passes no loudness gate: no gain brings it to a target")

@@ -22,7 +22,7 @@ class OfflineRenderer:
     def initialize(self, num_input_channels: int = 0, num_output_channels: int = 2, sample_rate: float = 44100,
                    block_size: int = 512, virtual_file_system: Optional[Dict[str, np.ndarray]] = None,
                    event_history_blocks: int = 0, capture_history_blocks: int = 0, loudness_meter: bool = False,
-                   output_sample_rate: Optional[float] = None, limiter=None) -> None:
+                   output_sample_rate: Optional[float] = None, limiter=None, input_sample_rate: Optional[float] = None) -> None:
         """``event_history_blocks`` (no counterpart in the reference; 0 = off): engine option of the same name — `scope` and `fft`
         nodes keep a device ring long enough for a relay window of that many blocks, so ``process`` still renders launch sets of
         that size with such a listener attached (engines without ``set_option`` relay after every block anyway).
@@ -42,7 +42,14 @@ class OfflineRenderer:
         many blocks), ``process_pcm`` and ``process_pcm_io`` deliver, behind the converter and in front of the PCM packing and the
         meter, with a latency of ``limiter()['latency_frames']`` delivered frames; ``write_wav`` and ``process_wav`` take that latency
         out. The delivered sample peak stays under the ceiling; the metered true peak of the output may exceed it slightly (about
-        0.1 dB at a look-ahead of one frame, 0.004 dB at 66). An engine without the option raises ``RuntimeError``."""
+        0.1 dB at a look-ahead of one frame, 0.004 dB at 66). An engine without the option raises ``RuntimeError``.
+        ``input_sample_rate`` (likewise; None or ``sample_rate`` itself: off): engine option ``input_rate`` — the inputs of ``process``,
+        ``process_pcm`` and ``process_pcm_io`` arrive at this rate and are converted to ``sample_rate`` on the GPU by the same
+        windowed-sinc filter, with a latency of ``input_resample()['latency_frames']`` ENGINE frames. Frame counts stay in engine
+        frames; a call of ``m`` of them consumes ``runtime.input_resample_frames(m)`` input frames from where the last one stopped,
+        and inputs that end early are padded with silence. ``process_wav`` then takes files at this rate, with that latency taken
+        out. With ``sample_rate`` = 4 x 44100 and both rates 44100, a 44.1 kHz file is processed with fourfold oversampling. An
+        engine without the option raises ``RuntimeError``."""
         self.num_in = int(num_input_channels)
         self.num_out = int(num_output_channels)
         self.block_size = int(block_size)
@@ -79,6 +86,16 @@ class OfflineRenderer:
                 self._rt.set_option("limiter", 1)
             except RuntimeError as e:
                 raise RuntimeError(f"this engine cannot limit with {params} at {self.output_sample_rate:g} Hz") from e
+        self.input_sample_rate = self.sample_rate
+        self._inres = input_sample_rate is not None and float(input_sample_rate) != self.sample_rate
+        if self._inres:
+            if not hasattr(self._rt, "set_option") or not hasattr(self._rt, "input_resample_read"):
+                raise RuntimeError("this engine cannot take inputs at another sample rate (option input_rate)")
+            try:
+                self._rt.set_option("input_rate", float(input_sample_rate))
+            except RuntimeError as e:
+                raise RuntimeError(f"this engine cannot take {float(input_sample_rate):g} Hz inputs at {self.sample_rate:g} Hz") from e
+            self.input_sample_rate = float(input_sample_rate)
         self._time = 0
         for k, v in (virtual_file_system or {}).items():
             self._rt.add_shared_resource(k, v)
@@ -118,7 +135,12 @@ class OfflineRenderer:
             # the output buffers hold DELIVERED frames: render the inputs' length, or — without inputs — what fills the buffers
             info = self._rt.resample_read()
             total = max([len(b) for b in inputs], default=-((-total * info["down"]) // info["up"]))
-        if host_batch is not None and window is not None and any(self._listeners.values()) and (total > bs or self._resample or self._limiter):
+            if getattr(self, "_inres", False) and self.num_in:      # (the inputs' length in ENGINE frames)
+                iinfo = self._rt.input_resample_read()
+                total = -((-total * iinfo["up"]) // iinfo["down"])
+        inres = getattr(self, "_inres", False) and self.num_in > 0
+        icur = 0                                     # input frames consumed so far (option input_rate: not the engine's count)
+        if host_batch is not None and window is not None and any(self._listeners.values()) and (total > bs or self._resample or self._limiter or inres):
             # listeners to serve: the reference relays events after EVERY block (index.ts:112-122). The engine keeps per-block readout
             # logs, so the block loop still runs as launch sets — `event_window_blocks()` blocks per engine call (1024 with meters and
             # snapshots only, fewer with a scope ring, one with a capture node made without history) — and the BLOCKWISE relay after each call hands the
@@ -129,10 +151,7 @@ class OfflineRenderer:
                 m = min(w, total - k)
                 x = None
                 if self.num_in:
-                    x = np.zeros((self.num_in, m), dtype=np.float32)
-                    for i, buf in enumerate(inputs):
-                        seg = np.asarray(buf[k:k + m], dtype=np.float32)
-                        x[i, :len(seg)] = seg
+                    x, icur = self._pull(inputs, icur, m)
                 y = host_batch(x, self.num_out, m, sample_time=self._time)
                 self._time += ((m + bs - 1) // bs) * bs
                 for kind, payload in self._rt.process_queued_events(blockwise=True):
@@ -144,17 +163,14 @@ class OfflineRenderer:
                         buf[at:at + mm] = y[i, :mm]
                 at += y.shape[1]
             return
-        if host_batch is not None and not any(self._listeners.values()) and (total > bs or self._resample or self._limiter):
+        if host_batch is not None and not any(self._listeners.values()) and (total > bs or self._resample or self._limiter or inres):
             # no event listeners to serve between blocks: the whole block loop in one engine call
             # (elemhip_process_blocks_host: launch sets staged through pinned double buffers); the event queues are drained
             # once afterwards, as the per-block loop's relay (index.ts:118-122) would have kept them drained — a listener
             # attached later must not find a capture / scope ring that overran during this render
             x = None
             if self.num_in:
-                x = np.zeros((self.num_in, total), dtype=np.float32)
-                for i, buf in enumerate(inputs):
-                    seg = np.asarray(buf[:total], dtype=np.float32)
-                    x[i, :len(seg)] = seg
+                x, icur = self._pull(inputs, icur, total)
             y = host_batch(x, self.num_out, total, sample_time=self._time)
             self._time += ((total + bs - 1) // bs) * bs
             self._rt.process_queued_events()
@@ -166,6 +182,8 @@ class OfflineRenderer:
             raise RuntimeError("this engine cannot deliver at another sample rate (no process_blocks_host)")
         if self._limiter and host_batch is None:
             raise RuntimeError("this engine cannot limit (no process_blocks_host)")
+        if inres:
+            raise RuntimeError("this engine cannot take inputs at another sample rate (no process_blocks_host)")
         for k in range(0, total, bs):
             block_in = None
             if self.num_in:
@@ -182,6 +200,17 @@ class OfflineRenderer:
                 m = min(bs, len(buf) - k)
                 if m > 0:
                     buf[k:k + m] = out[i, :m]
+
+    def _pull(self, inputs, cursor: int, m: int):
+        """The planar inputs of an engine call of ``m`` frames, from input frame ``cursor`` on, padded with silence: ``m`` frames, or
+        — ``initialize(input_sample_rate=...)`` — the ``input_resample_frames(m)`` frames the call consumes. Returns them and the
+        cursor behind them."""
+        ni = self._rt.input_resample_frames(m) if getattr(self, "_inres", False) else m
+        x = np.zeros((self.num_in, ni), dtype=np.float32)
+        for i, buf in enumerate(inputs):
+            seg = np.asarray(buf[cursor:cursor + ni], dtype=np.float32)
+            x[i, :len(seg)] = seg
+        return x, cursor + ni
 
     def process_pcm(self, inputs: Sequence[np.ndarray], num_streams: int, channels_per_stream: int, num_frames: int, fmt="s16",
                     dither_seed: Optional[int] = None, want_float: bool = False, sample_time: Optional[int] = None):
@@ -203,14 +232,12 @@ class OfflineRenderer:
         listening = any(self._listeners.values()) and hasattr(self._rt, "event_window_blocks")
         w = max(1, int(self._rt.event_window_blocks())) * bs if listening else max(total, 1)
         parts = []
+        icur = 0
         for k in range(0, max(total, 1), w):
             m = min(w, total - k)
             x = None
             if self.num_in:
-                x = np.zeros((self.num_in, m), dtype=np.float32)
-                for i, buf in enumerate(inputs):
-                    seg = np.asarray(buf[k:k + m], dtype=np.float32)
-                    x[i, :len(seg)] = seg
+                x, icur = self._pull(inputs, icur, m)
             parts.append(pcm(x, num_streams, channels_per_stream, m, fmt, dither_seed=dither_seed, want_float=want_float, sample_time=self._time))
             self._time += ((m + bs - 1) // bs) * bs
             events = self._rt.process_queued_events(blockwise=True) if listening else self._rt.process_queued_events()
@@ -258,6 +285,17 @@ class OfflineRenderer:
         """A new programme for the converter: time 0, silence in front of it."""
         self._rt.resample_reset()
 
+    def input_resample(self) -> Dict[str, int]:
+        """The input converter's plan and clock (``initialize(input_sample_rate=...)``): ``{'up', 'down', 'taps', 'latency_frames',
+        'frames_in', 'frames_out'}`` — the latency and ``frames_out`` in engine frames."""
+        if not getattr(self, "_inres", False):
+            raise RuntimeError("inputs at another rate are off: initialize(input_sample_rate=...)")
+        return self._rt.input_resample_read()
+
+    def input_resample_reset(self) -> None:
+        """A new programme for the input converter: time 0, silence in front of it."""
+        self._rt.input_resample_reset()
+
     def limiter(self) -> Dict[str, Any]:
         """The limiter's plan and statistics (``initialize(limiter=...)``): ``{'lookahead_frames', 'latency_frames', 'release_frames',
         'link', 'groups', 'frames', 'max_reduction', 'limited_frames'}`` — the last two one per linked group — and
@@ -273,12 +311,30 @@ class OfflineRenderer:
         """A new programme for the limiter: frame 0, silence in front of it, statistics zero."""
         self._rt.limiter_reset()
 
-    def _file_span(self, num_frames: int):
+    def _file_span(self, num_frames: int, input_frames: bool = False):
         """A file of a converted and / or limited render: (frames to render, delivered frames to drop in front, frames the file
         holds). The converter's latency Do and the limiter's D + 6, both in delivered frames, are taken out together, so frame n of
         the file is the (limited) render at time n * down / up: ceil((Do + D + 6) down / up) further frames are rendered, the first
-        Do + D + 6 delivered frames dropped, ceil(num_frames up / down) kept. New programmes start."""
+        Do + D + 6 delivered frames dropped, ceil(num_frames up / down) kept. New programmes start.
+        With ``initialize(input_sample_rate=...)`` the input converter's latency Di (engine frames) is taken out with the others: in
+        delivered frames it is Di up / down, rounded to nearest where that is not integral — the file then sits less than half a
+        delivered frame off. ``input_frames``: ``num_frames`` counts frames of an input file, which render ceil(F L / M) engine
+        frames (L / M = engine rate / input rate)."""
         limiting = getattr(self, "_limiter", False)
+        if getattr(self, "_inres", False):
+            self._rt.input_resample_reset()
+            iinfo = self._rt.input_resample_read()
+            n = -((-int(num_frames) * iinfo["up"]) // iinfo["down"]) if input_frames else int(num_frames)
+            up, down, lat = 1, 1, 0
+            if self._resample:
+                self._rt.resample_reset()
+                info = self._rt.resample_read()
+                up, down, lat = info["up"], info["down"], info["latency_frames"]
+            if limiting:
+                self._rt.limiter_reset()
+                lat += self._rt.limiter_read()["latency_frames"]
+            lat += (2 * iinfo["latency_frames"] * up + down) // (2 * down)
+            return n + -((-lat * down) // up), lat, -((-n * up) // down)
         if not self._resample and not limiting:
             return int(num_frames), 0, int(num_frames)
         up, down, lat = 1, 1, 0
@@ -329,9 +385,12 @@ class OfflineRenderer:
         writers = [WavWriter(p, fmt if isinstance(fmt, str) else {1: "s16", 2: "s24", 3: "f32"}[int(fmt)], G, self.output_sample_rate) for p in paths]
         stats = None
         try:
+            icur = 0                          # input frames consumed so far (initialize(input_sample_rate=...): not the engine's count)
             for k in range(0, total, chunk):
                 m = min(chunk, total - k)
-                streams, st, _ = self.process_pcm([np.asarray(b)[k:k + m] for b in inputs], S, G, m, fmt, dither_seed=dither_seed)
+                ni = self._rt.input_resample_frames(m) if getattr(self, "_inres", False) and self.num_in else m
+                streams, st, _ = self.process_pcm([np.asarray(b)[icur:icur + ni] for b in inputs], S, G, m, fmt, dither_seed=dither_seed)
+                icur += ni
                 drop = min(skip, len(streams[0])) if streams else 0
                 take = min(keep, (len(streams[0]) if streams else 0) - drop)
                 skip -= drop
@@ -366,20 +425,27 @@ class OfflineRenderer:
         if out_fmt is not None and int(num_streams) * int(channels_per_stream) != self.num_out:
             raise ValueError(f"Invalid stream layout; expected {self.num_out} channels in all.")
         bs = self.block_size
+        inres = getattr(self, "_inres", False) and bool(ins)
         total = int(num_frames) if num_frames is not None else (int(ins[0].shape[0]) if ins else 0)
+        if inres and num_frames is None:          # (the streams' length in ENGINE frames)
+            iinfo = self._rt.input_resample_read()
+            total = -((-total * iinfo["up"]) // iinfo["down"])
         if sample_time is not None:
             self._time = int(sample_time)
         listening = any(self._listeners.values()) and hasattr(self._rt, "event_window_blocks")
         w = max(1, int(self._rt.event_window_blocks())) * bs if listening else max(total, 1)
         parts = []
+        icur = 0                                  # input frames consumed so far
         for k in range(0, max(total, 1), w):
             m = min(w, total - k)
+            ni = self._rt.input_resample_frames(m) if inres else m
             x = []
             for a in ins:
-                seg = a[k:k + m]
-                if seg.shape[0] < m:      # (silence is all-zero bytes in every format)
-                    seg = np.concatenate([seg, np.zeros((m - seg.shape[0],) + a.shape[1:], dtype=a.dtype)])
+                seg = a[icur:icur + ni]
+                if seg.shape[0] < ni:     # (silence is all-zero bytes in every format)
+                    seg = np.concatenate([seg, np.zeros((ni - seg.shape[0],) + a.shape[1:], dtype=a.dtype)])
                 x.append(seg)
+            icur += ni
             parts.append(pcm_io(x, in_fmt, self.num_out, m, out_fmt, num_streams, channels_per_stream, dither_seed=dither_seed,
                                 want_float=want_float, sample_time=self._time))
             self._time += ((m + bs - 1) // bs) * bs
@@ -402,7 +468,9 @@ class OfflineRenderer:
         """RIFF/WAVE files through the graph into RIFF/WAVE files, ``chunk_frames`` (rounded to whole blocks) per engine call; the samples
         cross the host as they lie in the files and are converted on the GPU in both directions. ``in_paths``: one name or a list —
         the files' channels become the input channels in file order (files of one format, one channel count and the renderer's
-        sample rate). ``out_paths`` / ``channels_per_stream``: as ``write_wav``'s ``path``. ``num_frames``: frames to render, default
+        sample rate — or, with ``initialize(input_sample_rate=...)``, that rate: a file of F frames then renders ceil(F L / M) engine
+        frames, L / M = engine rate / input rate, and the input converter's latency is taken out with the others, to under half a
+        delivered frame). ``out_paths`` / ``channels_per_stream``: as ``write_wav``'s ``path``. ``num_frames``: frames to render, default
         the (longest) input's length; longer than that — a reverb's tail — renders the rest from silence. Returns the statistics
         (with the loudness meter on: ``integrated_lufs`` and ``true_peak_dbtp`` of the meter's programme so far included, as ``write_wav``;
         with the limiter on: ``limiter_max_reduction_db`` of this file)."""
@@ -426,20 +494,25 @@ class OfflineRenderer:
             for p in ins:
                 readers.append(WavReader(p))
             for r in readers:
-                if r.sample_rate != int(round(self.sample_rate)):
+                if r.sample_rate != int(round(getattr(self, "input_sample_rate", self.sample_rate))):
                     raise ValueError(f"sample rate {r.sample_rate} of an input file, the renderer runs at {int(round(self.sample_rate))}")
                 if (r.fmt, r.channels) != (readers[0].fmt, readers[0].channels):
                     raise ValueError(f"input files of one kind are expected: {readers[0].fmt} x {readers[0].channels} and {r.fmt} x {r.channels}")
             if sum(r.channels for r in readers) != self.num_in:
                 raise ValueError(f"Invalid input data; expected {self.num_in} channels in all.")
             bs = self.block_size
-            total, skip, keep = self._file_span(int(num_frames) if num_frames is not None else max([r.frames for r in readers], default=0))
+            inres = getattr(self, "_inres", False) and bool(readers)
+            if num_frames is not None or not inres:
+                total, skip, keep = self._file_span(int(num_frames) if num_frames is not None else max([r.frames for r in readers], default=0))
+            else:
+                total, skip, keep = self._file_span(max(r.frames for r in readers), input_frames=True)
             chunk = max(bs, (int(chunk_frames) // bs) * bs)
             writers = [WavWriter(p, fmt, G, self.output_sample_rate) for p in outs]
             in_fmt = readers[0].fmt if readers else "s16"
             for k in range(0, total, chunk):
                 m = min(chunk, total - k)
-                streams, st, _ = self.process_pcm_io([r.read(m) for r in readers], in_fmt, m, fmt, S, G, dither_seed=dither_seed)
+                ni = self._rt.input_resample_frames(m) if inres else m
+                streams, st, _ = self.process_pcm_io([r.read(ni) for r in readers], in_fmt, m, fmt, S, G, dither_seed=dither_seed)
                 drop = min(skip, len(streams[0])) if streams else 0
                 take = min(keep, (len(streams[0]) if streams else 0) - drop)
                 skip -= drop

@@ -78,6 +78,12 @@ def load_library() -> C.CDLL:
         lib.elemhip_resample_read.restype = C.c_int
         lib.elemhip_resample_reset.argtypes = [C.c_void_p]
         lib.elemhip_resample_reset.restype = C.c_int
+        lib.elemhip_input_resample_frames.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.elemhip_input_resample_frames.restype = C.c_int
+        lib.elemhip_input_resample_read.argtypes = [C.c_void_p, C.POINTER(_ResampleInfo)]
+        lib.elemhip_input_resample_read.restype = C.c_int
+        lib.elemhip_input_resample_reset.argtypes = [C.c_void_p]
+        lib.elemhip_input_resample_reset.restype = C.c_int
         lib.elemhip_limiter_read.argtypes = [C.c_void_p, C.POINTER(_LimiterInfo), _dp, C.POINTER(C.c_uint64), C.c_size_t]
         lib.elemhip_limiter_read.restype = C.c_int
         lib.elemhip_limiter_reset.argtypes = [C.c_void_p]
@@ -178,7 +184,9 @@ class Runtime(CRuntime):
 
         ``inputs``: float32 ``[num_inputs, num_frames]`` (or None); returns / fills ``out``: float32
         ``[num_outputs, num_frames]`` (C-contiguous rows). ``ceil(num_frames / block_size)`` full blocks are rendered. With option
-        ``resample_rate`` on, ``num_frames`` stays the rendered count and the rows hold ``resample_frames(num_frames)`` frames.
+        ``resample_rate`` on, ``num_frames`` stays the rendered count and the rows hold ``resample_frames(num_frames)`` frames. With
+        option ``input_rate`` on, ``inputs`` holds ``input_resample_frames(num_frames)`` frames at that rate; without ``num_frames``
+        the call renders as many frames as the inputs cover.
         """
         import numpy as np
         from ._cabi import _ptr_array
@@ -188,8 +196,7 @@ class Runtime(CRuntime):
             if a.ndim == 1:
                 a = a[None, :]
             rows = [a[i] for i in range(a.shape[0])]
-            if num_frames is None:
-                num_frames = a.shape[1]
+            num_frames = self._frames_for_inputs(a.shape[1], num_frames)
         if num_frames is None:
             num_frames = out.shape[1]
         n_out = self.resample_frames(num_frames)
@@ -225,8 +232,7 @@ class Runtime(CRuntime):
             if a.ndim == 1:
                 a = a[None, :]
             rows = [a[i] for i in range(a.shape[0])]
-            if num_frames is None:
-                num_frames = a.shape[1]
+            num_frames = self._frames_for_inputs(a.shape[1], num_frames)
         if num_frames is None:
             raise ValueError("num_frames is needed without inputs")
         n, S, G, code = int(num_frames), int(num_streams), int(channels_per_stream), pcm_format(fmt)
@@ -282,10 +288,11 @@ class Runtime(CRuntime):
         if num_frames is None:
             if not ins:
                 raise ValueError("num_frames is needed without inputs")
-            num_frames = ins[0].shape[0]
+            num_frames = self._frames_for_inputs(ins[0].shape[0], None)
         n = int(num_frames)
-        if ins and want is not None and in_channels_per_stream is None and ins[0].shape[0] < n:
-            raise ValueError(f"the input streams hold {ins[0].shape[0]} frames, {n} are asked for")
+        need = self.input_resample_frames(n) if ins else n      # input frames consumed (option "input_rate"; n while it is off)
+        if ins and want is not None and in_channels_per_stream is None and ins[0].shape[0] < need:
+            raise ValueError(f"the input streams hold {ins[0].shape[0]} frames, {need} are asked for")
         ip = (C.c_void_p * max(1, len(ins)))(*[C.c_void_p(a.ctypes.data) for a in ins])
         in_spec = _PcmInSpec(in_code, in_g)
         st = self.sample_time if sample_time is None else int(sample_time)
@@ -381,6 +388,54 @@ class Runtime(CRuntime):
             err = ElemHipError(f"elemhip_resample_reset failed: {describe(rc)} (code {rc})")
             err.code = rc
             raise err
+
+    def input_resample_frames(self, num_frames: int) -> int:
+        """``elemhip_input_resample_frames``: the input frames the next ``process_blocks_host`` / ``_pcm`` / ``_pcm_io`` call of
+        ``num_frames`` engine frames consumes — ``num_frames`` itself while option ``input_rate`` is off."""
+        got = C.c_size_t(0)
+        rc = self._lib.elemhip_input_resample_frames(self._h, int(num_frames), C.byref(got))
+        if rc != 0:
+            raise ElemHipError(f"elemhip_input_resample_frames failed: {describe(rc)} (code {rc})")
+        return int(got.value)
+
+    def input_resample_read(self) -> Dict[str, Any]:
+        """``elemhip_input_resample_read`` (option ``input_rate``): ``{'up', 'down', 'taps', 'latency_frames', 'frames_in',
+        'frames_out'}`` — engine rate / input rate = up / down in lowest terms, taps per engine frame, the filter's latency in ENGINE
+        frames, and the programme's clock: input frames consumed and engine frames rendered since the option was set or the last reset."""
+        info = _ResampleInfo()
+        rc = self._lib.elemhip_input_resample_read(self._h, C.byref(info))
+        if rc != 0:
+            err = ElemHipError(f"elemhip_input_resample_read failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return {k: int(getattr(info, k)) for k, _ in _ResampleInfo._fields_}
+
+    def input_resample_reset(self) -> None:
+        """``elemhip_input_resample_reset``: a new input programme (time 0, silence in front of it)."""
+        rc = self._lib.elemhip_input_resample_reset(self._h)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_input_resample_reset failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+
+    def _frames_for_inputs(self, have: int, num_frames: Optional[int]) -> int:
+        """The engine frames a call with ``have`` input frames renders: ``num_frames`` where it is given (checked against the inputs
+        while option ``input_rate`` is on), else the largest count whose need the inputs cover — ``have`` while the option is off."""
+        have = int(have)
+        if self._lib.elemhip_input_resample_read(self._h, None) != 0:      # off: as ever
+            return have if num_frames is None else int(num_frames)
+        if num_frames is not None:
+            need = self.input_resample_frames(num_frames)
+            if have < need:
+                raise ValueError(f"the inputs hold {have} frames, {int(num_frames)} engine frames need {need}")
+            return int(num_frames)
+        lo, hi = 0, 1                       # need(lo) <= have < need(hi); need() grows with the count
+        while self.input_resample_frames(hi) <= have:
+            lo, hi = hi, hi * 2
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if self.input_resample_frames(mid) <= have else (lo, mid)
+        return lo
 
     def limiter_read(self) -> Dict[str, Any]:
         """``elemhip_limiter_read`` (option ``limiter``): the plan — ``lookahead_frames`` D, ``latency_frames`` D + 6,

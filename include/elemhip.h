@@ -193,6 +193,28 @@ int elemhip_resample_frames(elemhip_t*, size_t numFrames, size_t* out);
 int elemhip_resample_read(elemhip_t*, elemhip_resample_info* info);
 int elemhip_resample_reset(elemhip_t*);
 
+/* EXTENSION (no counterpart in the reference): inputs at another sample rate, converted on the GPU (elementary_amd/csrc/resample_in.hip;
+ * the arithmetic: resample.h, the same prototype and tables as above with fin = hz and fout = the engine's rate). After
+ * elemhip_set_option(h, "input_rate", hz) — hz integral; 0 or the engine's own rate: off, the default — the inputs of
+ * elemhip_process_blocks_host, elemhip_process_blocks_pcm and elemhip_process_blocks_pcm_io, planar floats or interleaved PCM, arrive
+ * at hz: a kernel in front of every launch set's first render level decodes and converts them where the host-to-device copy left
+ * them, so only input-rate bytes cross the host link. numFrames stays in ENGINE frames; the input arrays and streams of such a call
+ * must hold elemhip_input_resample_frames(numFrames) frames. The engine pulls: with up / down = engine rate / hz in lowest terms, a
+ * call that renders the programme's engine frames [n0, n1) consumes the input frames [need(n0), need(n1)), need(0) = 0 and
+ * need(n) = floor((n - 1) down / up) + 1 — however a render is cut into calls and launch sets, the same bits. Engine frame n is the
+ * input at time (n - latency_frames) * down / up; frames in front of the programme are silence. The programme is the engine frames
+ * those calls rendered with inputs, in call order, since the option was set or elemhip_input_resample_reset; its channel count is that
+ * of its first call, a call with another count returns 6 (reset first), a call that fails starts a new programme. Code 6 for a rate
+ * without a plan, and nothing changes: not integral, up > 1024, more than 1024 taps, up / down > 8 or down / up > 8. Independent of
+ * "resample_rate", "limiter" and "loudness_meter": the frames delivered for a call are still elemhip_resample_frames(numFrames).
+ * elemhip_process and the device-resident elemhip_process_blocks take their inputs at the engine's rate as before.
+ *   elemhip_input_resample_frames  input frames the next host-buffer call of numFrames consumes (numFrames while the option is off)
+ *   elemhip_input_resample_read    the plan and the programme's clock (latency_frames and frames_out in engine frames); code 6 while off
+ *   elemhip_input_resample_reset   a new programme: time 0, silence in front of it; code 6 while the option is off */
+int elemhip_input_resample_frames(elemhip_t*, size_t numFrames, size_t* out);
+int elemhip_input_resample_read(elemhip_t*, elemhip_resample_info* info);
+int elemhip_input_resample_reset(elemhip_t*);
+
 /* EXTENSION (no counterpart in the reference): a static gain and a look-ahead true-peak limiter on the GPU (elementary_amd/csrc/limiter.hip;
  * the arithmetic: limiter.h). After elemhip_set_option(h, "limiter", 1) what elemhip_process_blocks_host, elemhip_process_blocks_pcm and
  * elemhip_process_blocks_pcm_io deliver — planar floats, packed streams, what the loudness meter meters — has passed, behind the
@@ -319,7 +341,7 @@ int  elemhip_sum_buses(int deviceOrdinal, void* hipStream, float* dst, const flo
  * into pinned host memory), "use_graph" / "graph_blocks" (per-block launch path replayed from a hipGraph), "stateless_rows",
  * "mixer_split", "pipeline_copies", "merge_phases", "pack_islands" / "pack_max" / "cu_count" (lane-packing of isomorphic
  * islands), "event_history_blocks" / "capture_history_blocks" (above, at elemhip_event_window_blocks), "loudness_meter" (above, at
- * elemhip_loudness_read), "resample_rate" (above, at elemhip_resample_frames), "limiter" /
+ * elemhip_loudness_read), "resample_rate" (above, at elemhip_resample_frames), "input_rate" (above, at elemhip_input_resample_frames), "limiter" /
  * "limiter_*" (above, at elemhip_limiter_read), "profile_launches", "time_batch". Unknown keys return code 6. */
 int  elemhip_set_option(elemhip_t*, const char* key, double value);
 

@@ -151,6 +151,11 @@ public:
     int resampleFrames(size_t numFrames, size_t* out) { return elemhip_resample_frames(h, numFrames, out); }
     int resampleRead(elemhip_resample_info* info) { return elemhip_resample_read(h, info); }
     int resampleReset() { return elemhip_resample_reset(h); }
+    // EXTENSION: inputs at another sample rate (setOption("input_rate", hz)): numFrames of the host-buffer render calls stays in
+    // engine frames, their input arrays and streams hold inputResampleFrames(numFrames) frames
+    int inputResampleFrames(size_t numFrames, size_t* out) { return elemhip_input_resample_frames(h, numFrames, out); }
+    int inputResampleRead(elemhip_resample_info* info) { return elemhip_input_resample_read(h, info); }
+    int inputResampleReset() { return elemhip_input_resample_reset(h); }
     // EXTENSION: gain and true-peak limiter on what the host-buffer render calls deliver (setOption("limiter", 1), "limiter_*")
     int limiterRead(elemhip_limiter_info* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity) {
         return elemhip_limiter_read(h, info, maxReduction, limitedFrames, capacity);
