@@ -9,6 +9,7 @@
 #include "../../include/elemhip.h"
 #include "engine.h"
 #include "launch.h"
+#include "flac_encode.h"
 
 using elemhip::Engine;
 using elemhip::Value;
@@ -194,6 +195,58 @@ int elemhip_limiter_read(elemhip_t* h, elemhip_limiter_info* info, double* maxRe
 }
 
 int elemhip_limiter_reset(elemhip_t* h) { return h ? h->engine.limiterReset() : elemhip::kInvalidInstructionFormat; }
+
+int elemhip_process_blocks_flac(elemhip_t* h, const void* const* inStreams, size_t nInStreams, const elemhip_pcm_in_spec* inSpec,
+                                void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams, const elemhip_flac_spec* spec,
+                                size_t numFrames, int64_t st, elemhip_pcm_channel_stats* stats) {
+    if (!h || !spec || (nInStreams && (!inStreams || !inSpec))) return elemhip::kInvalidInstructionFormat;
+    static_assert(sizeof(elemhip_flac_spec) == sizeof(Engine::FlacSpec), "same layout");
+    const Engine::PcmSource src{nInStreams ? inSpec->format : 0u, nInStreams ? inSpec->channels_per_stream : 0u, inStreams, nInStreams};
+    return h->engine.processBlocksFlac(src, outStreams, capacities, bytesOut, nOutStreams, *reinterpret_cast<const Engine::FlacSpec*>(spec), numFrames, st,
+                                       reinterpret_cast<Engine::PcmChannelStats*>(stats));
+}
+
+size_t elemhip_flac_bound(size_t frames, uint32_t channelsPerStream, uint32_t bits) { return (size_t)flac_encode::stream_bound(frames, channelsPerStream, bits); }
+
+int elemhip_flac_flush(elemhip_t* h, void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams) {
+    return h ? h->engine.flacFlush(outStreams, capacities, bytesOut, nOutStreams) : elemhip::kInvalidInstructionFormat;
+}
+
+int elemhip_flac_read(elemhip_t* h, elemhip_flac_info* info, elemhip_flac_stream_info* perStream, size_t capacity, uint32_t* frameBytes, size_t frameCap) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    static_assert(sizeof(elemhip_flac_stream_info) == sizeof(Engine::FlacStreamInfo), "same layout");
+    Engine::FlacInfo fi{};
+    const int rc = h->engine.flacRead(&fi, reinterpret_cast<Engine::FlacStreamInfo*>(perStream), capacity, frameBytes, frameCap);
+    if (info) {
+        info->flac_frame = fi.flacFrame; info->bits = fi.bits; info->channels_per_stream = fi.channelsPerStream; info->streams = fi.streams;
+        info->sample_rate = fi.sampleRate; info->flushed = fi.flushed; info->frames = fi.frames;
+    }
+    return rc;
+}
+
+int elemhip_flac_reset(elemhip_t* h) { return h ? h->engine.flacReset() : elemhip::kInvalidInstructionFormat; }
+
+int elemhip_flac_encode(const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t flacFrame, uint32_t bits, uint32_t sampleRate,
+                        uint32_t firstFrameNumber, int flush, uint8_t* out, size_t capacity, size_t* bytesOut, uint32_t* frameBytes, size_t frameCap,
+                        size_t* framesOut) {
+    namespace fe = flac_encode;
+    if (!fe::frame_ok(flacFrame) || !fe::bits_ok(bits) || channels == 0u || channels > fe::kMaxChannels || !bytesOut || (frames && !planar) || (capacity && !out))
+        return elemhip::kInvalidInstructionFormat;
+    const size_t count = frames / flacFrame + (flush && frames % flacFrame ? 1u : 0u);
+    if ((uint64_t)firstFrameNumber + count > 0x80000000ull || sampleRate > 1048575u) return elemhip::kInvalidPropertyValue;
+    if (frameBytes && frameCap < count) return elemhip::kInvalidPropertyValue;
+    const int32_t lim = 1 << (bits - 1u);
+    for (uint32_t c = 0; c < channels; ++c) {
+        if (frames && !planar[c]) return elemhip::kInvalidInstructionFormat;
+        for (size_t i = 0; i < frames; ++i) if (planar[c][i] < -lim || planar[c][i] >= lim) return elemhip::kInvalidPropertyValue;
+    }
+    size_t done = 0;
+    const size_t n = fe::encode_host(planar, channels, frames, flacFrame, bits, sampleRate, firstFrameNumber, flush != 0, out, capacity, frameBytes, &done);
+    if (n == (size_t)-1) return elemhip::kTooManyChannels;
+    *bytesOut = n;
+    if (framesOut) *framesOut = done;
+    return elemhip::kOk;
+}
 
 int elemhip_loudness_gate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
     if (!out || (channels && subBlocks && !meanSquares)) return elemhip::kInvalidInstructionFormat;

@@ -2,6 +2,7 @@
 // See engine.h for the mapping onto runtime/elem/Runtime.h. The other units behind engine.h: engine_nodes.cpp (instruction
 // interpreter and node table), engine_relay.cpp (event relay), engine_render.cpp (the per-block launch sequence and launch sets).
 #include "engine_impl.h"
+#include "flac_encode.h"
 #include "fft_frames.h"
 
 namespace elemhip {
@@ -191,6 +192,7 @@ Engine::~Engine() {
     resampleFree();
     inputResampleFree();
     limiterFree();
+    flacFree();
     if (ioStream) (void)hipStreamDestroy(ioStream);
     if (relayStream) { (void)hipStreamSynchronize(relayStream); (void)hipStreamDestroy(relayStream); }
     if (evRelay) (void)hipEventDestroy(evRelay);
@@ -534,6 +536,16 @@ int Engine::setOption(const std::string& key, double value) {
     // limiter.h: a static gain and a look-ahead true-peak limiter on what those calls deliver, behind the converter. Turning it on, or
     // changing a parameter while it is on, starts a new programme; off (the default) not one launch, allocation or byte differs.
     if (key.compare(0, 7, "limiter") == 0) return setLimiterOption(key, value);
+    // flac_encode.h: the block size (256, 512, 1024, 2048, 4096) and the sample size (16, 24) of FLAC delivery. A programme keeps the
+    // values it started with: while one is open another value is refused (flacReset first). No other call is touched.
+    if (key == "flac_frame" || key == "flac_bits") {
+        const bool frame = key == "flac_frame";
+        const uint32_t v = value >= 0.0 && value <= 65536.0 && value == std::floor(value) ? (uint32_t)value : 0u;
+        if (frame ? !flac_encode::frame_ok(v) : !flac_encode::bits_ok(v)) return kInvalidPropertyValue;
+        if (frame && flacStreams != 0u && v != flacFF) return kInvalidPropertyValue;
+        (frame ? flacFrameOpt : flacBitsOpt) = v;
+        return kOk;
+    }
     if (key == "batch_blocks") { batchBlocks = std::max(1, std::min(1024, (int)value)); return kOk; }      // blocks per multi-block launch (1 = off)
     if (key == "debug_build_delay_ms") { debugBuildDelayMs = std::max(0, (int)value); return kOk; }   // tests: stretches the unlocked part of a plan build
     if (key == "plan_cache") { planCache = std::max(0, std::min(2, (int)value)); islandCache.clear(); islandShapeCache.clear(); return kOk; }

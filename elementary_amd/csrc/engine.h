@@ -275,6 +275,22 @@ public:
     // maxReduction[group] (the largest d behind a delivered gain, 0 .. 1) / limitedFrames[group] (frames with g < 1): `capacity` entries each
     int limiterRead(LimiterInfo* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity);
     int limiterReset();
+    // FLAC delivery (flac_encode.h; options "flac_frame" 256 .. 4096, default 4096, and "flac_bits" 16 / 24): the host-buffer render
+    // delivered as RFC 9639 frames of a fixed block size, encoded on the GPU in the pack kernel's place (flac_encode.hip) — behind the
+    // converter and the limiter, next to the meter. The sample values are processBlocksPcm's codes for the same render. The programme is
+    // the frames FLAC calls delivered since creation or flacReset; FLAC frame j holds its frames [j F, (j + 1) F). A call returns the
+    // bytes of the frames it completed (bytesOut[s]; maybe none) and leaves the open frame's codes on the device; flacFlush encodes
+    // them as one short final frame, after which calls answer kInvalidPropertyValue until flacReset. spec.bits 0: the option's.
+    // spec.drop / spec.take: of the frames the call delivers, the first `drop` stay out of the programme and at most `take` enter it.
+    struct FlacSpec { uint32_t bits, channelsPerStream, dither, seed; uint64_t drop, take; };
+    struct FlacInfo { uint32_t flacFrame, bits, channelsPerStream, streams, sampleRate, flushed; uint64_t frames; };
+    struct FlacStreamInfo { uint64_t frames, totalSamples; uint32_t minFrameBytes, maxFrameBytes; };
+    int processBlocksFlac(const PcmSource& src, void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams,
+                          const FlacSpec& spec, size_t numFrames, int64_t sampleTime, PcmChannelStats* stats);
+    int flacFlush(void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams);
+    // perStream: `capacity` entries; frameBytes (may be null): [stream][frameCap], the byte length of every frame emitted so far
+    int flacRead(FlacInfo* info, FlacStreamInfo* perStream, size_t capacity, uint32_t* frameBytes, size_t frameCap);
+    int flacReset();
     // render `numBlocks` blocks with a HIP event pair around every kernel launch; msOut[l] = mean
     // duration of launch level l (l < numLevels), msOut[numLevels] = epilogue. Returns levels + 1.
     int timeLaunches(size_t nOut, size_t numBlocks, float* msOut, size_t cap);
@@ -490,9 +506,31 @@ private:
     void limiterFree();
     int growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], size_t& have, size_t want);
     int ensureRowTable(uint16_t*& dev, uint32_t& haveGroup, uint32_t& dwords, uint32_t group);
+    // FLAC delivery: the open frame's codes, the set's codes, the candidates' subframes and their bit counts on the device; the frames
+    // and their length table go through the packed halves (hPcm / dPcm), the payload copied on a stream of its own once the table is here
+    struct FlacJob {
+        FlacSpec spec;
+        void* const* streams; const size_t* caps; size_t* bytes; size_t nStreams;
+        std::vector<uint32_t> peakBits; std::vector<uint64_t> over, nonfinite;
+        uint32_t framesOf[2] = {0, 0};          // FLAC frames of the set in each half
+        uint64_t dropLeft = 0, takeLeft = 0;    // of the call's delivered frames still to come
+        size_t statsOff = 0, payloadOff = 0, stride = 0;
+    };
+    uint32_t flacFrameOpt = 4096, flacBitsOpt = 16;
+    uint32_t flacFF = 0, flacBits = 0, flacG = 0, flacStreams = 0, flacRate = 0, flacOpen = 0;      // the programme (flacStreams 0: none yet)
+    bool flacFlushed = false;
+    uint64_t flacFrames = 0, flacEmitted = 0;   // programme frames delivered; FLAC frames emitted per stream
+    std::vector<std::vector<uint32_t>> flacFrameBytes;
+    int32_t* dFlacCarry = nullptr; int32_t* dFlacCodes = nullptr; uint32_t* dFlacSlots = nullptr; uint32_t* dFlacSubBits = nullptr;
+    size_t flacCarryCh = 0, flacCodesCh = 0, flacCodesCap = 0, flacSlotCount = 0, flacSlotWords = 0;
+    hipStream_t flacStream = nullptr;
+    int ensureFlac(FlacJob& job, size_t setFrames);     // (`mu` held, both streams idle)
+    int flacResetLocked();
+    void flacFree();
+    int flacDeliver(FlacJob& job, int half);            // the table is in the pinned half: payload -> the caller's buffers
     // the set loop of processBlocksHost / processBlocksPcm (`pcm` null: planar floats only)
     int renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
-                       const PcmSource* src = nullptr);      // `src`: the inputs as PCM streams (`in` is null then)
+                       const PcmSource* src = nullptr, FlacJob* flac = nullptr);      // `src`: the inputs as PCM streams (`in` is null then)
     // enqueue `numBlocks` blocks on `stream` (no synchronise at the end): the body of processBlocks
     int enqueueBlocks(const float* inDev, size_t nIn, float* outDev, size_t nOut, size_t numBlocks, int64_t sampleTime);
 

@@ -2,6 +2,7 @@
 // kernel's host side and the measurement calls. Everything a render call reaches lives in this unit or inline in engine.h.
 #include "engine_impl.h"
 #include "pcm_unpack.h"
+#include "flac_encode.h"
 #include <functional>
 #include <thread>
 
@@ -1254,13 +1255,14 @@ int Engine::processBlocksPcmIo(const PcmSource& src, void* const* outStreams, si
 
 // (`out` may be null with `pcm`: nobody asked for the planar floats; with `src` the nIn input channels come from its streams, `in` is null)
 int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
-                           const PcmSource* src) {
+                           const PcmSource* src, FlacJob* flac) {
     const size_t bs = (size_t)blockSize;
     const uint32_t srcG = src ? src->channelsPerStream : 1u, srcFmt = src ? src->format : 0u;
     const size_t srcB = src ? pcm_pack::sample_bytes(srcFmt) : 0;
     const bool wantFloat = nOut > 0 && out != nullptr;
     const uint32_t pcmG = pcm ? pcm->spec.channelsPerStream : 1u, pcmFmt = pcm ? pcm->spec.format : 0u;
     const size_t pcmB = pcm ? pcm_pack::sample_bytes(pcmFmt) : 0;
+    const bool packed = pcm || flac;                 // (FLAC delivery stands where PCM delivery stands: nobody asked for the floats)
     const bool meter = loudnessOn && nOut > 0;       // option "loudness_meter": the delivered frames of every set go through the meter
     // option "resample_rate": what is delivered — floats, packed streams, the meter's frames — is the render converted to the delivery
     // rate; the pack kernel's time (the dither's key) is then the programme's OUTPUT frame index
@@ -1352,13 +1354,64 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         };
         auto inFail = [&]() { if (inres) { RenderGuard lock(*this); (void)inputResampleResetLocked(0); } };
         if (inres) { const int rc = inSync(true); if (rc != kOk) { resFail(); limFail(); if (meter) (void)meterSync(false); return rc; } }
+        // FLAC delivery: the open frame's codes come to the host too; the floats are quantised here and the header's scalar twin encodes
+        // every frame they complete — the kernel's functions, the kernel's bytes
+        std::vector<std::vector<int32_t>> flacCodes;
+        auto flacSync = [&](bool toHost) -> int {
+            RenderGuard lock(*this);
+            if (hipSetDevice(device) != hipSuccess) return kHipError;
+            if (toHost) { const int rc = ensureFlac(*flac, 0); if (rc != kOk) return rc; flacCodes.assign(nOut, std::vector<int32_t>(flacOpen)); }
+            HIP_OK(hipStreamSynchronize(stream));
+            for (size_t c = 0; c < nOut; ++c) {
+                int32_t* dev = dFlacCarry + c * flac_encode::kMaxFrame;
+                if (toHost) { if (flacOpen) HIP_OK(hipMemcpy(flacCodes[c].data(), dev, flacOpen * sizeof(int32_t), hipMemcpyDeviceToHost)); }
+                else if (!flacCodes[c].empty()) HIP_OK(hipMemcpy(dev, flacCodes[c].data(), flacCodes[c].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            }
+            if (!toHost) flacOpen = (uint32_t)flacCodes[0].size();
+            return kOk;
+        };
+        auto flacHost = [&](const float* got, size_t gotStride, size_t nd, int64_t gotTime) -> int {
+            std::lock_guard<std::mutex> lock(mu);
+            const uint64_t lead = std::min<uint64_t>(flac->dropLeft, nd), enter = std::min<uint64_t>(flac->takeLeft, nd - lead);
+            flac->dropLeft -= lead; flac->takeLeft -= enter;
+            const uint32_t G = flac->spec.channelsPerStream, bits = flac->spec.bits, ff = flacFF;
+            for (size_t c = 0; c < nOut; ++c) {
+                const uint32_t k0 = pcm_pack::channel_key(flac->spec.seed, (uint32_t)c);
+                pcm_pack::ChannelStats st{flac->peakBits[c], 0u, 0u};
+                for (size_t f = (size_t)lead; f < (size_t)(lead + enter); ++f) {
+                    const float x = got[c * gotStride + f];
+                    st = pcm_pack::stats_fold(x, st);
+                    flacCodes[c].push_back(pcm_pack::quantise(x, bits, flac->spec.dither ? pcm_pack::dither(k0, gotTime + (int64_t)f) : 0.0f));
+                }
+                flac->peakBits[c] = st.peakBits; flac->over[c] += st.over; flac->nonfinite[c] += st.nonfinite;
+            }
+            flacFrames += enter;
+            const size_t nF = flacCodes[0].size() / ff;
+            if (nF == 0) return kOk;
+            if (flacEmitted + nF > 0x7FFFFFFFull) return kInvariantViolation;
+            std::vector<uint32_t> lens(nF);
+            for (size_t s = 0; s < flac->nStreams; ++s) {
+                const int32_t* planar[flac_encode::kMaxChannels];
+                for (uint32_t g = 0; g < G; ++g) planar[g] = flacCodes[s * G + g].data();
+                size_t count = 0;
+                const size_t n = flac_encode::encode_host(planar, G, nF * ff, ff, bits, flacRate, (uint32_t)flacEmitted, false,
+                                                          static_cast<uint8_t*>(flac->streams[s]) + flac->bytes[s], flac->caps[s] - flac->bytes[s], lens.data(), &count);
+                if (n == (size_t)-1 || count != nF) return kInvariantViolation;
+                flac->bytes[s] += n;
+                flacFrameBytes[s].insert(flacFrameBytes[s].end(), lens.begin(), lens.end());
+            }
+            for (size_t c = 0; c < nOut; ++c) flacCodes[c].erase(flacCodes[c].begin(), flacCodes[c].begin() + (ptrdiff_t)(nF * ff));
+            flacEmitted += nF;
+            return kOk;
+        };
+        if (flac) { const int rc = flacSync(true); if (rc != kOk) { resFail(); limFail(); inFail(); if (meter) (void)meterSync(false); return rc; } }
         size_t inOff = 0;                       // input frames of this call consumed so far
         size_t outOff = 0;                      // delivered frames of this call so far
         for (size_t f0 = 0; f0 < numFrames; f0 += hb) {
             const size_t nf = std::min(hb, numFrames - f0);
             for (size_t c = 0; c < nIn; ++c) ip[c] = src ? nullptr : in[c] + f0;
             for (size_t c = 0; c < nOut; ++c) op[c] = wantFloat ? out[c] + f0 : nullptr;
-            if (nf < hb || pcm || meter || resamp || limit) {
+            if (nf < hb || packed || meter || resamp || limit) {
                 // the last, partly filled host block is still a whole block to the engine (offline-renderer/index.ts:104-131: inputs
                 // padded with zeros, the frames beyond the caller's arrays dropped); a PCM call renders every host block here
                 tailOut.assign(nOut * hb, 0.0f);
@@ -1421,16 +1474,21 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                     loudness::meter_host(loudPlan, meterState[c], got + c * gotStride, nd, loudFrames, [&](double ms) { loudSeries[c].push_back(ms); });
                 loudFrames += nd;
             }
-            if ((nf < hb || pcm || meter || resamp || limit) && wantFloat) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + at, got + c * gotStride, nd * sizeof(float));
+            if ((nf < hb || packed || meter || resamp || limit) && wantFloat) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + at, got + c * gotStride, nd * sizeof(float));
             if (pcm) {
                 // the floats are on the host: the header's scalar loop packs them — the kernel's functions, the kernel's bits
                 for (size_t s = 0; s < pcm->nStreams; ++s) sp[s] = static_cast<uint8_t*>(pcm->streams[s]) + at * pcmG * pcmB;
                 pcm_pack::pack_host(pcmFmt, pcmG, (uint32_t)pcm->nStreams, pcm->spec.dither != 0u, pcm->spec.seed, got, gotStride, nd,
                                     gotTime, sp.data(), pcm->peakBits.data(), pcm->over.data(), pcm->nonfinite.data());
             }
+            if (flac) {
+                const int rf = flacHost(got, gotStride, nd, gotTime);
+                if (rf != kOk) { if (meter) (void)meterSync(false); resFail(); limFail(); inFail(); return rf; }
+            }
             outOff += nd;
         }
         int rc = meter ? meterSync(false) : kOk;
+        if (flac) { const int rf = flacSync(false); if (rc == kOk) rc = rf; }
         if (resamp) { const int rr = resSync(false); if (rc == kOk) rc = rr; if (rc != kOk) resFail(); }
         if (limit) { const int rl = limSync(false); if (rc == kOk) rc = rl; if (rc != kOk) limFail(); }
         if (inres) { const int ri = inSync(false); if (rc == kOk) rc = ri; if (rc != kOk) inFail(); }
@@ -1483,7 +1541,12 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             rc = ensureLoudness(nOut, outCapFrames);
             if (rc != kOk) return rc;
         }
+        if (flac) {
+            rc = ensureFlac(*flac, outCapFrames);
+            if (rc != kOk) return rc;
+        }
     }
+    int flacRc = kOk;
     const size_t numSets = (numBlocks + setBlocks - 1) / setBlocks;
     // One thread copies ~10 GB/s; a set of many channels (C4: 128 outputs x 1024 blocks = 268 MB per 12.6 ms of rendering)
     // needs more than that to stay hidden behind the next set, so big sets are cut over a few threads.
@@ -1539,7 +1602,8 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         for (size_t c = 0; c < nOut; ++c)
             for (uint32_t j = 0; j < loudCountOf[k & 1]; ++j) loudSeries[c].push_back(sums[c * loudOutStride + j] / (double)loudPlan.hop);
     };
-    auto deliver = [&](size_t k) { if (wantFloat) { if (resamp) scatterConverted(k); else scatter(k); } if (pcm) deliverPcm(k); if (meter) deliverLoudness(k); };
+    auto deliver = [&](size_t k) { if (wantFloat) { if (resamp) scatterConverted(k); else scatter(k); } if (pcm) deliverPcm(k); if (meter) deliverLoudness(k);
+                                  if (flac && flacRc == kOk) flacRc = flacDeliver(*flac, (int)(k & 1)); };
     int result = kOk;
     size_t issued = 0, scattered = 0, outOff = 0;
     // a failing HIP call ends the loop; the tail below drains both streams, releases what was deferred and reports the code —
@@ -1685,6 +1749,32 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 HOST_TRY(launch_pcm_pack(stream, a, pcmFmt));
                 pcmCopy = statsOff + nOut * sizeof(pcm_pack::ChannelStats);
             }
+            if (flac) {
+                // the FLAC kernels in the pack kernel's place, on the same stream: the carried codes and the set's, quantised, behind one
+                // another per channel; every whole frame among them encoded and assembled; what is left over is the next set's carry.
+                // The codes, the slots and the carry are touched by this stream's kernels only, in order; the packed half was drained by
+                // the D2H of set k - 2 (evOut above) and its payload copy, which the host waited for before it delivered that set.
+                const uint64_t lead = std::min<uint64_t>(flac->dropLeft, valid), enter = std::min<uint64_t>(flac->takeLeft, valid - lead);
+                flac->dropLeft -= lead; flac->takeLeft -= enter;
+                const uint32_t ff = flacFF, total = flacOpen + (uint32_t)enter, nF = total / ff, rem = total % ff;
+                if (flacEmitted + nF > 0x7FFFFFFFull) { result = kInvariantViolation; break; }
+                flac->framesOf[half] = nF;
+                pcm_pack::ChannelStats* fst = reinterpret_cast<pcm_pack::ChannelStats*>(dPcm[half] + flac->statsOff);
+                HOST_TRY(hipMemsetAsync(fst, 0, nOut * sizeof(pcm_pack::ChannelStats), stream));
+                FlacStageArgs sa{};
+                sa.src = got; sa.carry = dFlacCarry; sa.codes = dFlacCodes; sa.stats = fst; sa.time0 = gotTime;
+                sa.blockSize = (uint32_t)bs; sa.numChannels = (uint32_t)nOut; sa.validFrames = (uint32_t)enter; sa.srcOffset = (uint32_t)lead; sa.open = flacOpen;
+                sa.cap = (uint32_t)flacCodesCap; sa.bits = flac->spec.bits; sa.dither = flac->spec.dither ? 1u : 0u; sa.seed = flac->spec.seed;
+                HOST_TRY(launch_flac_stage(stream, sa));
+                FlacEncodeArgs ea{};
+                ea.codes = dFlacCodes; ea.slots = dFlacSlots; ea.subBits = dFlacSubBits; ea.dst = dPcm[half] + flac->payloadOff;
+                ea.frameBytes = reinterpret_cast<uint32_t*>(dPcm[half]); ea.streamStride = flac->stride; ea.cap = (uint32_t)flacCodesCap;
+                ea.G = flac->spec.channelsPerStream; ea.numStreams = (uint32_t)flac->nStreams; ea.bits = flac->spec.bits; ea.flacFrame = ff; ea.n = ff;
+                ea.numFrames = nF; ea.slotWords = flac_encode::slot_words(ff, flac->spec.bits); ea.rate = flacRate; ea.firstNumber = (uint32_t)flacEmitted;
+                HOST_TRY(launch_flac_encode(stream, ea));
+                HOST_TRY(launch_flac_carry(stream, dFlacCodes, dFlacCarry, (uint32_t)nOut, (uint32_t)flacCodesCap, ff, nF * ff, rem));
+                flacOpen = rem; flacEmitted += nF; flacFrames += enter;
+            }
             if (meter) {
                 // the meter's kernels behind the set's last level too, next to the pack kernel: they read the same block. The state they
                 // carry lives on the device; the sums of the sub-blocks this set completes go to this half's small region, drained like
@@ -1700,8 +1790,13 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             }
             HOST_TRY(hipEventRecord(evRendered[half], stream));
             HOST_TRY(hipStreamWaitEvent(ioStream, evRendered[half], 0));
-            if (wantFloat || !pcm) { if (nOut && gotBlocks) HOST_TRY(hipMemcpyAsync(hStageOut[half], got, gotBlocks * nOut * bs * sizeof(float), hipMemcpyDeviceToHost, ioStream)); }
+            if (wantFloat || !packed) { if (nOut && gotBlocks) HOST_TRY(hipMemcpyAsync(hStageOut[half], got, gotBlocks * nOut * bs * sizeof(float), hipMemcpyDeviceToHost, ioStream)); }
             if (pcm) HOST_TRY(hipMemcpyAsync(hPcm[half], dPcm[half], pcmCopy, hipMemcpyDeviceToHost, ioStream));
+            if (flac) {     // the length table and the statistics; the frames follow once the table says how many bytes they are (flacDeliver)
+                const size_t tab = flac->nStreams * (size_t)flac->framesOf[half] * sizeof(uint32_t);
+                if (tab) HOST_TRY(hipMemcpyAsync(hPcm[half], dPcm[half], tab, hipMemcpyDeviceToHost, ioStream));
+                HOST_TRY(hipMemcpyAsync(hPcm[half] + flac->statsOff, dPcm[half] + flac->statsOff, nOut * sizeof(pcm_pack::ChannelStats), hipMemcpyDeviceToHost, ioStream));
+            }
             if (meter && loudCountOf[half]) HOST_TRY(hipMemcpyAsync(hLoudOut[half], dLoudOut[half], nOut * loudOutStride * sizeof(double), hipMemcpyDeviceToHost, ioStream));
             HOST_TRY(hipEventRecord(evOut[half], ioStream));
             issued = k + 1;
@@ -1710,6 +1805,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             HOST_TRY(hipEventSynchronize(evOut[(k - 1) & 1]));
             if (nOut) deliver(k - 1);
             scattered = k;
+            if (flacRc != kOk) { result = flacRc; break; }
         }
     }
 #undef HOST_TRY
@@ -1717,6 +1813,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         const size_t last = issued - 1;
         if (hipEventSynchronize(evOut[last & 1]) != hipSuccess) result = kHipError;
         else if (nOut) deliver(last);
+        if (flacRc != kOk) result = flacRc;
     }
     {
         RenderGuard lock(*this);

@@ -148,6 +148,29 @@ struct LimiterArgs {
     loudness::Plan  meter;          // the delivery rate's: its interpolator is the detector
 };
 hipError_t launch_limiter(hipStream_t s, const LimiterArgs& a);
+// ---- FLAC delivery (flac_encode.hip): behind the converter and the limiter, in the pack kernel's place, flac_encode.h ----
+struct FlacStageArgs {
+    const float*    src;            // the set's delivered frames, [block][numChannels][blockSize]: validFrames of them from srcOffset on
+    const int32_t*  carry;          // [numChannels][flacFrame]: the open frame's codes, `open` of them
+    int32_t*        codes;          // [numChannels][cap]: receives the carried codes, then the set's
+    pcm_pack::ChannelStats* stats;  // [numChannels], added into
+    int64_t         time0;          // sample time of frame 0 of `src` (the dither's key)
+    uint32_t        blockSize, numChannels, validFrames, open, cap, bits, dither, seed;
+    uint32_t        srcOffset;      // frames of `src` in front of the validFrames that stay out of the programme
+};
+hipError_t launch_flac_stage(hipStream_t s, const FlacStageArgs& a);
+// the codes behind the last whole frame become the next set's carry
+hipError_t launch_flac_carry(hipStream_t s, const int32_t* codes, int32_t* carry, uint32_t numChannels, uint32_t cap, uint32_t flacFrame, uint32_t from, uint32_t count);
+struct FlacEncodeArgs {
+    const int32_t*  codes;          // [numStreams * G][cap]
+    uint32_t*       slots;          // [numStreams][numFrames][candidates][slotWords]: the candidates' subframes, bit 0 = the top of word 0
+    uint32_t*       subBits;        // [numStreams][numFrames][candidates]
+    unsigned char*  dst;            // [stream] at `streamStride` bytes (a multiple of 16; the base 16-byte aligned): the frames back to back
+    uint32_t*       frameBytes;     // [numStreams][numFrames]
+    uint64_t        streamStride;
+    uint32_t        cap, G, numStreams, bits, flacFrame, n /* samples of every frame: flacFrame, or the flushed remainder */, numFrames, slotWords, rate, firstNumber;
+};
+hipError_t launch_flac_encode(hipStream_t s, const FlacEncodeArgs& a);      // the encode kernel, then the assemble kernel
 hipError_t launch_bus_sum(hipStream_t s, float* dst, const float* const* partials, uint32_t count, size_t n);   // dst = ((p0 + p1) + p2) + ... (rank order)
 
 } // namespace elemhip

@@ -14,7 +14,8 @@ from .wav import WavReader
 
 def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, target_lufs: float = -14.0, ceiling_dbtp: float = -1.0,
                fmt: str = "s24", block_size: int = 512, oversample: int = 1, **limiter) -> Dict[str, Any]:
-    """``in_path`` -> ``out_path`` (format ``fmt``, the input's rate and channel count) at ``target_lufs`` integrated loudness under a
+    """``in_path`` -> ``out_path`` (format ``fmt`` — 's16', 's24', 'f32', or 'flac16' / 'flac24' for a FLAC file encoded on the GPU —
+    the input's rate and channel count) at ``target_lufs`` integrated loudness under a
     true-peak ceiling of ``ceiling_dbtp``. ``limiter``: further limiter parameters (``lookahead_ms``, ``release_ms``, ``link``).
     Returns ``{'input_lufs', 'input_true_peak_dbtp', 'output_lufs', 'output_true_peak_dbtp', 'gain_db', 'max_reduction_db',
     'limited_frames', 'over', 'nonfinite'}``. Where the limiter worked the output is quieter than the target by what it took away; the

@@ -252,6 +252,141 @@ class OfflineRenderer:
         planar = np.concatenate([p[2] for p in parts], axis=1) if want_float else None
         return streams, stats, planar
 
+    def process_flac(self, inputs: Sequence[np.ndarray], num_streams: int, channels_per_stream: int, num_frames: int, bits: int = 16,
+                     dither_seed: Optional[int] = None, sample_time: Optional[int] = None, drop: int = 0, take: Optional[int] = None, in_fmt=None):
+        """``process_pcm`` delivered as FLAC frames encoded on the GPU (``Runtime.process_blocks_flac``): returns ``(streams, stats)``,
+        one ``bytes`` per stream with the whole FLAC frames this call completed in the engine's FLAC programme — the open frame stays on
+        the device until the next call or ``flac_flush()``. Decoded, the samples are ``process_pcm``'s s16 / s24 codes for the same
+        render. With listeners attached the render walks ``event_window_blocks()`` windows with the blockwise relay between them; the
+        bytes are those of one call. ``drop`` / ``take``: of the frames delivered, the first ``drop`` stay out of the programme and at
+        most ``take`` enter it. ``in_fmt``: the inputs are PCM stream arrays in that format (``process_pcm_io``'s), not planar floats."""
+        flac = getattr(self._rt, "process_blocks_flac", None)
+        if flac is None:
+            raise RuntimeError("this engine has no FLAC delivery (process_blocks_flac)")
+        if in_fmt is None and len(inputs) != self.num_in:
+            raise ValueError(f"Invalid input data; expected {self.num_in} buffers.")
+        if int(num_streams) * int(channels_per_stream) != self.num_out:
+            raise ValueError(f"Invalid stream layout; expected {self.num_out} channels in all.")
+        bs, total = self.block_size, int(num_frames)
+        if sample_time is not None:
+            self._time = int(sample_time)
+        listening = any(self._listeners.values()) and hasattr(self._rt, "event_window_blocks")
+        w = max(1, int(self._rt.event_window_blocks())) * bs if listening else max(total, 1)
+        inres = getattr(self, "_inres", False) and self.num_in > 0
+        ins = [np.asarray(a) for a in inputs] if in_fmt is not None else None
+        parts, icur = [], 0
+        drop_left, take_left = int(drop), None if take is None else int(take)
+        for k in range(0, max(total, 1), w):
+            m = min(w, total - k)
+            x = None
+            if ins is not None:
+                ni = self._rt.input_resample_frames(m) if inres else m
+                x = []
+                for a in ins:
+                    seg = a[icur:icur + ni]
+                    if seg.shape[0] < ni:
+                        seg = np.concatenate([seg, np.zeros((ni - seg.shape[0],) + a.shape[1:], dtype=a.dtype)])
+                    x.append(seg)
+                icur += ni
+            elif self.num_in:
+                x, icur = self._pull(inputs, icur, m)
+            nd = self._rt.resample_frames(m)
+            d = min(drop_left, nd)
+            t = nd - d if take_left is None else min(take_left, nd - d)
+            drop_left -= d
+            if take_left is not None:
+                take_left -= t
+            parts.append(flac(x, num_streams, channels_per_stream, m, bits, dither_seed=dither_seed, sample_time=self._time, drop=d, take=t, in_fmt=in_fmt))
+            self._time += ((m + bs - 1) // bs) * bs
+            events = self._rt.process_queued_events(blockwise=True) if listening else self._rt.process_queued_events()
+            for kind, payload in events:
+                for cb in self._listeners.get(kind, []):
+                    cb(payload)
+        if len(parts) == 1:
+            return parts[0]
+        streams = [b"".join(p[0][s] for p in parts) for s in range(int(num_streams))]
+        stats = {"peak": np.max([p[1]["peak"] for p in parts], axis=0), "over": np.sum([p[1]["over"] for p in parts], axis=0, dtype=np.uint64),
+                 "nonfinite": np.sum([p[1]["nonfinite"] for p in parts], axis=0, dtype=np.uint64)}
+        return streams, stats
+
+    def flac_flush(self):
+        """The open remainder of the FLAC programme as one final short frame per stream; the programme is closed until ``flac_reset()``."""
+        return self._rt.flac_flush()
+
+    def flac_reset(self) -> None:
+        """A new FLAC programme: nothing open, frame number 0."""
+        self._rt.flac_reset()
+
+    def flac(self) -> Dict[str, Any]:
+        """The FLAC programme so far (``Runtime.flac_read``): per stream the frames emitted, their byte lengths and the STREAMINFO fields."""
+        return self._rt.flac_read()
+
+    def _stream_paths(self, path, S: int):
+        if isinstance(path, (list, tuple)):
+            paths = [str(p) for p in path]
+        elif S == 1:
+            paths = [str(path)]
+        else:
+            if "{}" not in str(path):
+                raise ValueError("several streams need a list of paths or a path with {} for the stream number")
+            paths = [str(path).format(s) for s in range(S)]
+        if len(paths) != S:
+            raise ValueError(f"{S} streams need {S} paths")
+        return paths
+
+    def _flac_files(self, paths, pull, total: int, skip: int, keep: int, bits: int, S: int, G: int, dither_seed, chunk: int, in_fmt=None):
+        """``total`` frames rendered in chunks into one FLAC file per stream: a new FLAC programme that leaves the first ``skip``
+        delivered frames out and holds ``keep`` (frames cannot be cut on the host: the engine leaves them out in front of the
+        encoder), flushed at the end; STREAMINFO patched from ``flac_read``. ``pull(m)``: the inputs of the next ``m`` engine frames."""
+        from .flac import FlacWriter
+        self._rt.flac_reset()
+        frame = int(self._rt.flac_read()["flac_frame"])
+        writers = [FlacWriter(p, bits, G, self.output_sample_rate, frame) for p in paths]
+        stats = None
+        try:
+            for k in range(0, total, chunk):
+                m = min(chunk, total - k)
+                nd = self._rt.resample_frames(m)
+                drop = min(skip, nd)
+                take = min(keep, nd - drop)
+                skip -= drop
+                keep -= take
+                streams, st = self.process_flac(pull(m), S, G, m, bits, dither_seed=dither_seed, drop=drop, take=take, in_fmt=in_fmt)
+                for wtr, data in zip(writers, streams):
+                    wtr.write(data)
+                stats = st if stats is None else {"peak": np.maximum(stats["peak"], st["peak"]), "over": stats["over"] + st["over"],
+                                                  "nonfinite": stats["nonfinite"] + st["nonfinite"]}
+            for wtr, data in zip(writers, self._rt.flac_flush()):
+                wtr.write(data)
+            got = self._rt.flac_read()
+            for s, wtr in enumerate(writers):
+                wtr.patch(got["stream_frames"][s], got["min_frame_bytes"][s], got["max_frame_bytes"][s], got["total_samples"][s])
+        finally:
+            for wtr in writers:
+                wtr.close()
+        return self._with_loudness(stats)
+
+    def write_flac(self, path, inputs: Sequence[np.ndarray], num_frames: int, bits: int = 16, channels_per_stream: Optional[int] = None,
+                   dither_seed: Optional[int] = None, chunk_frames: int = 1 << 20):
+        """``write_wav`` into FLAC files (16 or 24 ``bits``), encoded on the GPU: one file per stream of ``channels_per_stream`` channels
+        (1 .. 8; default all output channels in one file), block size = option ``flac_frame``. The samples a decoder gets back are
+        those of ``write_wav`` in 's16' / 's24' with the same ``dither_seed``. The STREAMINFO MD5 is all zero ("not computed"): the
+        unencoded samples never reach the host. Returns the statistics as ``write_wav`` does, over the frames in the files."""
+        G = self.num_out if channels_per_stream is None else int(channels_per_stream)
+        S = self.num_out // max(G, 1)
+        paths = self._stream_paths(path, S)
+        bs = self.block_size
+        total, skip, keep = self._file_span(num_frames)
+        chunk = max(bs, (int(chunk_frames) // bs) * bs)
+        cursor = [0]
+
+        def pull(m):
+            ni = self._rt.input_resample_frames(m) if getattr(self, "_inres", False) and self.num_in else m
+            x = [np.asarray(b)[cursor[0]:cursor[0] + ni] for b in inputs]
+            cursor[0] += ni
+            return x
+        return self._flac_files(paths, pull, total, skip, keep, int(bits), S, G, dither_seed, chunk)
+
     def loudness(self, weights=None, programmes=None):
         """What the loudness meter (``initialize(loudness_meter=True)``) has measured since the renderer was made or
         ``loudness_reset()``: ``{'integrated_lufs', 'momentary_max_lufs', 'short_term_max_lufs',
@@ -466,7 +601,8 @@ class OfflineRenderer:
     def process_wav(self, in_paths, out_paths, out_fmt="s16", channels_per_stream: Optional[int] = None, num_frames: Optional[int] = None,
                     dither_seed: Optional[int] = None, chunk_frames: int = 1 << 20):
         """RIFF/WAVE files through the graph into RIFF/WAVE files, ``chunk_frames`` (rounded to whole blocks) per engine call; the samples
-        cross the host as they lie in the files and are converted on the GPU in both directions. ``in_paths``: one name or a list —
+        cross the host as they lie in the files and are converted on the GPU in both directions (``out_fmt`` 'flac16' / 'flac24': FLAC
+        files instead, encoded on the GPU — ``write_flac``'s). ``in_paths``: one name or a list —
         the files' channels become the input channels in file order (files of one format, one channel count and the renderer's
         sample rate — or, with ``initialize(input_sample_rate=...)``, that rate: a file of F frames then renders ceil(F L / M) engine
         frames, L / M = engine rate / input rate, and the input converter's latency is taken out with the others, to under half a
@@ -489,6 +625,7 @@ class OfflineRenderer:
         if len(outs) != S:
             raise ValueError(f"{S} streams need {S} paths")
         fmt = out_fmt if isinstance(out_fmt, str) else {1: "s16", 2: "s24", 3: "f32"}[int(out_fmt)]
+        flac_bits = {"flac16": 16, "flac24": 24}.get(fmt.lower())
         readers, writers, stats = [], [], None
         try:
             for p in ins:
@@ -507,8 +644,12 @@ class OfflineRenderer:
             else:
                 total, skip, keep = self._file_span(max(r.frames for r in readers), input_frames=True)
             chunk = max(bs, (int(chunk_frames) // bs) * bs)
-            writers = [WavWriter(p, fmt, G, self.output_sample_rate) for p in outs]
             in_fmt = readers[0].fmt if readers else "s16"
+            if flac_bits is not None:         # FLAC files: encoded on the GPU, the latencies left out in front of the encoder
+                def pull(m):
+                    return [r.read(self._rt.input_resample_frames(m) if inres else m) for r in readers]
+                return self._flac_files(outs, pull, total, skip, keep, flac_bits, S, G, dither_seed, chunk, in_fmt=in_fmt if readers else None)
+            writers = [WavWriter(p, fmt, G, self.output_sample_rate) for p in outs]
             for k in range(0, total, chunk):
                 m = min(chunk, total - k)
                 ni = self._rt.input_resample_frames(m) if inres else m

@@ -88,6 +88,21 @@ def load_library() -> C.CDLL:
         lib.elemhip_limiter_read.restype = C.c_int
         lib.elemhip_limiter_reset.argtypes = [C.c_void_p]
         lib.elemhip_limiter_reset.restype = C.c_int
+        _vpp, _szp, _u32p = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)
+        lib.elemhip_process_blocks_flac.argtypes = [C.c_void_p, _vpp, C.c_size_t, C.POINTER(_PcmInSpec), _vpp, _szp, _szp, C.c_size_t,
+                                                    C.POINTER(_FlacSpec), C.c_size_t, C.c_int64, C.POINTER(_PcmChannelStats)]
+        lib.elemhip_process_blocks_flac.restype = C.c_int
+        lib.elemhip_flac_bound.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32]
+        lib.elemhip_flac_bound.restype = C.c_size_t
+        lib.elemhip_flac_flush.argtypes = [C.c_void_p, _vpp, _szp, _szp, C.c_size_t]
+        lib.elemhip_flac_flush.restype = C.c_int
+        lib.elemhip_flac_read.argtypes = [C.c_void_p, C.POINTER(_FlacInfo), C.POINTER(_FlacStreamInfo), C.c_size_t, _u32p, C.c_size_t]
+        lib.elemhip_flac_read.restype = C.c_int
+        lib.elemhip_flac_reset.argtypes = [C.c_void_p]
+        lib.elemhip_flac_reset.restype = C.c_int
+        lib.elemhip_flac_encode.argtypes = [C.POINTER(C.POINTER(C.c_int32)), C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                            C.POINTER(C.c_uint8), C.c_size_t, _szp, _u32p, C.c_size_t, _szp]
+        lib.elemhip_flac_encode.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -116,6 +131,45 @@ class _ResampleInfo(C.Structure):
 class _LimiterInfo(C.Structure):
     _fields_ = [("lookahead_frames", C.c_uint32), ("latency_frames", C.c_uint32), ("release_frames", C.c_uint32), ("link", C.c_uint32),
                 ("groups", C.c_uint32), ("reserved", C.c_uint32), ("frames", C.c_uint64)]
+
+
+class _FlacSpec(C.Structure):
+    _fields_ = [("bits", C.c_uint32), ("channels_per_stream", C.c_uint32), ("dither", C.c_uint32), ("seed", C.c_uint32),
+                ("drop", C.c_uint64), ("take", C.c_uint64)]
+
+
+class _FlacInfo(C.Structure):
+    _fields_ = [("flac_frame", C.c_uint32), ("bits", C.c_uint32), ("channels_per_stream", C.c_uint32), ("streams", C.c_uint32),
+                ("sample_rate", C.c_uint32), ("flushed", C.c_uint32), ("frames", C.c_uint64)]
+
+
+class _FlacStreamInfo(C.Structure):
+    _fields_ = [("frames", C.c_uint64), ("total_samples", C.c_uint64), ("min_frame_bytes", C.c_uint32), ("max_frame_bytes", C.c_uint32)]
+
+
+def flac_encode(codes, bits: int = 16, flac_frame: int = 4096, sample_rate: int = 44100, first_frame_number: int = 0, flush: bool = True):
+    """``elemhip_flac_encode``: the scalar twin of the FLAC kernels, pure host arithmetic — ``codes`` int32 ``[channels, frames]`` (one
+    stream) -> ``(frame bytes back to back, uint32 array of the frames' byte lengths)``. Whole frames of ``flac_frame``; with ``flush``
+    the remainder as one short final frame."""
+    import numpy as np
+    lib = load_library()
+    a = np.ascontiguousarray(codes, dtype=np.int32)
+    if a.ndim == 1:
+        a = a[None, :]
+    ch, n = int(a.shape[0]), int(a.shape[1])
+    cap = int(lib.elemhip_flac_bound(n, max(ch, 1), int(bits)))
+    out = np.zeros(cap, dtype=np.uint8)
+    count = n // max(int(flac_frame), 1) + 2
+    lens = np.zeros(count, dtype=np.uint32)
+    rows = (C.POINTER(C.c_int32) * max(1, ch))(*[a[c].ctypes.data_as(C.POINTER(C.c_int32)) for c in range(ch)])
+    nbytes, nframes = C.c_size_t(0), C.c_size_t(0)
+    rc = lib.elemhip_flac_encode(rows, ch, n, int(flac_frame), int(bits), int(sample_rate), int(first_frame_number), 1 if flush else 0,
+                                 out.ctypes.data_as(C.POINTER(C.c_uint8)), cap, C.byref(nbytes), lens.ctypes.data_as(C.POINTER(C.c_uint32)), count, C.byref(nframes))
+    if rc != 0:
+        err = ElemHipError(f"elemhip_flac_encode failed: {describe(rc)} (code {rc})")
+        err.code = rc
+        raise err
+    return out[:nbytes.value].tobytes(), lens[:nframes.value].copy()
 
 
 class _LoudnessResult(C.Structure):
@@ -325,6 +379,120 @@ class Runtime(CRuntime):
         if sample_time is None:
             self.sample_time += ((n + self.block_size - 1) // self.block_size) * self.block_size
         return result
+
+    def process_blocks_flac(self, inputs, num_streams: int, channels_per_stream: int, num_frames: Optional[int] = None, bits: Optional[int] = None,
+                            dither_seed: Optional[int] = None, sample_time: Optional[int] = None, drop: int = 0, take: Optional[int] = None,
+                            in_fmt=None):
+        """``elemhip_process_blocks_flac``: the offline block loop delivered as FLAC frames, encoded on the GPU.
+
+        The ``num_streams * channels_per_stream`` output channels (laid out as in ``process_blocks_pcm``) come back as one ``bytes``
+        per stream: the whole FLAC frames this call completed in the programme (``flac_reset`` .. ``flac_flush``), possibly empty —
+        the open frame's samples stay on the device for the next call. Decoded, the samples are the s16 / s24 codes
+        ``process_blocks_pcm`` delivers for the same render, ``dither_seed`` and ``sample_time``. ``bits``: 16 or 24 (None: option
+        ``flac_bits``); the block size is option ``flac_frame``. ``inputs``: float32 ``[num_inputs, frames]`` (or None), or — with
+        ``in_fmt`` — a list of PCM stream arrays as ``process_blocks_pcm_io`` takes them. ``drop`` / ``take``: of the frames this call
+        delivers, the first ``drop`` stay out of the programme and at most ``take`` enter it (a file that leaves a converter's or the
+        limiter's latency out: frames cannot be cut on the host). Returns ``(streams, stats)``, ``stats`` over the frames that entered."""
+        import numpy as np
+        ins, in_code, in_g = [], 3, 1
+        if inputs is not None and in_fmt is None:
+            a = np.ascontiguousarray(inputs, dtype=np.float32)
+            if a.ndim == 1:
+                a = a[None, :]
+            ins = [a[i] for i in range(a.shape[0])]
+            num_frames = self._frames_for_inputs(a.shape[1], num_frames)
+        elif inputs is not None:
+            in_code = pcm_format(in_fmt)
+            ins = [np.ascontiguousarray(a) for a in inputs]
+            in_g = int(ins[0].shape[1]) if ins and ins[0].ndim > 1 else 1
+            if num_frames is None and ins:
+                num_frames = self._frames_for_inputs(ins[0].shape[0], None)
+        if num_frames is None:
+            raise ValueError("num_frames is needed without inputs")
+        n, S, G = int(num_frames), int(num_streams), int(channels_per_stream)
+        b = int(bits) if bits is not None else 0
+        nd = self.resample_frames(n)
+        cap = int(self._lib.elemhip_flac_bound(nd, max(G, 1), b if b in (16, 24) else 24))
+        bufs = [np.empty(cap, dtype=np.uint8) for _ in range(S)]
+        sp = (C.c_void_p * max(1, S))(*[C.c_void_p(a.ctypes.data) for a in bufs])
+        caps = (C.c_size_t * max(1, S))(*([cap] * S))
+        got = (C.c_size_t * max(1, S))()
+        ip = (C.c_void_p * max(1, len(ins)))(*[C.c_void_p(a.ctypes.data) for a in ins])
+        in_spec = _PcmInSpec(in_code, in_g)
+        stats = (_PcmChannelStats * max(1, S * G))()
+        spec = _FlacSpec(b, G, 0 if dither_seed is None else 1, 0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFF,
+                         int(drop), 0xFFFFFFFFFFFFFFFF if take is None else int(take))
+        st = self.sample_time if sample_time is None else int(sample_time)
+        rc = self._lib.elemhip_process_blocks_flac(self._h, ip, len(ins), C.byref(in_spec), sp, caps, got, S, C.byref(spec), n, st, stats)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_process_blocks_flac failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        if sample_time is None:
+            self.sample_time += ((n + self.block_size - 1) // self.block_size) * self.block_size
+        out_stats = {"peak": np.array([stats[c].peak for c in range(S * G)], dtype=np.float32),
+                     "over": np.array([stats[c].over for c in range(S * G)], dtype=np.uint64),
+                     "nonfinite": np.array([stats[c].nonfinite for c in range(S * G)], dtype=np.uint64)}
+        return [bufs[s][:got[s]].tobytes() for s in range(S)], out_stats
+
+    def flac_read(self) -> Dict[str, Any]:
+        """``elemhip_flac_read``: the FLAC programme so far — ``{'flac_frame', 'bits', 'channels_per_stream', 'streams', 'sample_rate',
+        'flushed', 'frames', 'stream_frames', 'total_samples', 'min_frame_bytes', 'max_frame_bytes', 'frame_bytes'}``: the last five
+        one entry per stream (the STREAMINFO fields; ``frame_bytes`` a uint32 array of every frame's byte length)."""
+        import numpy as np
+        info = _FlacInfo()
+        rc = self._lib.elemhip_flac_read(self._h, C.byref(info), None, 0, None, 0)
+        S = int(info.streams)
+        per = (_FlacStreamInfo * max(1, S))()
+        table = np.zeros((max(1, S), 1), dtype=np.uint32)
+        for _ in range(8):
+            if rc != 0 or S == 0:
+                break
+            rc = self._lib.elemhip_flac_read(self._h, C.byref(info), per, S, None, 0)
+            if rc != 0:
+                break
+            cap = max([int(per[s].frames) for s in range(S)] + [1])
+            table = np.zeros((S, cap), dtype=np.uint32)
+            rc = self._lib.elemhip_flac_read(self._h, C.byref(info), per, S, table.ctypes.data_as(C.POINTER(C.c_uint32)), cap)
+            if rc != 6:
+                break
+            rc = 0          # (another thread rendered in between: size the table again)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_flac_read failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return {"flac_frame": int(info.flac_frame), "bits": int(info.bits), "channels_per_stream": int(info.channels_per_stream), "streams": S,
+                "sample_rate": int(info.sample_rate), "flushed": bool(info.flushed), "frames": int(info.frames),
+                "stream_frames": [int(per[s].frames) for s in range(S)], "total_samples": [int(per[s].total_samples) for s in range(S)],
+                "min_frame_bytes": [int(per[s].min_frame_bytes) for s in range(S)], "max_frame_bytes": [int(per[s].max_frame_bytes) for s in range(S)],
+                "frame_bytes": [table[s, :int(per[s].frames)].copy() for s in range(S)]}
+
+    def flac_flush(self):
+        """``elemhip_flac_flush``: the open remainder as one final short frame per stream (``b''`` where nothing is open); the programme
+        is closed — further FLAC calls fail with code 6 until ``flac_reset``."""
+        import numpy as np
+        info = _FlacInfo()
+        self._lib.elemhip_flac_read(self._h, C.byref(info), None, 0, None, 0)
+        S, G, b = int(info.streams), max(1, int(info.channels_per_stream)), int(info.bits)
+        cap = int(self._lib.elemhip_flac_bound(0, G, b if b in (16, 24) else 24))
+        bufs = [np.empty(cap, dtype=np.uint8) for _ in range(S)]
+        sp = (C.c_void_p * max(1, S))(*[C.c_void_p(a.ctypes.data) for a in bufs])
+        caps = (C.c_size_t * max(1, S))(*([cap] * S))
+        got = (C.c_size_t * max(1, S))()
+        rc = self._lib.elemhip_flac_flush(self._h, sp, caps, got, S)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_flac_flush failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return [bufs[s][:got[s]].tobytes() for s in range(S)]
+
+    def flac_reset(self) -> None:
+        """``elemhip_flac_reset``: a new FLAC programme — nothing open, frame number 0."""
+        rc = self._lib.elemhip_flac_reset(self._h)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_flac_reset failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
 
     def loudness_read(self) -> Dict[str, Any]:
         """``elemhip_loudness_read`` (option ``loudness_meter``): the programme metered so far — ``{'channels', 'sub_blocks', 'hop',

@@ -236,6 +236,51 @@ typedef struct elemhip_limiter_info { uint32_t lookahead_frames, latency_frames,
 int elemhip_limiter_read(elemhip_t*, elemhip_limiter_info* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity);
 int elemhip_limiter_reset(elemhip_t*);
 
+/* EXTENSION (no counterpart in the reference): the same render delivered as FLAC, encoded on the GPU in the pack kernel's place
+ * (elementary_amd/csrc/flac_encode.hip; the arithmetic and the decision rules: flac_encode.h) — behind the delivery-rate converter and
+ * the limiter, next to the meter. RFC 9639 "subset" streams of a fixed block size (option "flac_frame": 256, 512, 1024, 2048 or 4096,
+ * the default) with 16 or 24 bits (spec.bits, or option "flac_bits" where that is 0) and 1 .. 8 channels per stream; nOutStreams *
+ * channels_per_stream = the output channels, laid out as for elemhip_process_blocks_pcm. The sample values are exactly the s16 / s24
+ * codes elemhip_process_blocks_pcm delivers for the same render, dither and seed: decoding the stream gives them back, sample for sample.
+ * Subframes are CONSTANT, VERBATIM or FIXED of order 0 .. 4 with partitioned Rice residuals (escape partitions allowed), two-channel
+ * streams choose per frame among independent, left/side, side/right and mid/side; every choice is made on exact bit counts, so no
+ * subframe is longer than its VERBATIM form, and the bytes are the same on the GPU and in elemhip_flac_encode.
+ * The programme is the frames these calls delivered since creation or elemhip_flac_reset, in call order; FLAC frame j holds programme
+ * frames [j F, (j + 1) F). A call returns the bytes of the FLAC frames it completed (bytesOut[s], possibly 0) and leaves the open
+ * frame's codes on the device, so the bytes of a render do not depend on how it is cut into calls, relay windows or launch sets.
+ * The inputs are those of elemhip_process_blocks_pcm_io (planar floats: format 3 with channels_per_stream 1). Every capacities[s] must
+ * be at least elemhip_flac_bound(frames delivered, channels_per_stream, bits), else code 103. Codes: 8 for channels_per_stream 0 or
+ * above 8, bits other than 16 / 24 or NULL buffers; 6 after elemhip_flac_flush, or where the call's shape (streams, channels, bits,
+ * delivery rate) is not the open programme's; 101 on a dry handle. A call that fails starts a new programme.
+ * spec.drop / spec.take: of the frames the call delivers, the first `drop` stay out of the programme and at most `take` enter it —
+ * how a file leaves the converters' and the limiter's latency out, since frames cannot be cut on the host. The dither stays keyed on
+ * the absolute frame, the statistics cover the frames that entered.
+ *   elemhip_flac_flush   the open remainder as one final short frame per stream (none where nothing is open); the programme is closed:
+ *                        further FLAC calls answer 6 until elemhip_flac_reset
+ *   elemhip_flac_read    the programme: info, and per stream (capacity entries) the frames emitted, the samples they hold and the
+ *                        smallest / largest frame in bytes — the STREAMINFO fields; frameBytes (NULL, or [stream][frameCap]): every
+ *                        frame's byte length, what a SEEKTABLE would be built from (code 6 when frameCap is too small)
+ *   elemhip_flac_reset   a new programme: nothing open, frame number 0
+ *   elemhip_flac_encode  pure host arithmetic, no handle: planar int32 codes of one stream -> its frames, the scalar twin of the
+ *                        kernels (whole frames; with `flush` the remainder as a short frame). Code 103 when `capacity` is too small,
+ *                        6 for a code outside the sample size or a frame number above 2^31 - 1.
+ * A stream needs "fLaC" and a STREAMINFO block in front (elementary_amd/flac.py writes them); its MD5 is left zero — "not computed":
+ * the unencoded samples never reach the host. */
+typedef struct elemhip_flac_spec { uint32_t bits /* 16, 24; 0: option "flac_bits" */, channels_per_stream, dither /*0 none, 1 TPDF*/, seed;
+                                   uint64_t drop, take; /* 0, UINT64_MAX: every delivered frame */ } elemhip_flac_spec;
+typedef struct elemhip_flac_info { uint32_t flac_frame, bits, channels_per_stream, streams, sample_rate, flushed; uint64_t frames; } elemhip_flac_info;
+typedef struct elemhip_flac_stream_info { uint64_t frames, total_samples; uint32_t min_frame_bytes, max_frame_bytes; } elemhip_flac_stream_info;
+int elemhip_process_blocks_flac(elemhip_t*, const void* const* inStreams, size_t nInStreams, const elemhip_pcm_in_spec* inSpec,
+                                void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams, const elemhip_flac_spec*,
+                                size_t numFrames, int64_t sampleTime, elemhip_pcm_channel_stats* stats);
+size_t elemhip_flac_bound(size_t frames, uint32_t channelsPerStream, uint32_t bits);
+int elemhip_flac_flush(elemhip_t*, void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams);
+int elemhip_flac_read(elemhip_t*, elemhip_flac_info* info, elemhip_flac_stream_info* perStream, size_t capacity, uint32_t* frameBytes, size_t frameCap);
+int elemhip_flac_reset(elemhip_t*);
+int elemhip_flac_encode(const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t flacFrame, uint32_t bits, uint32_t sampleRate,
+                        uint32_t firstFrameNumber, int flush, uint8_t* out, size_t capacity, size_t* bytesOut, uint32_t* frameBytes, size_t frameCap,
+                        size_t* framesOut);
+
 /* bool addSharedResource(name, unique_ptr<SharedResource>)       Runtime.h:83,461-465 (insert-only) */
 int    elemhip_add_shared_resource(elemhip_t*, const char* name, const float* const* channels, size_t nCh, size_t nSamples);
 /* void pruneSharedResources()                                    Runtime.h:89,467-471 */

@@ -161,6 +161,32 @@ public:
         return elemhip_limiter_read(h, info, maxReduction, limitedFrames, capacity);
     }
     int limiterReset() { return elemhip_limiter_reset(h); }
+    // EXTENSION: the block loop delivered as FLAC frames encoded on the GPU (elemhip_process_blocks_flac; setOption("flac_frame" /
+    // "flac_bits")): inputs as processBlocksPcmIo takes them, per output stream a buffer of at least flacBound(frames delivered,
+    // channels_per_stream, bits) bytes; bytesOut[s] = the bytes of the FLAC frames the call completed. flacFlush closes the programme
+    // with the open remainder as a short frame, flacReset starts a new one.
+    int processBlocksFlac(const void* const* inStreams, size_t nInStreams, elemhip_pcm_in_spec const& inSpec, void* const* outStreams,
+                          const size_t* capacities, size_t* bytesOut, size_t nOutStreams, elemhip_flac_spec const& spec, size_t numFrames,
+                          elemhip_pcm_channel_stats* stats = nullptr, void* userData = nullptr) {
+        const int64_t t = userData ? *static_cast<int64_t*>(userData) : implicitTime;
+        const int rc = elemhip_process_blocks_flac(h, inStreams, nInStreams, &inSpec, outStreams, capacities, bytesOut, nOutStreams, &spec, numFrames, t, stats);
+        if (!userData) implicitTime += (int64_t)numFrames;
+        return rc;
+    }
+    int flacFlush(void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams) {
+        return elemhip_flac_flush(h, outStreams, capacities, bytesOut, nOutStreams);
+    }
+    int flacRead(elemhip_flac_info* info, elemhip_flac_stream_info* perStream, size_t capacity, uint32_t* frameBytes = nullptr, size_t frameCap = 0) {
+        return elemhip_flac_read(h, info, perStream, capacity, frameBytes, frameCap);
+    }
+    int flacReset() { return elemhip_flac_reset(h); }
+    static size_t flacBound(size_t frames, uint32_t channelsPerStream, uint32_t bits) { return elemhip_flac_bound(frames, channelsPerStream, bits); }
+    static int flacEncode(const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t flacFrame, uint32_t bits, uint32_t sampleRate,
+                          uint32_t firstFrameNumber, bool flush, uint8_t* out, size_t capacity, size_t* bytesOut, uint32_t* frameBytes = nullptr,
+                          size_t frameCap = 0, size_t* framesOut = nullptr) {
+        return elemhip_flac_encode(planar, channels, frames, flacFrame, bits, sampleRate, firstFrameNumber, flush ? 1 : 0, out, capacity, bytesOut, frameBytes,
+                                   frameCap, framesOut);
+    }
     static int loudnessGate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
         return elemhip_loudness_gate(meanSquares, channels, subBlocks, weights, out);
     }
