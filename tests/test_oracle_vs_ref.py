@@ -13,6 +13,7 @@ import pytest
 
 import oracle
 from cases import NODE_CASES, REF_ONLY, node_case_resources, sampleseq_scenario
+from edge_cases import EDGE_REF_ONLY, NODE_EDGE_CASES, clock_starts, edge_inputs, edge_resources, edge_roots
 from elementary_amd import graphs
 from helpers import render_one, render_pair
 
@@ -91,7 +92,23 @@ def _events(make):
     return log
 
 
-SCENARIOS = ["node/" + n for n in sorted(set(NODE_CASES) - REF_ONLY)] + ["c1", "c2x64", "c4x6", "gc", "sampleseq32", "sampleseq512", "events"]
+def _edge(make, name, block=512, blocks=6):
+    """One engine over an edge-corpus case (tests/edge_cases.py): 6 blocks of 512 at 44.1 kHz from sample_time 0 — clock_far_out
+    from each of its start times, one after the other. Returns [starts * blocks, roots, block]."""
+    outs = []
+    for start in (clock_starts(block) if name == "clock_far_out" else [0]):
+        rt = make(44100.0, block)
+        for rname, data in edge_resources().items():
+            assert rt.add_shared_resource(rname, data)
+        roots = edge_roots(name, block)
+        assert rt.render(*roots)["result"] == 0
+        outs += [rt.process(edge_inputs(k, block), len(roots), block, sample_time=start + k * block) for k in range(blocks)]
+    return np.stack(outs)
+
+
+EDGE_SCENARIOS = ["edge/" + n for n in sorted(set(NODE_EDGE_CASES) - EDGE_REF_ONLY)]
+SCENARIOS = (["node/" + n for n in sorted(set(NODE_CASES) - REF_ONLY)] + ["c1", "c2x64", "c4x6", "gc", "sampleseq32", "sampleseq512", "events"]
+             + EDGE_SCENARIOS)
 
 
 def run_scenario(key, *makes):
@@ -105,6 +122,9 @@ def run_scenario(key, *makes):
         return _render(makes, lambda: graphs.c2_graph(64), sample_rate=graphs.C2_SAMPLE_RATE, blocks=60)
     if key == "c4x6":
         return _render(makes, lambda: [graphs.c4_instance(k) for k in range(6)], sample_rate=graphs.C4_SAMPLE_RATE, blocks=60)
+    if key.startswith("edge/"):
+        res = [_edge(mk, key[5:]) for mk in makes]
+        return res[0] if len(res) == 1 else tuple(res)
     one = {"gc": _gc, "sampleseq32": sampleseq_scenario, "sampleseq512": lambda mk: sampleseq_scenario(mk, block=512),
            "events": _events}[key]
     res = [one(mk) for mk in makes]
@@ -116,7 +136,10 @@ def against_reference(key):
     otherwise against the recorded digest of the reference's result."""
     if oracle.have_ref():
         got, want = run_scenario(key, port, ref)
-        if isinstance(got, np.ndarray):
+        if isinstance(got, np.ndarray) and key.startswith("edge/"):      # NaN != NaN: compare the bits, NaN payloads included
+            assert got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32)), \
+                f"{key}: {int((got.view(np.uint32) != want.view(np.uint32)).sum())} samples differ in their bits"
+        elif isinstance(got, np.ndarray):
             assert np.array_equal(got, want), f"{key}: max abs diff {np.abs(got - want).max():.3e}"
         else:
             assert got == want, key
@@ -130,6 +153,15 @@ def against_reference(key):
 @pytest.mark.parametrize("name", sorted(set(NODE_CASES) - REF_ONLY))
 def test_node_case_bit_exact(name):
     against_reference("node/" + name)
+
+
+@pytest.mark.parametrize("name", sorted(set(NODE_EDGE_CASES) - EDGE_REF_ONLY))
+def test_edge_case_bit_exact(name):
+    """The restatement is the GPU suite's checker wherever oracle/_ref is missing: pinned on the edge corpus too, NaN payloads
+    included (clamps, domain edges, non-finite samples through every recurrence, the clock beyond 2^32)."""
+    got = against_reference("edge/" + name)
+    if name in ("math_domain", "nan_ordering", "nonfinite_into_state"):
+        assert np.isnan(got).any() and np.isinf(got).any()
 
 
 def test_c1_and_c2_bit_exact():

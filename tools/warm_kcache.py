@@ -48,6 +48,10 @@ def main():
         from test_gpu_fuzz import random_graph
         for name in sorted(NODE_CASES):
             jobs.append((name, 44100.0, 512, NODE_CASES[name][0](), node_case_resources(), None))
+        import edge_cases                                 # tests/test_gpu_edges.py, the specialised path: 64 frames at 48 kHz
+        for name in sorted(edge_cases.NODE_EDGE_CASES):
+            roots = edge_cases.edge_roots(name, 64, edge_cases.settle_blocks(48000.0, 64))
+            jobs.append((f"edge_{name}", 48000.0, 64, roots, edge_cases.edge_resources(), None))
         for seed in range(0, 48, 3):
             n_out = min(3, 1 + seed % 5)
             jobs.append((f"fuzz{seed}", 48000.0, 512, random_graph(seed, n_nodes=24 + 22 * (seed % 4), n_roots=1 + seed % 5)[:n_out], None, None))
