@@ -248,6 +248,33 @@ int elemhip_flac_encode(const int32_t* const* planar, uint32_t channels, size_t 
     return elemhip::kOk;
 }
 
+int elemhip_flac_index(const uint8_t* data, size_t bytes, uint32_t channels, uint32_t bits, uint32_t blockSize, uint64_t* frameOffsets,
+                       uint64_t* frameFirstSamples, size_t capacity, size_t* entries) {
+    if (!entries || (bytes && !data) || (capacity && (!frameOffsets || !frameFirstSamples))) return elemhip::kInvalidInstructionFormat;
+    const uint32_t r = flac_decode::index_host(data, bytes, channels, bits, blockSize, frameOffsets, frameFirstSamples, capacity, entries);
+    return r == flac_decode::OK ? elemhip::kOk : elemhip::kFlacInput;
+}
+
+int elemhip_flac_decode(const elemhip_flac_in* in, size_t count, int32_t* const* planar, size_t* badFrame, uint32_t* reason) {
+    namespace fd = flac_decode;
+    static_assert(sizeof(elemhip_flac_in) == sizeof(Engine::FlacIn), "same layout");
+    if (reason) *reason = fd::OK;
+    if (!in || !in->frame_offsets || !in->frame_first_samples || (in->bytes && !in->data) || (count && !planar)) return elemhip::kInvalidInstructionFormat;
+    if (!fd::bits_ok(in->bits) || in->channels == 0u || in->channels > fd::kMaxChannels) return elemhip::kInvalidInstructionFormat;
+    for (uint32_t c = 0; c < in->channels && count; ++c) if (!planar[c]) return elemhip::kInvalidInstructionFormat;
+    for (uint64_t j = 0; j < in->frames; ++j)
+        if (in->frame_offsets[j + 1] < in->frame_offsets[j] || in->frame_offsets[j + 1] > in->bytes || in->frame_first_samples[j + 1] <= in->frame_first_samples[j])
+            return elemhip::kInvalidInstructionFormat;
+    const uint32_t r = fd::decode_host(in->data, in->frame_offsets, in->frame_first_samples, (size_t)in->frames, in->channels, in->bits, in->position, count,
+                                       planar, badFrame);
+    if (reason) *reason = r;
+    return r == fd::OK ? elemhip::kOk : elemhip::kFlacInput;
+}
+
+int elemhip_flac_in_error(elemhip_t* h, uint32_t* stream, uint64_t* frame, uint32_t* reason) {
+    return h ? h->engine.flacInError(stream, frame, reason) : elemhip::kInvalidInstructionFormat;
+}
+
 int elemhip_loudness_gate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
     if (!out || (channels && subBlocks && !meanSquares)) return elemhip::kInvalidInstructionFormat;
     const loudness::Gated g = loudness::gate(meanSquares, channels, subBlocks, weights);

@@ -24,6 +24,7 @@ const char* describe(int c) {
         case kTooManyChannels: return "Too many host channels";
         case kUnsupportedGraph: return "Graph uses a construct the HIP engine does not support";
         case kJsonParseError: return "Failed to parse json string";
+        case kFlacInput: return "A FLAC input frame does not decode";
         default: return "Return code not recognized";
     }
 }
@@ -193,6 +194,7 @@ Engine::~Engine() {
     inputResampleFree();
     limiterFree();
     flacFree();
+    flacInFree();
     if (ioStream) (void)hipStreamDestroy(ioStream);
     if (relayStream) { (void)hipStreamSynchronize(relayStream); (void)hipStreamDestroy(relayStream); }
     if (evRelay) (void)hipEventDestroy(evRelay);

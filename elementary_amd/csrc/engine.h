@@ -29,6 +29,7 @@
 #include "loudness.h"
 #include "resample.h"
 #include "limiter.h"
+#include "flac_decode.h"
 
 namespace elemhip {
 
@@ -37,9 +38,12 @@ enum ReturnCode : int {
     kOk = 0, kUnknownNodeType = 1, kNodeNotFound = 2, kNodeAlreadyExists = 3, kNodeTypeAlreadyExists = 4,
     kInvalidPropertyType = 5, kInvalidPropertyValue = 6, kInvariantViolation = 7, kInvalidInstructionFormat = 8,
     kHipError = 100, kNoDevice = 101, kBlockTooLarge = 102, kTooManyChannels = 103, kUnsupportedGraph = 104,
-    kJsonParseError = 105,
+    kJsonParseError = 105, kFlacInput = 106,
 };
 const char* describe(int code);
+using FlacInFrame = flac_decode::FrameRec;
+using FlacInStream = flac_decode::StreamRec;
+using FlacInError = flac_decode::ErrorRec;
 
 // Host call-out node types (Runtime::registerNodeType, runtime/elem/Runtime.h:105-106; GraphNode.h:19-96): a node whose
 // process() runs on the CPU between two launch levels. OP_HOST never reaches a kernel, so it is not a device opcode.
@@ -233,6 +237,13 @@ public:
     struct PcmSource { uint32_t format, channelsPerStream; const void* const* streams; size_t nStreams; };
     int processBlocksPcmIo(const PcmSource& src, void* const* outStreams, size_t nOutStreams, const PcmSpec* outSpec, float* const* planar,
                            size_t nPlanar, size_t numFrames, int64_t sampleTime, PcmChannelStats* stats);
+    // The FLAC form of a PcmSource (format flac_decode::kFormat = 4): streams[s] points at a FlacIn — the stream's frames, the table
+    // flac_decode::index_host makes of them, and `position`, the stream sample at the call's first input frame. Decoded on the GPU
+    // into the packed input half (flac_decode.hip); where the block-by-block path renders, decode_host decodes on the host.
+    // A frame that does not decode ends the call with kFlacInput; flacInError names it.
+    struct FlacIn { const uint8_t* data; uint64_t bytes; const uint64_t* frameOffsets; const uint64_t* frameFirstSamples; uint64_t frames;
+                    uint32_t channels, bits; uint64_t totalSamples, position; };
+    int flacInError(uint32_t* stream, uint64_t* frame, uint32_t* reason);
     // Option "loudness_meter" (loudness.h): every launch set of processBlocksHost / processBlocksPcm / processBlocksPcmIo is metered
     // where its output lies in HBM (loudness.hip), float or PCM delivery alike; where those calls render host block by host block the
     // header's scalar loop meters the floats on the host. process() and the device-resident processBlocks() are NOT metered. The
@@ -528,6 +539,31 @@ private:
     int flacResetLocked();
     void flacFree();
     int flacDeliver(FlacJob& job, int half);            // the table is in the pinned half: payload -> the caller's buffers
+    // FLAC input (flac_decode.h, engine_flac_in.cpp): per launch set the FLAC frames that cover the set's input frames go through
+    // staging halves of their own (two record tables in front of the bytes), are decoded into the packed input half (flac_decode.hip)
+    // and leave an error record that comes back with the set. The scratch and the descriptors are touched by the render stream's
+    // kernels only, in order: one copy serves both halves.
+    struct FlacInSet {
+        std::vector<FlacInFrame> frames; std::vector<FlacInStream> streams;
+        std::vector<uint64_t> from, len;        // per stream: its covering bytes in the caller's buffer
+        size_t stagedBytes = 0, scratchInts = 0;
+    };
+    FlacInSet flacInSets[2];
+    unsigned char* hFlacIn[2] = {nullptr, nullptr}; unsigned char* dFlacIn[2] = {nullptr, nullptr};
+    size_t flacInBytes = 0;
+    FlacInError* hFlacInErr = nullptr; FlacInError* dFlacInErr = nullptr;      // one per half
+    void* dFlacInSubs = nullptr; uint32_t* dFlacInState = nullptr; int32_t* dFlacInScratch = nullptr;
+    size_t flacInFrameCap = 0, flacInScratchCap = 0;
+    bool flacInErrSet = false; uint32_t flacInErrStream = 0, flacInErrReason = 0; uint64_t flacInErrFrame = 0;
+    int flacInCheck(const PcmSource& src) const;
+    uint32_t flacInBits(const PcmSource& src) const;
+    void flacInPlan(const PcmSource& src, uint64_t from, size_t valid, FlacInSet& set) const;
+    int ensureFlacIn(size_t stagedBytes, size_t frames, size_t scratchInts, uint32_t G);      // (`mu` held)
+    void flacInStage(const PcmSource& src, const FlacInSet& set, int half);
+    int flacInLaunch(const FlacInSet& set, int half, uint32_t G, uint32_t bits, size_t valid, size_t streamStride);      // (`mu` held)
+    bool flacInFailed(int half);                // the set's error record has arrived: anything in it -> the last error
+    int flacInHostImage(const PcmSource& src, uint64_t from, size_t n, std::vector<std::vector<unsigned char>>& images);
+    void flacInFree();
     // the set loop of processBlocksHost / processBlocksPcm (`pcm` null: planar floats only)
     int renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
                        const PcmSource* src = nullptr, FlacJob* flac = nullptr);      // `src`: the inputs as PCM streams (`in` is null then)

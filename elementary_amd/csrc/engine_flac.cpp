@@ -112,7 +112,9 @@ int Engine::flacDeliver(FlacJob& job, int half) {
 
 int Engine::processBlocksFlac(const PcmSource& src, void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams,
                               const FlacSpec& specIn, size_t numFrames, int64_t sampleTime, PcmChannelStats* stats) {
-    if (src.nStreams && (!pcm_pack::format_ok(src.format) || src.channelsPerStream == 0u || !src.streams)) return kInvalidInstructionFormat;
+    const bool flacSrc = src.nStreams && src.format == flac_decode::kFormat;
+    if (src.nStreams && ((!flacSrc && !pcm_pack::format_ok(src.format)) || src.channelsPerStream == 0u || !src.streams)) return kInvalidInstructionFormat;
+    if (flacSrc) { const int rc = flacInCheck(src); if (rc != kOk) return rc; }
     for (size_t s = 0; s < src.nStreams; ++s) if (!src.streams[s] && numFrames) return kInvalidInstructionFormat;
     FlacSpec spec = specIn;
     if (spec.bits == 0u) { std::lock_guard<std::mutex> lock(mu); spec.bits = flacBitsOpt; }

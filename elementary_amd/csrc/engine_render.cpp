@@ -1230,7 +1230,9 @@ int Engine::processBlocksPcm(const float* const* in, size_t nIn, void* const* st
 
 int Engine::processBlocksPcmIo(const PcmSource& src, void* const* outStreams, size_t nOutStreams, const PcmSpec* outSpec, float* const* planar,
                                size_t nPlanar, size_t numFrames, int64_t sampleTime, PcmChannelStats* stats) {
-    if (src.nStreams && (!pcm_pack::format_ok(src.format) || src.channelsPerStream == 0u || !src.streams)) return kInvalidInstructionFormat;
+    const bool flacSrc = src.nStreams && src.format == flac_decode::kFormat;
+    if (src.nStreams && ((!flacSrc && !pcm_pack::format_ok(src.format)) || src.channelsPerStream == 0u || !src.streams)) return kInvalidInstructionFormat;
+    if (flacSrc) { const int rc = flacInCheck(src); if (rc != kOk) return rc; }
     if (outSpec ? (!pcm_pack::format_ok(outSpec->format) || outSpec->channelsPerStream == 0u || (nOutStreams && !outStreams)) : (nPlanar && !planar))
         return kInvalidInstructionFormat;
     for (size_t s = 0; s < src.nStreams; ++s) if (!src.streams[s] && numFrames) return kInvalidInstructionFormat;
@@ -1257,7 +1259,11 @@ int Engine::processBlocksPcmIo(const PcmSource& src, void* const* outStreams, si
 int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
                            const PcmSource* src, FlacJob* flac) {
     const size_t bs = (size_t)blockSize;
-    const uint32_t srcG = src ? src->channelsPerStream : 1u, srcFmt = src ? src->format : 0u;
+    // a FLAC source (engine_flac_in.cpp) is decoded into the packed input half as the s16 / s24 stream of the same samples: from there
+    // on it IS that PCM source
+    const bool flacSrc = src && src->format == flac_decode::kFormat;
+    const uint32_t flacInB = flacSrc ? flacInBits(*src) : 0u;
+    const uint32_t srcG = src ? src->channelsPerStream : 1u, srcFmt = flacSrc ? flac_decode::image_format(flacInB) : src ? src->format : 0u;
     const size_t srcB = src ? pcm_pack::sample_bytes(srcFmt) : 0;
     const bool wantFloat = nOut > 0 && out != nullptr;
     const uint32_t pcmG = pcm ? pcm->spec.channelsPerStream : 1u, pcmFmt = pcm ? pcm->spec.format : 0u;
@@ -1292,6 +1298,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         std::vector<float> tailIn, tailOut;
         std::vector<uint8_t*> sp(pcm ? pcm->nStreams : 0);
         std::vector<const unsigned char*> srcAt(src ? src->nStreams : 0);
+        std::vector<std::vector<unsigned char>> flacImg;
         // the meter's carried state comes to the host for the call: the floats are here, the header's scalar loop meters them
         std::vector<loudness::ChannelState> meterState(meter ? nOut : 0);
         auto meterSync = [&](bool toHost) -> int {
@@ -1417,18 +1424,20 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 tailOut.assign(nOut * hb, 0.0f);
                 for (size_t c = 0; c < nOut; ++c) op[c] = tailOut.data() + c * hb;
             }
+            int flacInRc = kOk;       // a FLAC source is decoded on the host in front of unpack_host (decode_host): the kernels' bits
             if (inres) {
                 // the stretch this host block's nf engine frames pull, from the input cursor on: decoded where it is PCM, then converted
                 // into the block's rows (zeros behind nf)
                 std::lock_guard<std::mutex> lock(mu);
                 const size_t ni = (size_t)(resample::inputs_before(inp, inFramesOut + nf) - inFramesIn), stride = std::max<size_t>(ni, 1);
                 tailIn.assign(nIn * hb, 0.0f);
-                if (src) {
+                if (flacSrc) flacInRc = flacInHostImage(*src, inOff, ni, flacImg);
+                if (src && flacInRc == kOk) {
                     inX.resize(nIn * stride);
-                    for (size_t s = 0; s < src->nStreams; ++s) srcAt[s] = inStream(s) + inOff * srcG * srcB;
+                    for (size_t s = 0; s < src->nStreams; ++s) srcAt[s] = flacSrc ? flacImg[s].data() : inStream(s) + inOff * srcG * srcB;
                     pcm_unpack::unpack_host(srcFmt, srcG, (uint32_t)src->nStreams, srcAt.data(), ni, inX.data(), stride, ni);
                 }
-                for (size_t c = 0; c < nIn; ++c) {
+                for (size_t c = 0; c < nIn && flacInRc == kOk; ++c) {
                     (void)resample::resample_in_host(inp, inTable.data(), inRowBase.data(), inHist.data() + c * inp.H, src ? inX.data() + c * stride : in[c] + inOff,
                                                      inFramesOut, nf, tailIn.data() + c * hb);
                     ip[c] = tailIn.data() + c * hb;
@@ -1437,14 +1446,16 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             } else if (src) {
                 // the inputs are needed on the host: the header's scalar loop unpacks them — the kernel's functions, the kernel's floats
                 tailIn.resize(nIn * hb);
-                for (size_t s = 0; s < src->nStreams; ++s) srcAt[s] = static_cast<const unsigned char*>(src->streams[s]) + f0 * srcG * srcB;
-                pcm_unpack::unpack_host(srcFmt, srcG, (uint32_t)src->nStreams, srcAt.data(), nf, tailIn.data(), hb, hb);
+                if (flacSrc) { std::lock_guard<std::mutex> lock(mu); flacInRc = flacInHostImage(*src, f0, nf, flacImg); }
+                for (size_t s = 0; s < src->nStreams && flacInRc == kOk; ++s)
+                    srcAt[s] = flacSrc ? flacImg[s].data() : static_cast<const unsigned char*>(src->streams[s]) + f0 * srcG * srcB;
+                if (flacInRc == kOk) pcm_unpack::unpack_host(srcFmt, srcG, (uint32_t)src->nStreams, srcAt.data(), nf, tailIn.data(), hb, hb);
                 for (size_t c = 0; c < nIn; ++c) ip[c] = tailIn.data() + c * hb;
             } else if (nf < hb) {
                 tailIn.assign(nIn * hb, 0.0f);
                 for (size_t c = 0; c < nIn; ++c) { std::memcpy(tailIn.data() + c * hb, in[c] + f0, nf * sizeof(float)); ip[c] = tailIn.data() + c * hb; }
             }
-            const int rc = process(ip.data(), nIn, op.data(), nOut, hb, sampleTime + (int64_t)f0);
+            const int rc = flacInRc != kOk ? flacInRc : process(ip.data(), nIn, op.data(), nOut, hb, sampleTime + (int64_t)f0);
             if (rc != kOk) { if (meter) (void)meterSync(false); resFail(); limFail(); inFail(); return rc; }
             // what is delivered of this host block: its nf frames, or their conversion
             const float* got = tailOut.data();
@@ -1531,6 +1542,21 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             inN = inFramesOut;
         } else if (src) {
             rc = ensurePcmInStaging(src->nStreams * (size_t)pcm_pack::stream_stride(setBlocks * bs, srcG, srcFmt), srcG);
+            if (rc != kOk) return rc;
+        }
+        if (flacSrc) {
+            // the FLAC halves, the descriptors and the scratch hold the largest covering range of any set of this call: sized from the table
+            size_t staged = 0, frames = 0, scratch = 0;
+            FlacInSet probe;
+            const size_t sets = (numBlocks + setBlocks - 1) / setBlocks;
+            for (size_t k = 0; k < sets; ++k) {
+                const uint64_t e0 = std::min<uint64_t>(k * setBlocks * bs, numFrames), e1 = std::min<uint64_t>((k + 1) * setBlocks * bs, numFrames);
+                const uint64_t base = inres ? resample::inputs_before(inp, inN) : 0;
+                const uint64_t i0 = inres ? resample::inputs_before(inp, inN + e0) - base : e0, i1 = inres ? resample::inputs_before(inp, inN + e1) - base : e1;
+                flacInPlan(*src, i0, (size_t)(i1 - i0), probe);
+                staged = std::max(staged, probe.stagedBytes); frames = std::max(frames, probe.frames.size()); scratch = std::max(scratch, probe.scratchInts);
+            }
+            rc = ensureFlacIn(staged, std::max<size_t>(frames, 1), std::max<size_t>(scratch, 1), srcG);
             if (rc != kOk) return rc;
         }
         if (pcm) {
@@ -1622,7 +1648,13 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         const size_t inStride = inres ? (size_t)pcm_pack::stream_stride(inValid, inG, inFmt) : 0;
         if (nIn) {
             if (k >= 2) HOST_TRY(hipEventSynchronize(evIn[half]));     // the H2D of set k - 2 has left this pinned half
-            if (inres) {
+            if (flacSrc) {
+                // the FLAC frames that cover the set's input frames, found by binary search in the streams' tables, as they lie in the
+                // caller's buffers: the compressed bytes and nothing more
+                flacInPlan(*src, inres ? inOff : b0 * bs, inres ? inValid : srcValid, flacInSets[half]);
+                if (flacInSets[half].stagedBytes > flacInBytes) { result = kInvariantViolation; break; }      // (sized above from the same table)
+                flacInStage(*src, flacInSets[half], half);
+            } else if (inres) {
                 // one contiguous stretch per stream (per planar array): the input-rate bytes and nothing more
                 const size_t len = inValid * inG * inB;
                 unsigned char* dst = hPcmIn[half];
@@ -1657,11 +1689,19 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             if (nIn) {
                 // (the copy stream is in order: this H2D runs behind the D2H of set k - 2, which waited for that set's render,
                 //  the last reader of this device half)
-                if (inres) { if (inStreams * inStride) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], inStreams * inStride, hipMemcpyHostToDevice, ioStream)); }
+                if (flacSrc) { if (flacInSets[half].stagedBytes) HOST_TRY(hipMemcpyAsync(dFlacIn[half], hFlacIn[half], flacInSets[half].stagedBytes, hipMemcpyHostToDevice, ioStream)); }
+                else if (inres) { if (inStreams * inStride) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], inStreams * inStride, hipMemcpyHostToDevice, ioStream)); }
                 else if (src) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], src->nStreams * srcStride, hipMemcpyHostToDevice, ioStream))
                 else HOST_TRY(hipMemcpyAsync(dStageIn[half], hStageIn[half], nb * nIn * bs * sizeof(float), hipMemcpyHostToDevice, ioStream));
                 HOST_TRY(hipEventRecord(evIn[half], ioStream));
                 HOST_TRY(hipStreamWaitEvent(stream, evIn[half], 0));
+                if (flacSrc) {
+                    // the decode kernels write the packed input half the H2D of a PCM stream would have filled. The half was last read by
+                    // the unpack (or the converter) of set k - 2, earlier on this stream; the FLAC half by that set's decode, and its H2D
+                    // ran behind the D2H of set k - 2 like every other; the scratch is touched by this stream's kernels only.
+                    const int rf = flacInLaunch(flacInSets[half], half, srcG, flacInB, inres ? inValid : srcValid, inres ? inStride : srcStride);
+                    if (rf != kOk) { result = rf; break; }
+                }
                 if (inres) {
                     // the input converter in the unpack kernel's place, and the argument below holds for it word for word: dStageIn[half]
                     // and dPcmIn[half] are free for the same reasons, and it too writes every row of all nb blocks, zeros behind inOut.
@@ -1790,6 +1830,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             }
             HOST_TRY(hipEventRecord(evRendered[half], stream));
             HOST_TRY(hipStreamWaitEvent(ioStream, evRendered[half], 0));
+            if (flacSrc) HOST_TRY(hipMemcpyAsync(hFlacInErr + half, dFlacInErr + half, sizeof(FlacInError), hipMemcpyDeviceToHost, ioStream));   // the decode's error record
             if (wantFloat || !packed) { if (nOut && gotBlocks) HOST_TRY(hipMemcpyAsync(hStageOut[half], got, gotBlocks * nOut * bs * sizeof(float), hipMemcpyDeviceToHost, ioStream)); }
             if (pcm) HOST_TRY(hipMemcpyAsync(hPcm[half], dPcm[half], pcmCopy, hipMemcpyDeviceToHost, ioStream));
             if (flac) {     // the length table and the statistics; the frames follow once the table says how many bytes they are (flacDeliver)
@@ -1803,6 +1844,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         }
         if (k >= 1) {   // set k - 1 arrives while set k renders
             HOST_TRY(hipEventSynchronize(evOut[(k - 1) & 1]));
+            if (flacSrc && flacInFailed((int)((k - 1) & 1))) { result = kFlacInput; break; }      // a frame of set k - 1 did not decode: nothing further
             if (nOut) deliver(k - 1);
             scattered = k;
             if (flacRc != kOk) { result = flacRc; break; }
@@ -1812,6 +1854,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
     if (issued > scattered && result == kOk) {       // the last set (every earlier one was scattered while its successor rendered)
         const size_t last = issued - 1;
         if (hipEventSynchronize(evOut[last & 1]) != hipSuccess) result = kHipError;
+        else if (flacSrc && flacInFailed((int)(last & 1))) result = kFlacInput;
         else if (nOut) deliver(last);
         if (flacRc != kOk) result = flacRc;
     }

@@ -6,6 +6,7 @@
 #include "loudness.h"
 #include "resample.h"
 #include "limiter.h"
+#include "flac_decode.h"
 
 namespace elemhip {
 
@@ -171,6 +172,25 @@ struct FlacEncodeArgs {
     uint32_t        cap, G, numStreams, bits, flacFrame, n /* samples of every frame: flacFrame, or the flushed remainder */, numFrames, slotWords, rate, firstNumber;
 };
 hipError_t launch_flac_encode(hipStream_t s, const FlacEncodeArgs& a);      // the encode kernel, then the assemble kernel
+// ---- FLAC input (flac_decode.hip): in front of the unpack kernel or the input-rate converter, flac_decode.h ----
+using FlacInFrame = flac_decode::FrameRec;
+using FlacInStream = flac_decode::StreamRec;
+using FlacInError = flac_decode::ErrorRec;
+struct FlacDecodeArgs {
+    const unsigned char* staged;    // the covering frames' bytes
+    const FlacInFrame*  frames;
+    const FlacInStream* streams;
+    void*           subs;           // [numFrames][G] flac_decode::Sub
+    uint32_t*       state;          // [numFrames]: reason | channel assignment << 8
+    int32_t*        scratch;
+    FlacInError*    error;          // zeroed in front of the launch
+    unsigned char*  dst;            // [stream] at `streamStride` bytes (a multiple of 16; the base 16-byte aligned): valid * G samples each
+    uint64_t        streamStride;
+    uint32_t        numFrames, numStreams, G, bits, valid, pad;
+};
+// (the host's copies of the two tables are checked against the buffers' sizes before anything is launched)
+hipError_t launch_flac_decode(hipStream_t s, const FlacDecodeArgs& a, const FlacInFrame* hostFrames, const FlacInStream* hostStreams,
+                              size_t stagedBytes, size_t scratchInts);
 hipError_t launch_bus_sum(hipStream_t s, float* dst, const float* const* partials, uint32_t count, size_t n);   // dst = ((p0 + p1) + p2) + ... (rank order)
 
 } // namespace elemhip

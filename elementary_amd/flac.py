@@ -3,7 +3,9 @@ host twin ``runtime.flac_encode``): the ``fLaC`` marker and a STREAMINFO block i
 ``close`` the smallest / largest frame size and the total sample count patched into STREAMINFO.
 
 The STREAMINFO MD5 stays all zero — "not computed" in RFC 9639's words: the unencoded samples never reach the host, and that is the
-point of encoding on the GPU. Decoders accept it and skip their check."""
+point of encoding on the GPU. Decoders accept it and skip their check.
+
+``FlacReader`` — the other direction: a FLAC file as an input of the offline render, indexed on the host and decoded on the GPU."""
 from __future__ import annotations
 
 import struct
@@ -17,6 +19,77 @@ def streaminfo(flac_frame: int, bits: int, channels: int, sample_rate: int, tota
     v = (int(sample_rate) << 44) | ((int(channels) - 1) << 41) | ((int(bits) - 1) << 36) | int(total_samples)
     return (struct.pack(">HH", int(flac_frame), int(flac_frame)) + int(min_frame).to_bytes(3, "big") + int(max_frame).to_bytes(3, "big")
             + v.to_bytes(8, "big") + bytes(16))
+
+
+class FlacReader:
+    """One FLAC file as an input of the offline render (``in_fmt='flac'``): the metadata blocks are walked — STREAMINFO parsed, every
+    other block skipped — and the frames behind them indexed (``elemhip_flac_index``: header CRC-8, consecutive frame numbers, fixed
+    fields; the frames' CRC-16 is checked on the GPU). ``read(n)`` returns a ``FlacChunk``: a view of the frames that cover the next
+    ``n`` samples, their slice of the table and the position — the compressed bytes are what crosses the host link, the samples are
+    decoded on the GPU (``flac_decode.hip``). Fixed-block-size streams of 8 / 12 / 16 / 20 / 24 bits with blocks of up to 16384 samples.
+
+    The STREAMINFO MD5 is NOT verified: the decoded samples never reach the host. Every frame's CRC-16 is. Unlike ``WavReader``,
+    which streams, the whole (compressed) file is read into memory at construction: the index needs every frame header."""
+
+    def __init__(self, path):
+        import numpy as np
+        from .runtime import flac_index
+        with open(path, "rb") as f:
+            raw = f.read()
+        if raw[:4] != b"fLaC":
+            raise ValueError("no fLaC marker")
+        pos, last, info = 4, False, None
+        while not last:
+            if pos + 4 > len(raw):
+                raise ValueError("the metadata blocks run past the file's end")
+            last, kind = bool(raw[pos] & 0x80), raw[pos] & 0x7F
+            size = int.from_bytes(raw[pos + 1:pos + 4], "big")
+            if pos == 4:
+                if kind != 0 or size != 34 or pos + 4 + size > len(raw):
+                    raise ValueError("the first metadata block is not STREAMINFO")
+                body = raw[pos + 4:pos + 4 + size]
+                v = int.from_bytes(body[10:18], "big")
+                info = {"min_block": struct.unpack(">H", body[0:2])[0], "max_block": struct.unpack(">H", body[2:4])[0],
+                        "rate": v >> 44, "channels": ((v >> 41) & 7) + 1, "bits": ((v >> 36) & 31) + 1, "total": v & ((1 << 36) - 1)}
+            pos += 4 + size
+        if info["min_block"] != info["max_block"]:
+            raise ValueError("variable block size streams are not read")
+        self.sample_rate, self.channels, self.bits, self.flac_frame = info["rate"], info["channels"], info["bits"], info["max_block"]
+        self.fmt = "flac"
+        self._data = np.frombuffer(raw, dtype=np.uint8)[pos:]
+        self._off, self._first = flac_index(self._data, self.channels, self.bits, self.flac_frame)
+        self.frames = int(self._first[-1])                  # samples per channel ("frames" as WavReader counts them)
+        if info["total"] and info["total"] != self.frames:
+            raise ValueError(f"STREAMINFO announces {info['total']} samples, the frames hold {self.frames}")
+        self.flac_frames = len(self._off) - 1
+        self._pos = 0
+
+    def seek(self, position: int) -> None:
+        self._pos = int(position)
+
+    def read(self, n: int):
+        """The next ``n`` samples as a ``FlacChunk`` (the part past the stream's end is silence); the cursor moves on by ``n``."""
+        import numpy as np
+        from .runtime import FlacChunk
+        n, p0 = int(n), self._pos
+        self._pos += n
+        p1 = min(p0 + n, self.frames)
+        if p0 >= p1:
+            return FlacChunk(self._data[:0], [0], [p0], self.channels, self.bits, self.frames, p0, n)
+        j0 = int(np.searchsorted(self._first, p0, side="right")) - 1
+        j1 = int(np.searchsorted(self._first, p1 - 1, side="right")) - 1
+        base = int(self._off[j0])
+        return FlacChunk(self._data[base:int(self._off[j1 + 1])], self._off[j0:j1 + 2] - np.uint64(base), self._first[j0:j1 + 2],
+                         self.channels, self.bits, self.frames, p0, n)
+
+    def close(self) -> None:
+        self._data = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class FlacWriter:

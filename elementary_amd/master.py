@@ -1,4 +1,4 @@
-"""``master_wav`` — a RIFF/WAVE file brought to a delivery spec ("-14 LUFS, -1 dBTP") on the GPU, in two passes over a pass-through
+"""``master_wav`` — a RIFF/WAVE or FLAC file brought to a delivery spec ("-14 LUFS, -1 dBTP") on the GPU, in two passes over a pass-through
 graph: the first meters the input (BS.1770 integrated loudness and true peak), the second applies ``target - measured`` dB of static
 gain and the look-ahead true-peak limiter and meters what it writes. No sample is scaled or limited on the host."""
 from __future__ import annotations
@@ -9,7 +9,15 @@ import numpy as np
 
 from . import el
 from .offline import OfflineRenderer
+from .flac import FlacReader
 from .wav import WavReader
+
+
+def _reader(path):
+    """The input's reader: ``FlacReader`` for a file that starts with ``fLaC`` (its frames are decoded on the GPU), else ``WavReader``."""
+    with open(path, "rb") as f:
+        flac = f.read(4) == b"fLaC"
+    return FlacReader(path) if flac else WavReader(path)
 
 
 def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, target_lufs: float = -14.0, ceiling_dbtp: float = -1.0,
@@ -35,8 +43,9 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
     unknown = set(limiter) - {"lookahead_ms", "release_ms", "link"}
     if unknown:
         raise ValueError(f"unknown limiter parameters: {sorted(unknown)}")
-    with WavReader(str(in_path)) as r:
+    with _reader(str(in_path)) as r:
         rate, channels, frames, in_fmt = float(r.sample_rate), int(r.channels), int(r.frames), r.fmt
+    sil_fmt = "s16" if in_fmt == "flac" else in_fmt      # (silence is fed as PCM: a FLAC input is decoded to PCM on the GPU anyway)
 
     def renderer(**kw):
         core = OfflineRenderer(engine_factory)
@@ -47,7 +56,7 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
         core.render(*[el.in_({"channel": c}) for c in range(channels)])
         # the roots fade in over 20 ms of engine time: let that pass on silence, then start the meter's programme
         warm = -(-int(0.05 * rate * k) // int(block_size)) * int(block_size)
-        core.process_pcm_io([silence(warm)], in_fmt, warm)
+        core.process_pcm_io([silence(warm)], sil_fmt, warm)
         core.loudness_reset()
         if k > 1:                                  # the converters' programmes start with the meter's
             core.input_resample_reset()
@@ -55,7 +64,7 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
         return core
 
     def silence(n):
-        shape, dtype = {"s16": ((n, channels), np.int16), "s24": ((n, channels, 3), np.uint8)}.get(in_fmt, ((n, channels), np.float32))
+        shape, dtype = {"s16": ((n, channels), np.int16), "s24": ((n, channels, 3), np.uint8)}.get(sil_fmt, ((n, channels), np.float32))
         return np.zeros(shape, dtype=dtype)
 
     params = dict(limiter, ceiling_dbtp=float(ceiling_dbtp))
@@ -64,8 +73,8 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
     latency = probe.limiter()["latency_frames"]
     del probe
     first = renderer()
-    first.process_pcm_io([silence(latency)], in_fmt, latency * k)      # (every call renders a multiple of k engine frames: it consumes its frames / k)
-    with WavReader(str(in_path)) as r:
+    first.process_pcm_io([silence(latency)], sil_fmt, latency * k)      # (every call renders a multiple of k engine frames: it consumes its frames / k)
+    with _reader(str(in_path)) as r:
         done = 0
         while done < frames:
             m = min(1 << 20, frames - done)
@@ -74,7 +83,7 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
     if k > 1:
         # what the second pass renders behind the file to take the converters' latencies out (OfflineRenderer._file_span)
         tail = first.resample()["latency_frames"] + (2 * first.input_resample()["latency_frames"] + k) // (2 * k)
-        first.process_pcm_io([silence(1)], in_fmt, tail * k)
+        first.process_pcm_io([silence(1)], sil_fmt, tail * k)
     measured = first.loudness()
     if not np.isfinite(measured["integrated_lufs"]):
         raise ValueError("the input passes no loudness gate: no gain brings it to a target")

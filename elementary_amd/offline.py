@@ -13,6 +13,11 @@ from typing import Any, Callable, Dict, List, Optional, Sequence
 import numpy as np
 
 
+def _is_flac(in_fmt) -> bool:
+    """``in_fmt`` 'flac' (or the C-ABI's 4): the inputs are ``FlacChunk`` objects, not arrays."""
+    return in_fmt.lower() == "flac" if isinstance(in_fmt, str) else in_fmt == 4
+
+
 class OfflineRenderer:
     def __init__(self, engine_factory: Callable[[float, int], Any]):
         self._factory = engine_factory
@@ -273,7 +278,8 @@ class OfflineRenderer:
         listening = any(self._listeners.values()) and hasattr(self._rt, "event_window_blocks")
         w = max(1, int(self._rt.event_window_blocks())) * bs if listening else max(total, 1)
         inres = getattr(self, "_inres", False) and self.num_in > 0
-        ins = [np.asarray(a) for a in inputs] if in_fmt is not None else None
+        flac_in = _is_flac(in_fmt)
+        ins = (list(inputs) if flac_in else [np.asarray(a) for a in inputs]) if in_fmt is not None else None
         parts, icur = [], 0
         drop_left, take_left = int(drop), None if take is None else int(take)
         for k in range(0, max(total, 1), w):
@@ -283,6 +289,9 @@ class OfflineRenderer:
                 ni = self._rt.input_resample_frames(m) if inres else m
                 x = []
                 for a in ins:
+                    if flac_in:
+                        x.append(a.at(icur, ni))
+                        continue
                     seg = a[icur:icur + ni]
                     if seg.shape[0] < ni:
                         seg = np.concatenate([seg, np.zeros((ni - seg.shape[0],) + a.shape[1:], dtype=a.dtype)])
@@ -546,7 +555,8 @@ class OfflineRenderer:
                        want_float: bool = False, sample_time: Optional[int] = None):
         """``process`` / ``process_pcm`` fed with interleaved PCM that is unpacked on the GPU (``Runtime.process_blocks_pcm_io``):
         ``in_streams`` are arrays in stream layout (``WavReader.read``, or what ``process_pcm`` returns) that together hold the
-        ``num_input_channels`` input channels; a stream shorter than ``num_frames`` is padded with silence. ``out_fmt`` None: returns
+        ``num_input_channels`` input channels; a stream shorter than ``num_frames`` is padded with silence. ``in_fmt`` 'flac': the
+        streams are ``FlacChunk`` objects (``FlacReader.read``) — FLAC frames that are decoded on the GPU. ``out_fmt`` None: returns
         float32 ``[num_output_channels, num_frames]``; else ``(streams, stats, planar)`` as ``process_pcm`` does. With listeners attached
         the render walks ``event_window_blocks()`` windows with the blockwise relay between them, as ``process`` does. With
         ``initialize(limiter=...)`` what comes back is limited and carries the limiter's latency: frame n is the limited render at
@@ -554,14 +564,15 @@ class OfflineRenderer:
         pcm_io = getattr(self._rt, "process_blocks_pcm_io", None)
         if pcm_io is None:
             raise RuntimeError("this engine takes no PCM input (process_blocks_pcm_io)")
-        ins = [np.asarray(a) for a in in_streams]
-        if sum(int(a.shape[1]) for a in ins) != self.num_in:
+        flac_in = _is_flac(in_fmt)        # ``in_streams``: FlacChunk objects (``FlacReader.read``), decoded on the GPU
+        ins = list(in_streams) if flac_in else [np.asarray(a) for a in in_streams]
+        if sum(int(a.channels if flac_in else a.shape[1]) for a in ins) != self.num_in:
             raise ValueError(f"Invalid input data; expected {self.num_in} channels in all.")
         if out_fmt is not None and int(num_streams) * int(channels_per_stream) != self.num_out:
             raise ValueError(f"Invalid stream layout; expected {self.num_out} channels in all.")
         bs = self.block_size
         inres = getattr(self, "_inres", False) and bool(ins)
-        total = int(num_frames) if num_frames is not None else (int(ins[0].shape[0]) if ins else 0)
+        total = int(num_frames) if num_frames is not None else (int(ins[0].count if flac_in else ins[0].shape[0]) if ins else 0)
         if inres and num_frames is None:          # (the streams' length in ENGINE frames)
             iinfo = self._rt.input_resample_read()
             total = -((-total * iinfo["up"]) // iinfo["down"])
@@ -576,6 +587,9 @@ class OfflineRenderer:
             ni = self._rt.input_resample_frames(m) if inres else m
             x = []
             for a in ins:
+                if flac_in:               # (the engine looks the covering frames up; past the stream's end is silence)
+                    x.append(a.at(icur, ni))
+                    continue
                 seg = a[icur:icur + ni]
                 if seg.shape[0] < ni:     # (silence is all-zero bytes in every format)
                     seg = np.concatenate([seg, np.zeros((ni - seg.shape[0],) + a.shape[1:], dtype=a.dtype)])
@@ -602,7 +616,8 @@ class OfflineRenderer:
                     dither_seed: Optional[int] = None, chunk_frames: int = 1 << 20):
         """RIFF/WAVE files through the graph into RIFF/WAVE files, ``chunk_frames`` (rounded to whole blocks) per engine call; the samples
         cross the host as they lie in the files and are converted on the GPU in both directions (``out_fmt`` 'flac16' / 'flac24': FLAC
-        files instead, encoded on the GPU — ``write_flac``'s). ``in_paths``: one name or a list —
+        files instead, encoded on the GPU — ``write_flac``'s). An input that starts with ``fLaC`` is read by ``FlacReader``: its frames
+        cross the host compressed and are decoded on the GPU (the STREAMINFO MD5 is not verified). ``in_paths``: one name or a list —
         the files' channels become the input channels in file order (files of one format, one channel count and the renderer's
         sample rate — or, with ``initialize(input_sample_rate=...)``, that rate: a file of F frames then renders ceil(F L / M) engine
         frames, L / M = engine rate / input rate, and the input converter's latency is taken out with the others, to under half a
@@ -610,6 +625,7 @@ class OfflineRenderer:
         the (longest) input's length; longer than that — a reverb's tail — renders the rest from silence. Returns the statistics
         (with the loudness meter on: ``integrated_lufs`` and ``true_peak_dbtp`` of the meter's programme so far included, as ``write_wav``;
         with the limiter on: ``limiter_max_reduction_db`` of this file)."""
+        from .flac import FlacReader
         from .wav import WavReader, WavWriter
         ins = [str(in_paths)] if isinstance(in_paths, (str, bytes)) or hasattr(in_paths, "__fspath__") else [str(p) for p in in_paths]
         G = self.num_out if channels_per_stream is None else int(channels_per_stream)
@@ -629,7 +645,9 @@ class OfflineRenderer:
         readers, writers, stats = [], [], None
         try:
             for p in ins:
-                readers.append(WavReader(p))
+                with open(p, "rb") as probe:
+                    is_flac = probe.read(4) == b"fLaC"
+                readers.append(FlacReader(p) if is_flac else WavReader(p))      # (a FLAC file is decoded on the GPU: its frames cross the host as they are)
             for r in readers:
                 if r.sample_rate != int(round(getattr(self, "input_sample_rate", self.sample_rate))):
                     raise ValueError(f"sample rate {r.sample_rate} of an input file, the renderer runs at {int(round(self.sample_rate))}")

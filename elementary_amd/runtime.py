@@ -103,6 +103,13 @@ def load_library() -> C.CDLL:
         lib.elemhip_flac_encode.argtypes = [C.POINTER(C.POINTER(C.c_int32)), C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                             C.POINTER(C.c_uint8), C.c_size_t, _szp, _u32p, C.c_size_t, _szp]
         lib.elemhip_flac_encode.restype = C.c_int
+        _u64p = C.POINTER(C.c_uint64)
+        lib.elemhip_flac_index.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p, C.c_size_t, _szp]
+        lib.elemhip_flac_index.restype = C.c_int
+        lib.elemhip_flac_decode.argtypes = [C.POINTER(_FlacIn), C.c_size_t, C.POINTER(C.POINTER(C.c_int32)), _szp, _u32p]
+        lib.elemhip_flac_decode.restype = C.c_int
+        lib.elemhip_flac_in_error.argtypes = [C.c_void_p, _u32p, _u64p, _u32p]
+        lib.elemhip_flac_in_error.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -172,16 +179,106 @@ def flac_encode(codes, bits: int = 16, flac_frame: int = 4096, sample_rate: int 
     return out[:nbytes.value].tobytes(), lens[:nframes.value].copy()
 
 
+class _FlacIn(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("bytes", C.c_uint64), ("frame_offsets", C.c_void_p), ("frame_first_samples", C.c_void_p),
+                ("frames", C.c_uint64), ("channels", C.c_uint32), ("bits", C.c_uint32), ("total_samples", C.c_uint64), ("position", C.c_uint64)]
+
+
+FLAC_IN_REASONS = {1: "bad CRC", 2: "reserved value", 3: "bits missing", 4: "non-zero padding", 5: "sample out of range", 6: "unsupported"}
+
+
+class FlacChunk:
+    """A FLAC input (``in_fmt='flac'``): the frames that cover stream samples ``[position, position + count)`` — ``data`` (uint8, the
+    frames' bytes), ``offsets`` / ``first_samples`` (uint64, ``frames + 1`` entries: byte offsets into ``data``, stream samples) — of a
+    stream of ``channels`` channels and ``bits`` bits that holds ``total_samples`` samples. What ``FlacReader.read`` returns."""
+
+    def __init__(self, data, offsets, first_samples, channels: int, bits: int, total_samples: int, position: int, count: int):
+        import numpy as np
+        self.data = np.ascontiguousarray(data, dtype=np.uint8)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self.first_samples = np.ascontiguousarray(first_samples, dtype=np.uint64)
+        if len(self.offsets) != len(self.first_samples) or len(self.offsets) < 1:
+            raise ValueError("a FLAC table holds frames + 1 entries of offset and first sample")
+        self.channels, self.bits, self.total_samples, self.position, self.count = int(channels), int(bits), int(total_samples), int(position), int(count)
+
+    @property
+    def frames(self) -> int:
+        return len(self.offsets) - 1
+
+    def at(self, offset: int, count: int) -> "FlacChunk":
+        """The same frames read from ``position + offset`` on for ``count`` samples (the engine looks the covering frames up itself)."""
+        return FlacChunk(self.data, self.offsets, self.first_samples, self.channels, self.bits, self.total_samples, self.position + int(offset), count)
+
+    def struct(self) -> "_FlacIn":
+        return _FlacIn(self.data.ctypes.data, self.data.size, self.offsets.ctypes.data, self.first_samples.ctypes.data, self.frames,
+                       self.channels, self.bits, self.total_samples, self.position)
+
+
+def _need_chunks(chunks, call: str) -> None:
+    """Input format 4 points the engine at ``elemhip_flac_in`` structs: anything but a ``FlacChunk`` is refused here, with the code the
+    engine gives a malformed one."""
+    if any(not isinstance(c, FlacChunk) for c in chunks):
+        err = ElemHipError(f"{call} failed: {describe(8)} (code 8): a FLAC input stream is a FlacChunk")
+        err.code = 8
+        raise err
+
+
+def _flac_in_pointers(chunks):
+    """The ``elemhip_flac_in`` structs of a call's chunks and the pointer array over them (both have to outlive the call)."""
+    structs = (_FlacIn * max(1, len(chunks)))(*[c.struct() for c in chunks])
+    ptrs = (C.c_void_p * max(1, len(chunks)))(*[C.addressof(structs[i]) for i in range(len(chunks))])
+    return structs, ptrs
+
+
+def flac_index(data, channels: int, bits: int, block_size: int = 0):
+    """``elemhip_flac_index``: a stream's frame bytes (behind its metadata) -> ``(offsets, first_samples)``, uint64 arrays of
+    ``frames + 1`` entries (the closing entry: ``len(data)`` and the samples in all)."""
+    import numpy as np
+    lib = load_library()
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    cap = 0
+    while True:
+        off, first = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint64)
+        need = C.c_size_t(0)
+        rc = lib.elemhip_flac_index(a.ctypes.data_as(C.POINTER(C.c_uint8)), a.size, int(channels), int(bits), int(block_size),
+                                    off.ctypes.data_as(C.POINTER(C.c_uint64)), first.ctypes.data_as(C.POINTER(C.c_uint64)), cap, C.byref(need))
+        if rc != 0:
+            err = ElemHipError(f"elemhip_flac_index failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        if need.value <= cap:
+            return off[:need.value].copy(), first[:need.value].copy()
+        cap = need.value
+
+
+def flac_decode(chunk: "FlacChunk", count: Optional[int] = None):
+    """``elemhip_flac_decode``: the scalar twin of the decode kernels — the chunk's samples ``[position, position + count)`` as int32
+    ``[channels, count]`` (zeros past the stream's end). A frame that does not decode raises with ``.code`` 106, ``.frame``, ``.reason``."""
+    import numpy as np
+    lib = load_library()
+    n = chunk.count if count is None else int(count)
+    out = np.zeros((chunk.channels, max(n, 1)), dtype=np.int32)
+    rows = (C.POINTER(C.c_int32) * max(1, chunk.channels))(*[out[c].ctypes.data_as(C.POINTER(C.c_int32)) for c in range(chunk.channels)])
+    st = chunk.struct()
+    bad, reason = C.c_size_t(0), C.c_uint32(0)
+    rc = lib.elemhip_flac_decode(C.byref(st), n, rows, C.byref(bad), C.byref(reason))
+    if rc != 0:
+        err = ElemHipError(f"elemhip_flac_decode failed: {describe(rc)} (code {rc}; frame {bad.value}: {FLAC_IN_REASONS.get(reason.value, reason.value)})")
+        err.code, err.frame, err.reason = rc, bad.value, reason.value
+        raise err
+    return out[:, :n]
+
+
 class _LoudnessResult(C.Structure):
     _fields_ = [("integrated", C.c_double), ("momentary_max", C.c_double), ("short_term_max", C.c_double),
                 ("blocks", C.c_uint64), ("gated_blocks", C.c_uint64)]
 
 
-PCM_FORMATS = {"s16": 1, "s24": 2, "f32": 3}
+PCM_FORMATS = {"s16": 1, "s24": 2, "f32": 3, "flac": 4}
 
 
 def pcm_format(fmt) -> int:
-    """'s16' / 's24' / 'f32' (or the C-ABI's 1 / 2 / 3) -> the C-ABI's format number; anything else is handed on for the engine to refuse."""
+    """'s16' / 's24' / 'f32' (or the C-ABI's 1 / 2 / 3; as an input also 'flac', 4) -> the C-ABI's format number; anything else is handed on for the engine to refuse."""
     return PCM_FORMATS.get(fmt.lower(), 0) if isinstance(fmt, str) else int(fmt)
 
 
@@ -322,14 +419,20 @@ class Runtime(CRuntime):
         is input channel ``s * G + g`` (``G`` is read off the arrays unless ``in_channels_per_stream`` says it). s16 samples are worth
         ``code * 2**-15``, s24 ``code * 2**-23``, f32 passes as bits. ``out_fmt`` None: returns float32 ``[num_outputs, frames]`` as
         ``process_blocks_host`` does; else ``(streams, stats, planar)`` as ``process_blocks_pcm`` does for ``num_streams`` streams of
-        ``channels_per_stream`` channels in ``out_fmt``.
+        ``channels_per_stream`` channels in ``out_fmt``. ``in_fmt`` 'flac': ``in_streams`` is a list of ``FlacChunk`` objects, one per
+        stream — FLAC frames, decoded on the GPU into the s16 / s24 stream of the same samples; a frame that does not decode raises
+        with ``.code`` 106 (``flac_in_error()`` names it).
         """
         import numpy as np
         from ._cabi import _ptr_array
         in_code = pcm_format(in_fmt)
         want = {1: (np.int16, 2), 2: (np.uint8, 3), 3: (np.float32, 2)}.get(in_code)
         ins = []
-        for a in (in_streams or []):
+        chunks = list(in_streams or []) if in_code == 4 else []      # FLAC: FlacChunk objects, decoded on the GPU
+        _need_chunks(chunks, "elemhip_process_blocks_pcm_io")
+        if chunks and num_frames is None:
+            num_frames = chunks[0].count
+        for a in ([] if in_code == 4 else (in_streams or [])):
             a = np.ascontiguousarray(a)
             if want is not None and (a.dtype != want[0] or a.ndim != want[1] or (in_code == 2 and a.shape[2] != 3)):
                 raise ValueError(f"a {in_fmt} input stream is {np.dtype(want[0]).name} [frames, G{', 3' if in_code == 2 else ''}], got {a.dtype} {a.shape}")
@@ -348,13 +451,17 @@ class Runtime(CRuntime):
         if ins and want is not None and in_channels_per_stream is None and ins[0].shape[0] < need:
             raise ValueError(f"the input streams hold {ins[0].shape[0]} frames, {need} are asked for")
         ip = (C.c_void_p * max(1, len(ins)))(*[C.c_void_p(a.ctypes.data) for a in ins])
+        if chunks:
+            keep, ip = _flac_in_pointers(chunks)
+            ins, in_g = chunks, (int(in_channels_per_stream) if in_channels_per_stream is not None else chunks[0].channels)
         in_spec = _PcmInSpec(in_code, in_g)
         st = self.sample_time if sample_time is None else int(sample_time)
         nd = self.resample_frames(n)          # frames delivered (option "resample_rate"; n while it is off)
         if out_fmt is None:
             if num_outputs is None:
                 raise ValueError("num_outputs is needed for planar float output")
-            out = np.empty((int(num_outputs), nd), dtype=np.float32)
+            # (a FLAC-fed call can end after some launch sets, code 106: what it did not deliver is then zeros, not stale memory)
+            out = (np.zeros if chunks else np.empty)((int(num_outputs), nd), dtype=np.float32)
             rc = self._lib.elemhip_process_blocks_pcm_io(self._h, ip, len(ins), C.byref(in_spec), None, 0, None,
                                                          _ptr_array([out[i] for i in range(int(num_outputs))]), int(num_outputs), n, st, None)
             result = out
@@ -375,6 +482,7 @@ class Runtime(CRuntime):
         if rc != 0:
             err = ElemHipError(f"elemhip_process_blocks_pcm_io failed: {describe(rc)} (code {rc})")
             err.code = rc
+            err.result = result       # (after 106: the whole launch sets in front of the failing one, zeros behind them)
             raise err
         if sample_time is None:
             self.sample_time += ((n + self.block_size - 1) // self.block_size) * self.block_size
@@ -403,10 +511,17 @@ class Runtime(CRuntime):
             num_frames = self._frames_for_inputs(a.shape[1], num_frames)
         elif inputs is not None:
             in_code = pcm_format(in_fmt)
-            ins = [np.ascontiguousarray(a) for a in inputs]
-            in_g = int(ins[0].shape[1]) if ins and ins[0].ndim > 1 else 1
-            if num_frames is None and ins:
-                num_frames = self._frames_for_inputs(ins[0].shape[0], None)
+            if in_code == 4:
+                ins = list(inputs)
+                _need_chunks(ins, "elemhip_process_blocks_flac")
+                in_g = ins[0].channels if ins else 1
+                if num_frames is None and ins:
+                    num_frames = ins[0].count
+            else:
+                ins = [np.ascontiguousarray(a) for a in inputs]
+                in_g = int(ins[0].shape[1]) if ins and ins[0].ndim > 1 else 1
+                if num_frames is None and ins:
+                    num_frames = self._frames_for_inputs(ins[0].shape[0], None)
         if num_frames is None:
             raise ValueError("num_frames is needed without inputs")
         n, S, G = int(num_frames), int(num_streams), int(channels_per_stream)
@@ -417,7 +532,10 @@ class Runtime(CRuntime):
         sp = (C.c_void_p * max(1, S))(*[C.c_void_p(a.ctypes.data) for a in bufs])
         caps = (C.c_size_t * max(1, S))(*([cap] * S))
         got = (C.c_size_t * max(1, S))()
-        ip = (C.c_void_p * max(1, len(ins)))(*[C.c_void_p(a.ctypes.data) for a in ins])
+        if in_code == 4 and in_fmt is not None:
+            keep, ip = _flac_in_pointers(ins)
+        else:
+            ip = (C.c_void_p * max(1, len(ins)))(*[C.c_void_p(a.ctypes.data) for a in ins])
         in_spec = _PcmInSpec(in_code, in_g)
         stats = (_PcmChannelStats * max(1, S * G))()
         spec = _FlacSpec(b, G, 0 if dither_seed is None else 1, 0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFF,
@@ -434,6 +552,17 @@ class Runtime(CRuntime):
                      "over": np.array([stats[c].over for c in range(S * G)], dtype=np.uint64),
                      "nonfinite": np.array([stats[c].nonfinite for c in range(S * G)], dtype=np.uint64)}
         return [bufs[s][:got[s]].tobytes() for s in range(S)], out_stats
+
+    def flac_in_error(self) -> Dict[str, Any]:
+        """``elemhip_flac_in_error``: ``{'stream', 'frame', 'reason', 'text'}`` of the last call that answered 106 — the first FLAC
+        input frame that did not decode (``frame``: its index in the stream's table as the call was given it)."""
+        s, f, r = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        rc = self._lib.elemhip_flac_in_error(self._h, C.byref(s), C.byref(f), C.byref(r))
+        if rc != 0:
+            err = ElemHipError(f"elemhip_flac_in_error failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return {"stream": s.value, "frame": f.value, "reason": r.value, "text": FLAC_IN_REASONS.get(r.value, str(r.value))}
 
     def flac_read(self) -> Dict[str, Any]:
         """``elemhip_flac_read``: the FLAC programme so far — ``{'flac_frame', 'bits', 'channels_per_stream', 'streams', 'sample_rate',

@@ -281,6 +281,38 @@ int elemhip_flac_encode(const int32_t* const* planar, uint32_t channels, size_t 
                         uint32_t firstFrameNumber, int flush, uint8_t* out, size_t capacity, size_t* bytesOut, uint32_t* frameBytes, size_t frameCap,
                         size_t* framesOut);
 
+/* EXTENSION (no counterpart in the reference): the same render FED with FLAC, decoded on the GPU in front of the unpack kernel (or
+ * the input-rate converter) of every launch set (elementary_amd/csrc/flac_decode.hip; the arithmetic: flac_decode.h). Input format
+ *   format  4: inStreams[s] points at an elemhip_flac_in — the stream's frames (the bytes behind its metadata blocks), the table
+ *           elemhip_flac_index makes of them (frames + 1 entries: byte offset and first sample of every frame, one closing entry) and
+ *           `position`, the stream sample at the call's first input frame. channels_per_stream has to be the streams' channel count,
+ *           and all streams of a call have one sample size.
+ * of elemhip_process_blocks_pcm_io and elemhip_process_blocks_flac. Only the frames that cover a launch set's input frames cross the
+ * host link. A sample of `bits` <= 16 bits is worth code * 2^-(bits - 1), as the s16 sample code << (16 - bits) is; above 16 bits as
+ * the s24 sample code << (24 - bits): the floats a graph sees are bit for bit those of the PCM input of the same samples, however the
+ * render is cut into calls (a frame that straddles two launch sets or calls is decoded in both). Input frames past the table's
+ * closing entry are silence; total_samples (the whole stream's length, where the table is a slice of it) is carried for the caller's
+ * book-keeping and not read by the engine. With "input_rate" on a call pulls elemhip_input_resample_frames(numFrames) input frames from `position`.
+ * What is read: fixed-block-size streams of 8 / 12 / 16 / 20 / 24 bits, 1 .. 8 channels, blocks of 16 .. 16384 samples (a shorter last
+ * one), CONSTANT / VERBATIM / FIXED / LPC subframes, wasted bits, both residual coding methods with escapes, all channel assignments;
+ * every frame's CRC-16 is verified on the GPU. Not read: variable block size, 32-bit samples, blocks above 16384; STREAMINFO's MD5 is
+ * not verified (the decoded samples never reach the host).
+ * Codes: 8 for a NULL field, a sample size or channel count outside the above, or channels_per_stream unequal to a stream's channels;
+ * 106 where a frame does not decode — elemhip_flac_in_error then names the first such (stream, frame index in the stream's table) and
+ * the reason: 1 bad CRC, 2 reserved value, 3 bits missing, 4 non-zero padding, 5 sample out of range, 6 unsupported. A call that
+ * answers 106 has delivered the launch sets in front of the failing one and renders nothing further; the engine stays usable.
+ *   elemhip_flac_index   pure host arithmetic, no handle: a stream's frame bytes -> the table. *entries receives the entries the
+ *                        stream needs (frames + 1); the tables are filled up to `capacity` entries — call again with more where it was
+ *                        too small. blockSize 0: the first frame's. Code 106 where the bytes hold no frame this decoder reads.
+ *   elemhip_flac_decode  pure host arithmetic, no handle: the scalar twin of the kernels — stream samples [position, position + count)
+ *                        as planar int32 codes (zeros past the end). Code 106 with *badFrame / *reason on a frame that fails. */
+typedef struct elemhip_flac_in { const uint8_t* data; uint64_t bytes; const uint64_t* frame_offsets; const uint64_t* frame_first_samples;
+                                 uint64_t frames; uint32_t channels, bits; uint64_t total_samples, position; } elemhip_flac_in;
+int elemhip_flac_index(const uint8_t* data, size_t bytes, uint32_t channels, uint32_t bits, uint32_t blockSize, uint64_t* frameOffsets,
+                       uint64_t* frameFirstSamples, size_t capacity, size_t* entries);
+int elemhip_flac_decode(const elemhip_flac_in* in, size_t count, int32_t* const* planar, size_t* badFrame, uint32_t* reason);
+int elemhip_flac_in_error(elemhip_t*, uint32_t* stream, uint64_t* frame, uint32_t* reason);   /* of the last call that answered 106 (code 6: none) */
+
 /* bool addSharedResource(name, unique_ptr<SharedResource>)       Runtime.h:83,461-465 (insert-only) */
 int    elemhip_add_shared_resource(elemhip_t*, const char* name, const float* const* channels, size_t nCh, size_t nSamples);
 /* void pruneSharedResources()                                    Runtime.h:89,467-471 */
