@@ -226,10 +226,24 @@ int elemhip_flac_read(elemhip_t* h, elemhip_flac_info* info, elemhip_flac_stream
 
 int elemhip_flac_reset(elemhip_t* h) { return h ? h->engine.flacReset() : elemhip::kInvalidInstructionFormat; }
 
+int elemhip_flac_lpc_order(elemhip_t* h, uint32_t* order) {
+    if (!h || !order) return elemhip::kInvalidInstructionFormat;
+    *order = h->engine.flacLpcOrder();
+    return elemhip::kOk;
+}
+
 int elemhip_flac_encode(const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t flacFrame, uint32_t bits, uint32_t sampleRate,
                         uint32_t firstFrameNumber, int flush, uint8_t* out, size_t capacity, size_t* bytesOut, uint32_t* frameBytes, size_t frameCap,
                         size_t* framesOut) {
+    return elemhip_flac_encode_lpc(planar, channels, frames, flacFrame, bits, sampleRate, firstFrameNumber, flush, out, capacity, bytesOut, frameBytes, frameCap,
+                                   framesOut, 0u);
+}
+
+int elemhip_flac_encode_lpc(const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t flacFrame, uint32_t bits, uint32_t sampleRate,
+                            uint32_t firstFrameNumber, int flush, uint8_t* out, size_t capacity, size_t* bytesOut, uint32_t* frameBytes, size_t frameCap,
+                            size_t* framesOut, uint32_t lpcOrder) {
     namespace fe = flac_encode;
+    if (!fe::lpc_order_ok(lpcOrder)) return elemhip::kInvalidPropertyValue;
     if (!fe::frame_ok(flacFrame) || !fe::bits_ok(bits) || channels == 0u || channels > fe::kMaxChannels || !bytesOut || (frames && !planar) || (capacity && !out))
         return elemhip::kInvalidInstructionFormat;
     const size_t count = frames / flacFrame + (flush && frames % flacFrame ? 1u : 0u);
@@ -241,7 +255,7 @@ int elemhip_flac_encode(const int32_t* const* planar, uint32_t channels, size_t 
         for (size_t i = 0; i < frames; ++i) if (planar[c][i] < -lim || planar[c][i] >= lim) return elemhip::kInvalidPropertyValue;
     }
     size_t done = 0;
-    const size_t n = fe::encode_host(planar, channels, frames, flacFrame, bits, sampleRate, firstFrameNumber, flush != 0, out, capacity, frameBytes, &done);
+    const size_t n = fe::encode_host(planar, channels, frames, flacFrame, bits, sampleRate, firstFrameNumber, flush != 0, out, capacity, frameBytes, &done, lpcOrder);
     if (n == (size_t)-1) return elemhip::kTooManyChannels;
     *bytesOut = n;
     if (framesOut) *framesOut = done;

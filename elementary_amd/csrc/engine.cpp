@@ -540,6 +540,13 @@ int Engine::setOption(const std::string& key, double value) {
     if (key.compare(0, 7, "limiter") == 0) return setLimiterOption(key, value);
     // flac_encode.h: the block size (256, 512, 1024, 2048, 4096) and the sample size (16, 24) of FLAC delivery. A programme keeps the
     // values it started with: while one is open another value is refused (flacReset first). No other call is touched.
+    // flac_lpc.h: the LPC order P (0 .. 12; 0, the default: none — not one byte, launch or allocation differs). The programme keeps it too.
+    if (key == "flac_lpc_order") {
+        if (!(value >= 0.0) || value > (double)flac_encode::kLpcMaxOrder || value != std::floor(value)) return kInvalidPropertyValue;
+        if (flacStreams != 0u && (uint32_t)value != flacLpc) return kInvalidPropertyValue;
+        flacLpcOpt = (uint32_t)value;
+        return kOk;
+    }
     if (key == "flac_frame" || key == "flac_bits") {
         const bool frame = key == "flac_frame";
         const uint32_t v = value >= 0.0 && value <= 65536.0 && value == std::floor(value) ? (uint32_t)value : 0u;

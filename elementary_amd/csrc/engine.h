@@ -286,7 +286,7 @@ public:
     // maxReduction[group] (the largest d behind a delivered gain, 0 .. 1) / limitedFrames[group] (frames with g < 1): `capacity` entries each
     int limiterRead(LimiterInfo* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity);
     int limiterReset();
-    // FLAC delivery (flac_encode.h; options "flac_frame" 256 .. 4096, default 4096, and "flac_bits" 16 / 24): the host-buffer render
+    // FLAC delivery (flac_encode.h; options "flac_frame" 256 .. 4096, default 4096, "flac_bits" 16 / 24 and "flac_lpc_order" 0 .. 12): the host-buffer render
     // delivered as RFC 9639 frames of a fixed block size, encoded on the GPU in the pack kernel's place (flac_encode.hip) — behind the
     // converter and the limiter, next to the meter. The sample values are processBlocksPcm's codes for the same render. The programme is
     // the frames FLAC calls delivered since creation or flacReset; FLAC frame j holds its frames [j F, (j + 1) F). A call returns the
@@ -302,6 +302,8 @@ public:
     // perStream: `capacity` entries; frameBytes (may be null): [stream][frameCap], the byte length of every frame emitted so far
     int flacRead(FlacInfo* info, FlacStreamInfo* perStream, size_t capacity, uint32_t* frameBytes, size_t frameCap);
     int flacReset();
+    // option "flac_lpc_order" (flac_lpc.h; 0 .. 12, default 0: none): the open programme's, else the option's
+    uint32_t flacLpcOrder();
     // render `numBlocks` blocks with a HIP event pair around every kernel launch; msOut[l] = mean
     // duration of launch level l (l < numLevels), msOut[numLevels] = epilogue. Returns levels + 1.
     int timeLaunches(size_t nOut, size_t numBlocks, float* msOut, size_t cap);
@@ -527,7 +529,8 @@ private:
         uint64_t dropLeft = 0, takeLeft = 0;    // of the call's delivered frames still to come
         size_t statsOff = 0, payloadOff = 0, stride = 0;
     };
-    uint32_t flacFrameOpt = 4096, flacBitsOpt = 16;
+    uint32_t flacFrameOpt = 4096, flacBitsOpt = 16, flacLpcOpt = 0;
+    uint32_t flacLpc = 0;       // the programme's LPC order (flac_lpc.h), taken with flacFF
     uint32_t flacFF = 0, flacBits = 0, flacG = 0, flacStreams = 0, flacRate = 0, flacOpen = 0;      // the programme (flacStreams 0: none yet)
     bool flacFlushed = false;
     uint64_t flacFrames = 0, flacEmitted = 0;   // programme frames delivered; FLAC frames emitted per stream

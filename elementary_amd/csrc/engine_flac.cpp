@@ -1,4 +1,4 @@
-// engine_flac.cpp — the host side of FLAC delivery (options "flac_frame", "flac_bits"; flac_encode.h, flac_encode.hip): the programme's
+// engine_flac.cpp — the host side of FLAC delivery (options "flac_frame", "flac_bits", "flac_lpc_order"; flac_encode.h, flac_encode.hip): the programme's
 // state, the device buffers' life, the hand-over of a set's frames to the caller's buffers, the flush, the read-out and the reset. The
 // set loop that launches the kernels is renderHostSets (engine_render.cpp).
 #include "engine_impl.h"
@@ -20,7 +20,7 @@ void Engine::flacFree() {
 
 // a new programme: nothing open, frame number 0; its shape is set by the first call (`mu` held)
 int Engine::flacResetLocked() {
-    flacFF = flacBits = flacG = flacStreams = flacRate = flacOpen = 0;
+    flacFF = flacBits = flacG = flacStreams = flacRate = flacOpen = flacLpc = 0;
     flacFlushed = false; flacFrames = flacEmitted = 0;
     flacFrameBytes.clear();
     return kOk;
@@ -34,7 +34,7 @@ int Engine::ensureFlac(FlacJob& job, size_t setFrames) {
     if (flacStreams == 0) {
         const double rate = deliveryRate();
         if (!(rate >= 1.0) || rate > 1048575.0 || rate != std::floor(rate)) return kInvalidPropertyValue;       // (STREAMINFO holds 20 bits of Hz)
-        flacFF = flacFrameOpt; flacBits = bits; flacG = G; flacStreams = S; flacRate = (uint32_t)rate; flacOpen = 0;
+        flacFF = flacFrameOpt; flacLpc = flacLpcOpt; flacBits = bits; flacG = G; flacStreams = S; flacRate = (uint32_t)rate; flacOpen = 0;
         flacFrameBytes.assign(S, std::vector<uint32_t>());
     } else if (flacBits != bits || flacG != G || flacStreams != S || flacRate != (uint32_t)deliveryRate()) return kInvalidPropertyValue;
     const uint32_t ff = flacFF;
@@ -180,6 +180,7 @@ int Engine::flacFlush(void* const* outStreams, const size_t* capacities, size_t*
     ea.codes = dFlacCodes; ea.slots = dFlacSlots; ea.subBits = dFlacSubBits; ea.dst = dPcm[0] + job.payloadOff; ea.frameBytes = reinterpret_cast<uint32_t*>(dPcm[0]);
     ea.streamStride = job.stride; ea.cap = (uint32_t)flacCodesCap; ea.G = flacG; ea.numStreams = flacStreams; ea.bits = flacBits; ea.flacFrame = flacFF;
     ea.n = flacOpen; ea.numFrames = 1u; ea.slotWords = fe::slot_words(flacFF, flacBits); ea.rate = flacRate; ea.firstNumber = (uint32_t)flacEmitted;
+    ea.lpcOrder = flacLpc;
     HIP_OK(launch_flac_encode(stream, ea));
     HIP_OK(hipMemcpyAsync(hPcm[0], dPcm[0], job.payloadOff + (size_t)flacStreams * job.stride, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
@@ -214,6 +215,11 @@ int Engine::flacRead(FlacInfo* info, FlacStreamInfo* perStream, size_t capacity,
         }
     }
     return kOk;
+}
+
+uint32_t Engine::flacLpcOrder() {
+    RenderGuard lock(*this);
+    return flacStreams ? flacLpc : flacLpcOpt;
 }
 
 int Engine::flacReset() {

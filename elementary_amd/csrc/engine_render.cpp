@@ -1402,7 +1402,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 for (uint32_t g = 0; g < G; ++g) planar[g] = flacCodes[s * G + g].data();
                 size_t count = 0;
                 const size_t n = flac_encode::encode_host(planar, G, nF * ff, ff, bits, flacRate, (uint32_t)flacEmitted, false,
-                                                          static_cast<uint8_t*>(flac->streams[s]) + flac->bytes[s], flac->caps[s] - flac->bytes[s], lens.data(), &count);
+                                                          static_cast<uint8_t*>(flac->streams[s]) + flac->bytes[s], flac->caps[s] - flac->bytes[s], lens.data(), &count, flacLpc);
                 if (n == (size_t)-1 || count != nF) return kInvariantViolation;
                 flac->bytes[s] += n;
                 flacFrameBytes[s].insert(flacFrameBytes[s].end(), lens.begin(), lens.end());
@@ -1811,6 +1811,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 ea.frameBytes = reinterpret_cast<uint32_t*>(dPcm[half]); ea.streamStride = flac->stride; ea.cap = (uint32_t)flacCodesCap;
                 ea.G = flac->spec.channelsPerStream; ea.numStreams = (uint32_t)flac->nStreams; ea.bits = flac->spec.bits; ea.flacFrame = ff; ea.n = ff;
                 ea.numFrames = nF; ea.slotWords = flac_encode::slot_words(ff, flac->spec.bits); ea.rate = flacRate; ea.firstNumber = (uint32_t)flacEmitted;
+                ea.lpcOrder = flacLpc;
                 HOST_TRY(launch_flac_encode(stream, ea));
                 HOST_TRY(launch_flac_carry(stream, dFlacCodes, dFlacCarry, (uint32_t)nOut, (uint32_t)flacCodesCap, ff, nF * ff, rem));
                 flacOpen = rem; flacEmitted += nF; flacFrames += enter;

@@ -6,7 +6,10 @@
 // EXACT bit counts before a bit is written; a block of equal samples is CONSTANT, otherwise the smallest count wins and ties go to
 // the simpler kind and then the lower number
 // (CONSTANT, VERBATIM, FIXED 0..4; lower partition order; lower Rice parameter, a parameter before the escape; independent, left/side,
-// side/right, mid/side). Integer arithmetic only: the kernel's bytes are encode_host()'s.
+// side/right, mid/side). With option "flac_lpc_order" = P > 0 two LPC orders (P and ceil(P / 2), flac_lpc.h) are priced on top, to the bit
+// like the FIXED ones; they come last in the tie rule, by ascending order. Integer arithmetic only — but for the LPC coefficients'
+// recursion and quantisation, which one lane does in double under the rules flac_lpc.h states (+ - x / and floor() in a written order,
+// no contraction) and the twin repeats statement by statement: the kernel's bytes are encode_host()'s.
 //
 // The kernels (flac_encode.hip):
 //   stage     thread <-> frame of a channel row: quantise, fold the statistics, codes to [channel][programme frame] behind the carried ones
@@ -26,6 +29,7 @@
 #include <vector>
 
 #include "pcm_pack.h"
+#include "flac_lpc.h"
 
 namespace flac_encode {
 
@@ -33,6 +37,8 @@ constexpr uint32_t kThreads = 256;
 constexpr uint32_t kMaxFrame = 4096;
 constexpr uint32_t kMaxChannels = 8;           // channels of one stream
 constexpr uint32_t kMaxOrder = 4;
+constexpr uint32_t kRows = kMaxOrder + 1u + kLpcSlots;      // rows of the pricing tables: FIXED 0 .. 4, then the priced LPC orders
+PCM_CX uint32_t lpc_row(uint32_t slot) { return kMaxOrder + 1u + slot; }
 constexpr uint32_t kLevels = 9;                // tree levels 0..8: level L has 2^L nodes of 256 >> L lanes each
 constexpr uint32_t kMaxParams = 31;            // Rice parameters 0..30 (5-bit method); 0..14 with the 4-bit method
 constexpr uint32_t kEscape = 0x80u;            // a partition's choice: the parameter, or kEscape | raw bits
@@ -196,26 +202,35 @@ PCM_FD uint32_t choose_param(uint32_t bits, uint32_t cnt, uint32_t maxU, Sum sum
     }
     const uint32_t raw = bit_length(maxU);
     const uint64_t esc = (uint64_t)pb + 5u + (uint64_t)cnt * raw;
-    if (esc < best) { best = esc; bk = kEscape | raw; }
+    if (raw < 32u && esc < best) { best = esc; bk = kEscape | raw; }      // (5 bits name the width: an LPC residual of 32 bits stays Rice-coded)
     *code = bk;
     return (uint32_t)best;
 }
 
 // ---- the encode kernel's shared memory, and its phases lane by lane ------------------------------------------------------------------------
-// (the image takes the sums' place once the decisions are made)
+// (the image takes the sums' place once the decisions are made; before the first leaf they hold the windowed samples, then the
+// workspace of the lane that designs the LPC candidates, whose lags arrive through maxU)
 struct Work {
     int32_t  codes[kMaxFrame];
-    uint32_t sums[kMaxParams * kThreads];        // [k][lane]; later the image: slot_words() words at most
-    uint32_t cnt[kThreads], maxU[kThreads];
-    uint32_t total[kMaxOrder + 1][kLevels];      // [order][partition order]: the residual's partitions in all
-    uint32_t rootMax[kMaxOrder + 1];
-    uint8_t  param[kMaxOrder + 1][kNodeSlots];
+    union {
+        uint32_t sums[kMaxParams * kThreads];    // [k][lane]; later the image: slot_words() words at most
+        LpcScratch lpcWork;
+    };
+    uint16_t cnt[kThreads];                      // (a lane's run, and a node's samples: 4096 at most)
+    uint32_t maxU[kThreads];
+    uint32_t total[kRows][kLevels];              // [row][partition order]: the residual's partitions in all
+    uint32_t rootMax[kRows];
+    uint8_t  param[kRows][kNodeSlots];
+    LpcPlan  lpc;
 };
+struct FixedResidual { const int32_t* s; uint32_t order; PCM_FD int32_t operator()(uint32_t i) const { return residual(s, i, order); } };
+PCM_FD LpcResidual lpc_residual(const int32_t* s, const LpcPlan& plan, uint32_t slot) { return LpcResidual{s, plan.coef[slot], plan.order[slot], plan.shift[slot]}; }
 struct OrPlain { PCM_FD void operator()(uint32_t* p, uint32_t v) const { *p |= v; } };
 struct AddPlain { PCM_FD void operator()(uint32_t* p, uint32_t v) const { *p += v; } };
 
-// phase 1 (per order): the lane's run -> its leaf of the tree
-PCM_FD void leaf(Work& w, const Shape& s, uint32_t bits, uint32_t order, uint32_t lane) {
+// phase 1 (per row): the lane's run -> its leaf of the tree; `order` warm-up samples have no residual, res(i) is sample i's
+template <class Res>
+PCM_FD void leaf_with(Work& w, const Shape& s, uint32_t bits, uint32_t order, uint32_t lane, Res res) {
     uint32_t b, e;
     lane_run(s, lane, b, e);
     if (b < order) b = order < e ? order : e;
@@ -223,16 +238,20 @@ PCM_FD void leaf(Work& w, const Shape& s, uint32_t bits, uint32_t order, uint32_
     uint32_t u[16], m = 0;
     const uint32_t c = e - b;
 #pragma unroll
-    for (uint32_t j = 0; j < 16u; ++j) { u[j] = b + j < e ? zigzag(residual(w.codes, b + j, order)) : 0u; m = u[j] > m ? u[j] : m; }
+    for (uint32_t j = 0; j < 16u; ++j) { u[j] = b + j < e ? zigzag(res(b + j)) : 0u; m = u[j] > m ? u[j] : m; }
     for (uint32_t k = 0; k < K; ++k) {
         uint32_t sum = 0;
 #pragma unroll
         for (uint32_t j = 0; j < 16u; ++j) sum = sat_add(sum, u[j] >> k);
         w.sums[k * kThreads + lane] = sum;
     }
-    w.cnt[lane] = c; w.maxU[lane] = m;
+    w.cnt[lane] = (uint16_t)c; w.maxU[lane] = m;
 }
-// phase 2 (per order, L = 8 .. 0, a barrier between levels): lane j < 2^L merges node j's halves and, where the level is a partition
+PCM_FD void leaf(Work& w, const Shape& s, uint32_t bits, uint32_t order, uint32_t lane) { leaf_with(w, s, bits, order, lane, FixedResidual{w.codes, order}); }
+PCM_FD void leaf_lpc(Work& w, const Shape& s, uint32_t bits, uint32_t slot, uint32_t lane) {
+    leaf_with(w, s, bits, w.lpc.order[slot], lane, lpc_residual(w.codes, w.lpc, slot));
+}
+// phase 2 (per row — a FIXED order, or lpc_row(slot) —, L = 8 .. 0, a barrier between levels): lane j < 2^L merges node j's halves and, where the level is a partition
 // order, prices the partition
 template <class Add>
 PCM_FD void tree_level(Work& w, const Shape& s, uint32_t bits, uint32_t order, uint32_t L, uint32_t lane, Add add) {
@@ -241,7 +260,7 @@ PCM_FD void tree_level(Work& w, const Shape& s, uint32_t bits, uint32_t order, u
     if (L < 8u) {
         const uint32_t half = at + (kThreads >> (L + 1u));
         for (uint32_t k = 0; k < K; ++k) w.sums[k * kThreads + at] = sat_add(w.sums[k * kThreads + at], w.sums[k * kThreads + half]);
-        w.cnt[at] += w.cnt[half];
+        w.cnt[at] = (uint16_t)(w.cnt[at] + w.cnt[half]);
         w.maxU[at] = w.maxU[at] > w.maxU[half] ? w.maxU[at] : w.maxU[half];
     }
     if (L == 0u) w.rootMax[order] = w.maxU[0];
@@ -254,10 +273,12 @@ PCM_FD void tree_level(Work& w, const Shape& s, uint32_t bits, uint32_t order, u
 }
 
 // ---- the decision ------------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t CONSTANT = 0, VERBATIM = 1, FIXED = 2;
-struct Decision { uint32_t kind, order, porder, bits; };
-// total[order][p]: the partitions' bits at partition order p; rootMax[1] == 0: every sample equals its predecessor
-PCM_FD Decision decide(const Shape& s, uint32_t bps, const uint32_t (*total)[kLevels], const uint32_t* rootMax) {
+constexpr uint32_t CONSTANT = 0, VERBATIM = 1, FIXED = 2, LPC = 3;
+struct Decision { uint32_t kind, order, porder, bits, slot = 0u; };      // slot: which priced LPC order (kind == LPC)
+PCM_FD uint32_t decision_row(const Decision& d) { return d.kind == LPC ? lpc_row(d.slot) : d.order; }
+// total[row][p]: the partitions' bits at partition order p; rootMax[1] == 0: every sample equals its predecessor. `lpc`: the priced LPC
+// orders whose rows are filled (null: none); one that was dropped, or whose residual left int32 (rootMax == kLpcOverflow), is no candidate.
+PCM_FD Decision decide(const Shape& s, uint32_t bps, const uint32_t (*total)[kLevels], const uint32_t* rootMax, const LpcPlan* lpc = nullptr) {
     const bool constant = s.n == 1u || rootMax[1] == 0u;
     // a constant block is CONSTANT. (Only for digital silence is there a shorter form, by one bit: FIXED 0 with a zero-width escape
     // partition. A silent frame is header + G (8 + bps) bits + CRC all the same: every reader knows that form.)
@@ -268,6 +289,14 @@ PCM_FD Decision decide(const Shape& s, uint32_t bps, const uint32_t (*total)[kLe
         for (uint32_t p = 1; p <= s.pmax; ++p) if (total[o][p] < rb) { rb = total[o][p]; bp = p; }
         const uint64_t all = 8ull + (uint64_t)bps * o + 6u + rb;
         if (all < d.bits) d = Decision{FIXED, o, bp, (uint32_t)all};
+    }
+    for (uint32_t i = 0; lpc && i < lpc->count; ++i) {
+        const uint32_t row = lpc_row(i);
+        if (lpc->drop[i] != LPC_OK || rootMax[row] == kLpcOverflow) continue;
+        uint32_t rb = total[row][0], bp = 0;
+        for (uint32_t p = 1; p <= s.pmax; ++p) if (total[row][p] < rb) { rb = total[row][p]; bp = p; }
+        const uint64_t all = (uint64_t)lpc_base(bps, lpc->order[i], lpc->precision) + rb;
+        if (all < d.bits) d = Decision{LPC, lpc->order[i], bp, (uint32_t)all, i};
     }
     return d;
 }
@@ -298,46 +327,44 @@ PCM_FD void put_bits(uint32_t* image, uint32_t pos, uint32_t nb, uint32_t v, Or 
 }
 PCM_FD uint32_t sample_len(uint32_t code, uint32_t u) { return (code & kEscape) ? (code & 31u) : 1u + code + (u >> code); }
 // phase 3: the bits of the lane's run under the decision (a lane that opens a partition carries its parameter)
-PCM_FD uint32_t lane_bits(const Work& w, const Shape& s, uint32_t bits, const Decision& d, uint32_t lane) {
-    if (d.kind != FIXED) return 0u;
+template <class Res>
+PCM_FD uint32_t lane_bits_with(const Work& w, const Shape& s, uint32_t bits, const Decision& d, uint32_t lane, Res res) {
     uint32_t b, e;
     lane_run(s, lane, b, e);
     if (b < d.order) b = d.order < e ? d.order : e;
-    const uint32_t span = kThreads >> d.porder, code = w.param[d.order][node_slot(d.porder, lane / span)];
+    const uint32_t span = kThreads >> d.porder, code = w.param[decision_row(d)][node_slot(d.porder, lane / span)];
     uint32_t len = lane % span == 0u ? param_bits(bits) + ((code & kEscape) ? 5u : 0u) : 0u;
-    for (uint32_t i = b; i < e; ++i) len += sample_len(code, zigzag(residual(w.codes, i, d.order)));
+    for (uint32_t i = b; i < e; ++i) len += sample_len(code, zigzag(res(i)));
     return len;
+}
+PCM_FD uint32_t lane_bits(const Work& w, const Shape& s, uint32_t bits, const Decision& d, uint32_t lane) {
+    if (d.kind == FIXED) return lane_bits_with(w, s, bits, d, lane, FixedResidual{w.codes, d.order});
+    if (d.kind == LPC) return lane_bits_with(w, s, bits, d, lane, lpc_residual(w.codes, w.lpc, d.slot));
+    return 0u;
 }
 // what stands in front of the residual's partitions: subframe header, warm-up samples, coding method and partition order
 PCM_FD uint32_t residual_base(uint32_t bps, uint32_t order) { return 8u + bps * order + 6u; }
-// phase 4: the lane's bits into the zeroed image; `start` = the exclusive scan of lane_bits (FIXED). Lane 0 writes what stands in front.
-template <class Or>
-PCM_FD void lane_emit(const Work& w, uint32_t* image, const Shape& s, uint32_t bits, uint32_t bps, const Decision& d, uint32_t lane, uint32_t start, Or orw) {
-    if (lane == 0u) {
-        put_bits(image, 0u, 8u, d.kind == CONSTANT ? 0u : d.kind == VERBATIM ? 2u : (8u | d.order) << 1, orw);
-        if (d.kind == CONSTANT) put_bits(image, 8u, bps, (uint32_t)w.codes[0], orw);
-        if (d.kind == FIXED) {
-            for (uint32_t i = 0; i < d.order; ++i) put_bits(image, 8u + bps * i, bps, (uint32_t)w.codes[i], orw);
-            put_bits(image, 8u + bps * d.order, 6u, ((bits == 16u ? 0u : 1u) << 4) | d.porder, orw);
-        }
-    }
-    if (d.kind == CONSTANT) return;
+PCM_FD uint32_t residual_base(uint32_t bps, const Decision& d, const LpcPlan& lpc) {
+    return d.kind == LPC ? lpc_base(bps, d.order, lpc.precision) : residual_base(bps, d.order);
+}
+PCM_FD uint32_t subframe_byte(const Decision& d) {
+    return d.kind == CONSTANT ? 0u : d.kind == VERBATIM ? 2u : d.kind == FIXED ? (8u | d.order) << 1 : (0x20u | (d.order - 1u)) << 1;
+}
+// the residual's partitions of a FIXED or LPC subframe, the lane's part
+template <class Res, class Or>
+PCM_FD void lane_emit_residual(const Work& w, uint32_t* image, const Shape& s, uint32_t bits, uint32_t bps, const Decision& d, uint32_t lane, uint32_t start, Res res, Or orw) {
     uint32_t b, e;
     lane_run(s, lane, b, e);
-    if (d.kind == VERBATIM) {
-        for (uint32_t i = b; i < e; ++i) put_bits(image, 8u + bps * i, bps, (uint32_t)w.codes[i], orw);
-        return;
-    }
     if (b < d.order) b = d.order < e ? d.order : e;
-    const uint32_t span = kThreads >> d.porder, code = w.param[d.order][node_slot(d.porder, lane / span)];
-    uint32_t pos = residual_base(bps, d.order) + start;
+    const uint32_t span = kThreads >> d.porder, code = w.param[decision_row(d)][node_slot(d.porder, lane / span)];
+    uint32_t pos = residual_base(bps, d, w.lpc) + start;
     if (lane % span == 0u) {
         const uint32_t pb = param_bits(bits);
         if (code & kEscape) { put_bits(image, pos, pb, 0xFFFFFFFFu, orw); put_bits(image, pos + pb, 5u, code & 31u, orw); pos += pb + 5u; }
         else { put_bits(image, pos, pb, code, orw); pos += pb; }
     }
     for (uint32_t i = b; i < e; ++i) {
-        const int32_t r = residual(w.codes, i, d.order);
+        const int32_t r = res(i);
         const uint32_t u = zigzag(r);
         if (code & kEscape) { put_bits(image, pos, code & 31u, (uint32_t)r, orw); pos += code & 31u; continue; }
         const uint32_t q = u >> code;                   // q zeros are already there
@@ -345,6 +372,33 @@ PCM_FD void lane_emit(const Work& w, uint32_t* image, const Shape& s, uint32_t b
         put_bits(image, pos + q + 1u, code, u, orw);
         pos += q + 1u + code;
     }
+}
+// phase 4: the lane's bits into the zeroed image; `start` = the exclusive scan of lane_bits (FIXED, LPC). Lane 0 writes what stands in front.
+template <class Or>
+PCM_FD void lane_emit(const Work& w, uint32_t* image, const Shape& s, uint32_t bits, uint32_t bps, const Decision& d, uint32_t lane, uint32_t start, Or orw) {
+    if (lane == 0u) {
+        put_bits(image, 0u, 8u, subframe_byte(d), orw);
+        if (d.kind == CONSTANT) put_bits(image, 8u, bps, (uint32_t)w.codes[0], orw);
+        if (d.kind == FIXED || d.kind == LPC) {
+            uint32_t pos = 8u;
+            for (uint32_t i = 0; i < d.order; ++i, pos += bps) put_bits(image, pos, bps, (uint32_t)w.codes[i], orw);
+            if (d.kind == LPC) {
+                const uint32_t q = w.lpc.precision;
+                put_bits(image, pos, 4u, q - 1u, orw); put_bits(image, pos + 4u, 5u, w.lpc.shift[d.slot], orw); pos += 9u;
+                for (uint32_t j = 0; j < d.order; ++j, pos += q) put_bits(image, pos, q, (uint32_t)(int32_t)w.lpc.coef[d.slot][j], orw);
+            }
+            put_bits(image, pos, 6u, ((bits == 16u ? 0u : 1u) << 4) | d.porder, orw);
+        }
+    }
+    if (d.kind == CONSTANT) return;
+    if (d.kind == VERBATIM) {
+        uint32_t b, e;
+        lane_run(s, lane, b, e);
+        for (uint32_t i = b; i < e; ++i) put_bits(image, 8u + bps * i, bps, (uint32_t)w.codes[i], orw);
+        return;
+    }
+    if (d.kind == FIXED) lane_emit_residual(w, image, s, bits, bps, d, lane, start, FixedResidual{w.codes, d.order}, orw);
+    else lane_emit_residual(w, image, s, bits, bps, d, lane, start, lpc_residual(w.codes, w.lpc, d.slot), orw);
 }
 
 // ---- the assemble kernel: a frame's bytes from its header and its subframes' words ------------------------------------------------------------
@@ -399,60 +453,81 @@ struct BitWriter {
     void unary(uint32_t q) { for (; q >= 32u; q -= 32u) put(32u, 0u); put(q + 1u, 1u); }
     void align() { if (fill) put(8u - fill, 0u); }
 };
-struct SubPlan { Decision d; uint8_t param[1u << 8]; };
+struct SubPlan { Decision d; uint8_t param[1u << 8]; LpcPlan lpc; };
 struct HostScratch {            // what the twin needs besides the stack
     std::vector<uint64_t> sums = std::vector<uint64_t>(256 * kMaxParams);
-    std::vector<uint8_t> param = std::vector<uint8_t>((kMaxOrder + 1) * kNodeSlots);
+    std::vector<uint8_t> param = std::vector<uint8_t>(kRows * kNodeSlots);
     std::vector<int32_t> cand = std::vector<int32_t>(4 * kMaxFrame);
     SubPlan plans[kMaxChannels], four[4];
+    std::vector<uint32_t> windowed = std::vector<uint32_t>(kMaxFrame);
 };
-// the decision for one subframe, the way the tree makes it: per order the smallest partitions' sums, merged pairwise per partition order
-inline void plan_subframe(HostScratch& hs, const int32_t* s, uint32_t n, uint32_t bits, uint32_t bps, SubPlan& plan) {
-    const Shape sh = shape(n);
+// one row of the pricing tables the way the tree fills it: the smallest partitions' sums, merged pairwise per partition order
+template <class Res>
+inline void price_row(HostScratch& hs, const Shape& sh, uint32_t bits, uint32_t row, uint32_t warm, Res res, uint32_t (*total)[kLevels], uint32_t* rootMax) {
     const uint32_t K = param_count(bits), nb = 1u << sh.pmax;
     uint64_t* sums = hs.sums.data();
     uint32_t cnt[256], mx[256];
     uint8_t (*param)[kNodeSlots] = reinterpret_cast<uint8_t (*)[kNodeSlots]>(hs.param.data());
-    uint32_t total[kMaxOrder + 1][kLevels] = {}, rootMax[kMaxOrder + 1] = {};
-    for (uint32_t o = 0; o <= max_order(n); ++o) {
-        for (uint32_t p = 0; p < nb; ++p) {
-            uint32_t c = 0, m = 0;
-            for (uint32_t k = 0; k < K; ++k) sums[p * kMaxParams + k] = 0;
-            for (uint32_t i = p * sh.part; i < (p + 1u) * sh.part; ++i) {
-                if (i < o) continue;
-                const uint32_t u = zigzag(residual(s, i, o));
-                for (uint32_t k = 0; k < K; ++k) sums[p * kMaxParams + k] += u >> k;
-                m = u > m ? u : m; ++c;
-            }
-            cnt[p] = c; mx[p] = m;
+    for (uint32_t p = 0; p < nb; ++p) {
+        uint32_t c = 0, m = 0;
+        for (uint32_t k = 0; k < K; ++k) sums[p * kMaxParams + k] = 0;
+        for (uint32_t i = p * sh.part; i < (p + 1u) * sh.part; ++i) {
+            if (i < warm) continue;
+            const uint32_t u = zigzag(res(i));
+            for (uint32_t k = 0; k < K; ++k) sums[p * kMaxParams + k] += u >> k;
+            m = u > m ? u : m; ++c;
         }
-        for (uint32_t L = sh.pmax + 1u; L-- > 0u;) {
-            const uint32_t nodes = 1u << L, stride = nb >> L;
-            for (uint32_t j = 0; j < nodes; ++j) {
-                const uint32_t at = j * stride;
-                if (L < sh.pmax) {
-                    const uint32_t half = at + stride / 2u;
-                    for (uint32_t k = 0; k < K; ++k) sums[at * kMaxParams + k] += sums[half * kMaxParams + k];
-                    cnt[at] += cnt[half]; mx[at] = mx[at] > mx[half] ? mx[at] : mx[half];
-                }
-                uint32_t code;
-                const uint64_t* row = sums + at * kMaxParams;
-                total[o][L] += choose_param(bits, cnt[at], mx[at], [&](uint32_t k) { return row[k]; }, &code);
-                param[o][node_slot(L, j)] = (uint8_t)code;
-            }
-        }
-        rootMax[o] = mx[0];
+        cnt[p] = c; mx[p] = m;
     }
+    for (uint32_t L = sh.pmax + 1u; L-- > 0u;) {
+        const uint32_t nodes = 1u << L, stride = nb >> L;
+        for (uint32_t j = 0; j < nodes; ++j) {
+            const uint32_t at = j * stride;
+            if (L < sh.pmax) {
+                const uint32_t half = at + stride / 2u;
+                for (uint32_t k = 0; k < K; ++k) sums[at * kMaxParams + k] += sums[half * kMaxParams + k];
+                cnt[at] += cnt[half]; mx[at] = mx[at] > mx[half] ? mx[at] : mx[half];
+            }
+            uint32_t code;
+            const uint64_t* rowSums = sums + at * kMaxParams;
+            total[row][L] += choose_param(bits, cnt[at], mx[at], [&](uint32_t k) { return rowSums[k]; }, &code);
+            param[row][node_slot(L, j)] = (uint8_t)code;
+        }
+    }
+    rootMax[row] = mx[0];
+}
+// the decision for one subframe: the FIXED orders' rows, then (lpcOrder > 0) the LPC plan from the windowed samples' lags and its rows
+inline void plan_subframe(HostScratch& hs, const int32_t* s, uint32_t n, uint32_t bits, uint32_t bps, SubPlan& plan, uint32_t lpcOrder = 0u) {
+    const Shape sh = shape(n);
+    uint8_t (*param)[kNodeSlots] = reinterpret_cast<uint8_t (*)[kNodeSlots]>(hs.param.data());
+    uint32_t total[kRows][kLevels] = {}, rootMax[kRows] = {};
+    for (uint32_t o = 0; o <= max_order(n); ++o) price_row(hs, sh, bits, o, o, FixedResidual{s, o}, total, rootMax);
     if (n == 1u) rootMax[1] = 0u;
-    plan.d = decide(sh, bps, total, rootMax);
-    if (plan.d.kind == FIXED) for (uint32_t j = 0; j < (1u << plan.d.porder); ++j) plan.param[j] = param[plan.d.order][node_slot(plan.d.porder, j)];
+    if (lpcOrder > 0u) {
+        LpcScratch ws;
+        int64_t lag[kLpcLags] = {};
+        for (uint32_t i = 0; i < n; ++i) hs.windowed[i] = (uint32_t)lpc_windowed(s[i], i, n);
+        lpc_lags(hs.windowed.data(), n, lpcOrder, 0u, 1u, lag);
+        for (uint32_t k = 0; k < kLpcLags; ++k) ws.lag[k] = lag[k];
+        lpc_design(ws, lpcOrder, n, bits, plan.lpc);
+        for (uint32_t i = 0; i < plan.lpc.count; ++i)
+            if (plan.lpc.drop[i] == LPC_OK) price_row(hs, sh, bits, lpc_row(i), plan.lpc.order[i], lpc_residual(s, plan.lpc, i), total, rootMax);
+    }
+    plan.d = decide(sh, bps, total, rootMax, lpcOrder > 0u ? &plan.lpc : nullptr);
+    if (plan.d.kind == FIXED || plan.d.kind == LPC)
+        for (uint32_t j = 0; j < (1u << plan.d.porder); ++j) plan.param[j] = param[decision_row(plan.d)][node_slot(plan.d.porder, j)];
 }
 inline void write_subframe(BitWriter& bw, const int32_t* s, uint32_t n, uint32_t bits, uint32_t bps, const SubPlan& plan) {
     const Decision& d = plan.d;
-    bw.put(8u, d.kind == CONSTANT ? 0u : d.kind == VERBATIM ? 2u : (8u | d.order) << 1);
+    bw.put(8u, subframe_byte(d));
     if (d.kind == CONSTANT) { bw.put(bps, (uint32_t)s[0]); return; }
     if (d.kind == VERBATIM) { for (uint32_t i = 0; i < n; ++i) bw.put(bps, (uint32_t)s[i]); return; }
     for (uint32_t i = 0; i < d.order; ++i) bw.put(bps, (uint32_t)s[i]);
+    const LpcResidual lpc = d.kind == LPC ? lpc_residual(s, plan.lpc, d.slot) : LpcResidual{s, nullptr, 0u, 0u};
+    if (d.kind == LPC) {
+        bw.put(4u, plan.lpc.precision - 1u); bw.put(5u, plan.lpc.shift[d.slot]);
+        for (uint32_t j = 0; j < d.order; ++j) bw.put(plan.lpc.precision, (uint32_t)(int32_t)plan.lpc.coef[d.slot][j]);
+    }
     bw.put(2u, bits == 16u ? 0u : 1u); bw.put(4u, d.porder);
     const uint32_t pb = param_bits(bits), part = n >> d.porder;
     for (uint32_t j = 0; j < (1u << d.porder); ++j) {
@@ -460,7 +535,7 @@ inline void write_subframe(BitWriter& bw, const int32_t* s, uint32_t n, uint32_t
         if (code & kEscape) { bw.put(pb, 0xFFFFFFFFu >> (32u - pb)); bw.put(5u, code & 31u); } else bw.put(pb, code);
         for (uint32_t i = j * part; i < (j + 1u) * part; ++i) {
             if (i < d.order) continue;
-            const int32_t r = residual(s, i, d.order);
+            const int32_t r = d.kind == LPC ? lpc(i) : residual(s, i, d.order);
             if (code & kEscape) { bw.put(code & 31u, (uint32_t)r); continue; }
             const uint32_t u = zigzag(r);
             bw.unary(u >> code); bw.put(code, u);
@@ -469,7 +544,7 @@ inline void write_subframe(BitWriter& bw, const int32_t* s, uint32_t n, uint32_t
 }
 // One stream's frame: `chan[g]` points at the n codes of channel g. Returns the frame's bytes (0: `cap` is too small).
 inline size_t encode_frame_host(const int32_t* const* chan, uint32_t G, uint32_t n, uint32_t ff, uint32_t bits, uint32_t rate, uint32_t number,
-                                uint8_t* out, size_t cap, HostScratch& hs, uint32_t* modeOut = nullptr) {
+                                uint8_t* out, size_t cap, HostScratch& hs, uint32_t* modeOut = nullptr, uint32_t lpcOrder = 0u) {
     int32_t (*cand)[kMaxFrame] = reinterpret_cast<int32_t (*)[kMaxFrame]>(hs.cand.data());
     SubPlan* plans = hs.plans;
     const int32_t* sub[kMaxChannels];
@@ -478,7 +553,7 @@ inline size_t encode_frame_host(const int32_t* const* chan, uint32_t G, uint32_t
         SubPlan* four = hs.four;
         for (uint32_t q = 0; q < 4u; ++q) {
             for (uint32_t i = 0; i < n; ++i) cand[q][i] = candidate_sample(2u, q, chan[0][i], chan[1][i]);
-            plan_subframe(hs, cand[q], n, bits, candidate_bps(2u, bits, q), four[q]);
+            plan_subframe(hs, cand[q], n, bits, candidate_bps(2u, bits, q), four[q], lpcOrder);
         }
         mode = choose_stereo(four[0].d.bits, four[1].d.bits, four[2].d.bits, four[3].d.bits);
         for (uint32_t c = 0; c < 2u; ++c) {
@@ -486,7 +561,7 @@ inline size_t encode_frame_host(const int32_t* const* chan, uint32_t G, uint32_t
             sub[c] = cand[q]; bps[c] = candidate_bps(2u, bits, q); plans[c] = four[q];
         }
     } else {
-        for (uint32_t c = 0; c < G; ++c) { sub[c] = chan[c]; bps[c] = bits; plan_subframe(hs, chan[c], n, bits, bits, plans[c]); }
+        for (uint32_t c = 0; c < G; ++c) { sub[c] = chan[c]; bps[c] = bits; plan_subframe(hs, chan[c], n, bits, bits, plans[c], lpcOrder); }
     }
     if (modeOut) *modeOut = mode;
     uint8_t header[kMaxHeader];
@@ -507,7 +582,7 @@ inline size_t encode_frame_host(const int32_t* const* chan, uint32_t G, uint32_t
 // `flush`) the remainder as one short frame. frameBytes (may be null) receives each frame's length. Returns the bytes written, or
 // (size_t)-1 where `cap` is too small; *framesOut = frames written.
 inline size_t encode_host(const int32_t* const* planar, uint32_t G, size_t frames, uint32_t ff, uint32_t bits, uint32_t rate, uint32_t firstNumber,
-                          bool flush, uint8_t* out, size_t cap, uint32_t* frameBytes, size_t* framesOut) {
+                          bool flush, uint8_t* out, size_t cap, uint32_t* frameBytes, size_t* framesOut, uint32_t lpcOrder = 0u) {
     size_t at = 0, done = 0, count = 0;
     HostScratch hs;
     const int32_t* chan[kMaxChannels];
@@ -516,7 +591,7 @@ inline size_t encode_host(const int32_t* const* planar, uint32_t G, size_t frame
         if (left < ff && !flush) break;
         const uint32_t n = left < ff ? (uint32_t)left : ff;
         for (uint32_t g = 0; g < G; ++g) chan[g] = planar[g] + done;
-        const size_t len = encode_frame_host(chan, G, n, ff, bits, rate, firstNumber + (uint32_t)count, out + at, cap - at, hs);
+        const size_t len = encode_frame_host(chan, G, n, ff, bits, rate, firstNumber + (uint32_t)count, out + at, cap - at, hs, nullptr, lpcOrder);
         if (len == 0) return (size_t)-1;
         if (frameBytes) frameBytes[count] = (uint32_t)len;
         at += len; done += n; ++count;

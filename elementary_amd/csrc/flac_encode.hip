@@ -4,7 +4,9 @@
 // runs on the CPU lane by lane:
 //   stage     thread <-> frame of a channel row: the carried codes, then the set's floats quantised as pcm_pack quantises them
 //   encode    one workgroup per (FLAC frame, subframe candidate): exact bit counts up the partition tree, the decision, the bits
-//             ORed into a zeroed LDS image, the image's words to the candidate's slot
+//             ORed into a zeroed LDS image, the image's words to the candidate's slot. With an LPC order (flac_lpc.h) the second
+//             instantiation runs: windowed samples, the lanes' lags reduced over the workgroup, lane 0's recursion and quantisation,
+//             and the same leaf / tree passes once more per priced LPC order
 //   assemble  one workgroup per (stream, FLAC frame): stereo mode, header, subframes shift-copied, CRC-16 of lane chunks combined,
 //             16-byte stores where a piece of the stream is whole
 #include <hip/hip_runtime.h>
@@ -77,6 +79,38 @@ __device__ uint32_t block_sum(uint32_t v, uint32_t* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// The priced LPC orders' plan into w.lpc (every lane returns behind a barrier that publishes it). The windowed samples live in w.sums,
+// which is free until the first leaf; the waves' partial lags pass through w.maxU as halves, [wave][lag] low words then high words.
+__device__ void lpc_prepare(fe::Work& w, uint32_t n, uint32_t bits, uint32_t P, uint32_t lane) {
+    for (uint32_t i = lane; i < n; i += fe::kThreads) w.sums[i] = (uint32_t)fe::lpc_windowed(w.codes[i], i, n);
+    __syncthreads();
+    int64_t acc[fe::kLpcLags];
+#pragma unroll
+    for (uint32_t k = 0; k < fe::kLpcLags; ++k) acc[k] = 0;
+    fe::lpc_lags(w.sums, n, P, lane, fe::kThreads, acc);
+#pragma unroll
+    for (uint32_t k = 0; k < fe::kLpcLags; ++k) {
+        long long v = acc[k];
+#pragma unroll
+        for (uint32_t o = 32u; o > 0u; o >>= 1) v += __shfl_xor(v, (int)o);
+        if ((lane & 63u) == 0u) {
+            w.maxU[(lane >> 6) * fe::kLpcLags + k] = (uint32_t)(uint64_t)v;
+            w.maxU[(4u + (lane >> 6)) * fe::kLpcLags + k] = (uint32_t)((uint64_t)v >> 32);
+        }
+    }
+    __syncthreads();            // the windowed samples are read, the halves written: the workspace may take the samples' place
+    if (lane < fe::kLpcLags) {
+        uint64_t sum = 0;
+        for (uint32_t v = 0; v < 4u; ++v) sum += (uint64_t)w.maxU[v * fe::kLpcLags + lane] | ((uint64_t)w.maxU[(4u + v) * fe::kLpcLags + lane] << 32);
+        w.lpcWork.lag[lane] = (int64_t)sum;
+    }
+    __syncthreads();
+    if (lane == 0u) fe::lpc_design(w.lpcWork, P, n, bits, w.lpc);
+    __syncthreads();
+}
+
+// kLpc: a.lpcOrder > 0 (launch_flac_encode chooses the instantiation: without an LPC order the kernel is the one it was)
+template <bool kLpc>
 __global__ __launch_bounds__(fe::kThreads) void elemhip_flac_encode(FlacEncodeArgs a) {
     __shared__ fe::Work w;
     __shared__ uint32_t waveSum[4];
@@ -88,8 +122,8 @@ __global__ __launch_bounds__(fe::kThreads) void elemhip_flac_encode(FlacEncodeAr
         const int32_t* c1 = a.G == 2u ? c0 + a.cap : c0;
         for (uint32_t i = lane; i < n; i += fe::kThreads) w.codes[i] = fe::candidate_sample(a.G, cand, c0[i], c1[i]);
         uint32_t* tot = &w.total[0][0];
-        if (lane < (fe::kMaxOrder + 1u) * fe::kLevels) tot[lane] = 0u;
-        if (lane <= fe::kMaxOrder) w.rootMax[lane] = 0u;
+        if (lane < fe::kRows * fe::kLevels) tot[lane] = 0u;
+        if (lane < fe::kRows) w.rootMax[lane] = 0u;
     }
     __syncthreads();
     const fe::Shape sh = fe::shape(n);
@@ -101,7 +135,20 @@ __global__ __launch_bounds__(fe::kThreads) void elemhip_flac_encode(FlacEncodeAr
             __syncthreads();
         }
     }
-    const fe::Decision d = fe::decide(sh, bps, w.total, w.rootMax);
+    if (kLpc) {
+        lpc_prepare(w, n, bits, a.lpcOrder, lane);
+        for (uint32_t slot = 0; slot < w.lpc.count; ++slot) {
+            if (w.lpc.drop[slot] != fe::LPC_OK) continue;
+            fe::leaf_lpc(w, sh, bits, slot, lane);
+            __syncthreads();
+            for (uint32_t L = 9u; L-- > 0u;) {
+                fe::tree_level(w, sh, bits, fe::lpc_row(slot), L, lane, AddLds{});
+                __syncthreads();
+            }
+        }
+    }
+    const fe::Decision d = fe::decide(sh, bps, w.total, w.rootMax, kLpc ? &w.lpc : nullptr);
+    if (!kLpc && d.kind == fe::LPC) __builtin_unreachable();      // (no LPC code in the instantiation without)
     // exclusive scan of the lanes' code lengths: inside the wave by shuffles, the waves' sums through LDS
     const uint32_t len = fe::lane_bits(w, sh, bits, d, lane);
     uint32_t incl = len;
@@ -216,8 +263,11 @@ hipError_t launch_flac_encode(hipStream_t s, const FlacEncodeArgs& a) {
     if (!fe::bits_ok(a.bits) || !fe::frame_ok(a.flacFrame) || a.G == 0u || a.G > fe::kMaxChannels || a.n == 0u || a.n > a.flacFrame) return hipErrorInvalidValue;
     if (a.slotWords < fe::slot_words(a.flacFrame, a.bits) || (uint64_t)(a.numFrames - (a.numFrames ? 1u : 0u)) * a.flacFrame + a.n > a.cap) return hipErrorInvalidValue;
     if ((uint64_t)a.firstNumber + a.numFrames > 0x80000000ull || (a.n != a.flacFrame && a.numFrames > 1u)) return hipErrorInvalidValue;
+    if (!fe::lpc_order_ok(a.lpcOrder)) return hipErrorInvalidValue;
     if (a.numFrames == 0u || a.numStreams == 0u) return hipSuccess;
-    hipLaunchKernelGGL(elemhip_flac_encode, dim3(a.numFrames, a.numStreams * fe::candidates(a.G)), dim3(fe::kThreads), 0, s, a);
+    const dim3 grid(a.numFrames, a.numStreams * fe::candidates(a.G));
+    if (a.lpcOrder > 0u) hipLaunchKernelGGL(elemhip_flac_encode<true>, grid, dim3(fe::kThreads), 0, s, a);
+    else hipLaunchKernelGGL(elemhip_flac_encode<false>, grid, dim3(fe::kThreads), 0, s, a);
     hipLaunchKernelGGL(elemhip_flac_assemble, dim3(a.numFrames, a.numStreams), dim3(fe::kThreads), 0, s, a);
     return hipGetLastError();
 }

@@ -170,6 +170,7 @@ struct FlacEncodeArgs {
     uint32_t*       frameBytes;     // [numStreams][numFrames]
     uint64_t        streamStride;
     uint32_t        cap, G, numStreams, bits, flacFrame, n /* samples of every frame: flacFrame, or the flushed remainder */, numFrames, slotWords, rate, firstNumber;
+    uint32_t        lpcOrder;       // flac_lpc.h: 0 (no LPC candidates) .. 12
 };
 hipError_t launch_flac_encode(hipStream_t s, const FlacEncodeArgs& a);      // the encode kernel, then the assemble kernel
 // ---- FLAC input (flac_decode.hip): in front of the unpack kernel or the input-rate converter, flac_decode.h ----

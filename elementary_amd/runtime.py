@@ -103,6 +103,10 @@ def load_library() -> C.CDLL:
         lib.elemhip_flac_encode.argtypes = [C.POINTER(C.POINTER(C.c_int32)), C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                             C.POINTER(C.c_uint8), C.c_size_t, _szp, _u32p, C.c_size_t, _szp]
         lib.elemhip_flac_encode.restype = C.c_int
+        lib.elemhip_flac_encode_lpc.argtypes = lib.elemhip_flac_encode.argtypes + [C.c_uint32]
+        lib.elemhip_flac_encode_lpc.restype = C.c_int
+        lib.elemhip_flac_lpc_order.argtypes = [C.c_void_p, _u32p]
+        lib.elemhip_flac_lpc_order.restype = C.c_int
         _u64p = C.POINTER(C.c_uint64)
         lib.elemhip_flac_index.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p, C.c_size_t, _szp]
         lib.elemhip_flac_index.restype = C.c_int
@@ -154,10 +158,12 @@ class _FlacStreamInfo(C.Structure):
     _fields_ = [("frames", C.c_uint64), ("total_samples", C.c_uint64), ("min_frame_bytes", C.c_uint32), ("max_frame_bytes", C.c_uint32)]
 
 
-def flac_encode(codes, bits: int = 16, flac_frame: int = 4096, sample_rate: int = 44100, first_frame_number: int = 0, flush: bool = True):
+def flac_encode(codes, bits: int = 16, flac_frame: int = 4096, sample_rate: int = 44100, first_frame_number: int = 0, flush: bool = True,
+                lpc_order: int = 0):
     """``elemhip_flac_encode``: the scalar twin of the FLAC kernels, pure host arithmetic — ``codes`` int32 ``[channels, frames]`` (one
     stream) -> ``(frame bytes back to back, uint32 array of the frames' byte lengths)``. Whole frames of ``flac_frame``; with ``flush``
-    the remainder as one short final frame."""
+    the remainder as one short final frame. ``lpc_order`` (0 .. 12; ``elemhip_flac_encode_lpc``): the twin of a programme with option
+    ``flac_lpc_order``; 0 gives ``elemhip_flac_encode``'s bytes."""
     import numpy as np
     lib = load_library()
     a = np.ascontiguousarray(codes, dtype=np.int32)
@@ -170,8 +176,12 @@ def flac_encode(codes, bits: int = 16, flac_frame: int = 4096, sample_rate: int 
     lens = np.zeros(count, dtype=np.uint32)
     rows = (C.POINTER(C.c_int32) * max(1, ch))(*[a[c].ctypes.data_as(C.POINTER(C.c_int32)) for c in range(ch)])
     nbytes, nframes = C.c_size_t(0), C.c_size_t(0)
-    rc = lib.elemhip_flac_encode(rows, ch, n, int(flac_frame), int(bits), int(sample_rate), int(first_frame_number), 1 if flush else 0,
-                                 out.ctypes.data_as(C.POINTER(C.c_uint8)), cap, C.byref(nbytes), lens.ctypes.data_as(C.POINTER(C.c_uint32)), count, C.byref(nframes))
+    args = (rows, ch, n, int(flac_frame), int(bits), int(sample_rate), int(first_frame_number), 1 if flush else 0,
+            out.ctypes.data_as(C.POINTER(C.c_uint8)), cap, C.byref(nbytes), lens.ctypes.data_as(C.POINTER(C.c_uint32)), count, C.byref(nframes))
+    if int(lpc_order) != lpc_order or not 0 <= int(lpc_order) <= 0xFFFFFFFF:
+        rc = 6          # (what the C side answers to an order above 12: kInvalidPropertyValue)
+    else:
+        rc = lib.elemhip_flac_encode_lpc(*args, int(lpc_order)) if lpc_order else lib.elemhip_flac_encode(*args)
     if rc != 0:
         err = ElemHipError(f"elemhip_flac_encode failed: {describe(rc)} (code {rc})")
         err.code = rc
@@ -566,8 +576,9 @@ class Runtime(CRuntime):
 
     def flac_read(self) -> Dict[str, Any]:
         """``elemhip_flac_read``: the FLAC programme so far — ``{'flac_frame', 'bits', 'channels_per_stream', 'streams', 'sample_rate',
-        'flushed', 'frames', 'stream_frames', 'total_samples', 'min_frame_bytes', 'max_frame_bytes', 'frame_bytes'}``: the last five
-        one entry per stream (the STREAMINFO fields; ``frame_bytes`` a uint32 array of every frame's byte length)."""
+        'flushed', 'frames', 'lpc_order', 'stream_frames', 'total_samples', 'min_frame_bytes', 'max_frame_bytes', 'frame_bytes'}``: the
+        last five one entry per stream (the STREAMINFO fields; ``frame_bytes`` a uint32 array of every frame's byte length);
+        ``lpc_order`` (``elemhip_flac_lpc_order``) the programme's option ``flac_lpc_order``."""
         import numpy as np
         info = _FlacInfo()
         rc = self._lib.elemhip_flac_read(self._h, C.byref(info), None, 0, None, 0)
@@ -586,11 +597,14 @@ class Runtime(CRuntime):
             if rc != 6:
                 break
             rc = 0          # (another thread rendered in between: size the table again)
+        lpc = C.c_uint32(0)
+        if rc == 0:
+            rc = self._lib.elemhip_flac_lpc_order(self._h, C.byref(lpc))
         if rc != 0:
             err = ElemHipError(f"elemhip_flac_read failed: {describe(rc)} (code {rc})")
             err.code = rc
             raise err
-        return {"flac_frame": int(info.flac_frame), "bits": int(info.bits), "channels_per_stream": int(info.channels_per_stream), "streams": S,
+        return {"flac_frame": int(info.flac_frame), "lpc_order": int(lpc.value), "bits": int(info.bits), "channels_per_stream": int(info.channels_per_stream), "streams": S,
                 "sample_rate": int(info.sample_rate), "flushed": bool(info.flushed), "frames": int(info.frames),
                 "stream_frames": [int(per[s].frames) for s in range(S)], "total_samples": [int(per[s].total_samples) for s in range(S)],
                 "min_frame_bytes": [int(per[s].min_frame_bytes) for s in range(S)], "max_frame_bytes": [int(per[s].max_frame_bytes) for s in range(S)],
@@ -775,7 +789,9 @@ class Runtime(CRuntime):
     def set_option(self, key: str, value: float) -> None:
         rc = self._lib.elemhip_set_option(self._h, key.encode(), float(value))
         if rc != 0:
-            raise ElemHipError(f"unknown option {key!r}")
+            err = ElemHipError(f"unknown option {key!r}")
+            err.code = rc
+            raise err
 
     def time_launches(self, num_outputs: int, num_blocks: int):
         """Mean HIP-event duration (ms) of each launch level and of the epilogue kernel."""

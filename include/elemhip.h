@@ -245,6 +245,11 @@ int elemhip_limiter_reset(elemhip_t*);
  * Subframes are CONSTANT, VERBATIM or FIXED of order 0 .. 4 with partitioned Rice residuals (escape partitions allowed), two-channel
  * streams choose per frame among independent, left/side, side/right and mid/side; every choice is made on exact bit counts, so no
  * subframe is longer than its VERBATIM form, and the bytes are the same on the GPU and in elemhip_flac_encode.
+ * Option "flac_lpc_order" = P (integral, 0 .. 12; 0, the default: off, and then not one byte differs) adds LPC subframes: per subframe
+ * the orders P and ceil(P / 2) (those below the block's samples) are priced to the bit next to the FIXED ones, from a Welch-windowed
+ * integer autocorrelation and a Levinson-Durbin recursion whose arithmetic the kernel and elemhip_flac_encode_lpc share
+ * (elementary_amd/csrc/flac_lpc.h); ties go to the simpler kind, LPC last. Like "flac_frame" the programme keeps the order it started
+ * with: another value is refused (code 6) until elemhip_flac_reset; values that are not integral or outside 0 .. 12 are refused too.
  * The programme is the frames these calls delivered since creation or elemhip_flac_reset, in call order; FLAC frame j holds programme
  * frames [j F, (j + 1) F). A call returns the bytes of the FLAC frames it completed (bytesOut[s], possibly 0) and leaves the open
  * frame's codes on the device, so the bytes of a render do not depend on how it is cut into calls, relay windows or launch sets.
@@ -264,6 +269,8 @@ int elemhip_limiter_reset(elemhip_t*);
  *   elemhip_flac_encode  pure host arithmetic, no handle: planar int32 codes of one stream -> its frames, the scalar twin of the
  *                        kernels (whole frames; with `flush` the remainder as a short frame). Code 103 when `capacity` is too small,
  *                        6 for a code outside the sample size or a frame number above 2^31 - 1.
+ *   elemhip_flac_encode_lpc  the same with an LPC order (0 .. 12, else code 6): the twin of a programme with option "flac_lpc_order"
+ *   elemhip_flac_lpc_order   the open programme's LPC order, or the option's where none is open
  * A stream needs "fLaC" and a STREAMINFO block in front (elementary_amd/flac.py writes them); its MD5 is left zero — "not computed":
  * the unencoded samples never reach the host. */
 typedef struct elemhip_flac_spec { uint32_t bits /* 16, 24; 0: option "flac_bits" */, channels_per_stream, dither /*0 none, 1 TPDF*/, seed;
@@ -280,6 +287,10 @@ int elemhip_flac_reset(elemhip_t*);
 int elemhip_flac_encode(const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t flacFrame, uint32_t bits, uint32_t sampleRate,
                         uint32_t firstFrameNumber, int flush, uint8_t* out, size_t capacity, size_t* bytesOut, uint32_t* frameBytes, size_t frameCap,
                         size_t* framesOut);
+int elemhip_flac_encode_lpc(const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t flacFrame, uint32_t bits, uint32_t sampleRate,
+                            uint32_t firstFrameNumber, int flush, uint8_t* out, size_t capacity, size_t* bytesOut, uint32_t* frameBytes, size_t frameCap,
+                            size_t* framesOut, uint32_t lpcOrder);
+int elemhip_flac_lpc_order(elemhip_t*, uint32_t* order);
 
 /* EXTENSION (no counterpart in the reference): the same render FED with FLAC, decoded on the GPU in front of the unpack kernel (or
  * the input-rate converter) of every launch set (elementary_amd/csrc/flac_decode.hip; the arithmetic: flac_decode.h). Input format

@@ -187,6 +187,14 @@ public:
         return elemhip_flac_encode(planar, channels, frames, flacFrame, bits, sampleRate, firstFrameNumber, flush ? 1 : 0, out, capacity, bytesOut, frameBytes,
                                    frameCap, framesOut);
     }
+    // ... with LPC subframes (setOption("flac_lpc_order", P), 0 .. 12): the twin of such a programme, and the order in force
+    static int flacEncodeLpc(const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t flacFrame, uint32_t bits, uint32_t sampleRate,
+                             uint32_t firstFrameNumber, bool flush, uint8_t* out, size_t capacity, size_t* bytesOut, uint32_t lpcOrder,
+                             uint32_t* frameBytes = nullptr, size_t frameCap = 0, size_t* framesOut = nullptr) {
+        return elemhip_flac_encode_lpc(planar, channels, frames, flacFrame, bits, sampleRate, firstFrameNumber, flush ? 1 : 0, out, capacity, bytesOut,
+                                       frameBytes, frameCap, framesOut, lpcOrder);
+    }
+    int flacLpcOrder(uint32_t* order) { return elemhip_flac_lpc_order(h, order); }
     static int loudnessGate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
         return elemhip_loudness_gate(meanSquares, channels, subBlocks, weights, out);
     }

@@ -5,20 +5,63 @@ synchronised); the medians are compared. Reported besides: the bytes that crosse
 FLAC: the frames and their length table) and the compression ratio on the probe's programme.
 
 `--flac-only` renders a few FLAC sets and nothing else: the run for a kernel trace of its own (rocprofv3 --kernel-trace --stats),
-where elemhip_flac_stage, elemhip_flac_encode and elemhip_flac_assemble show their own times."""
+where elemhip_flac_stage, elemhip_flac_encode and elemhip_flac_assemble show their own times.
+
+`--lpc-order P` (1 .. 12) compares FLAC delivery with option flac_lpc_order = P against FLAC delivery without (order 0) instead: two
+engines that render the same programme, the legs alternating in the same way, set time and bytes of one relative to the other. With
+`--flac-only` only the engine with the order renders."""
 import sys, time; sys.path.insert(0, '.')
 from elementary_amd import graphs
 from elementary_amd.runtime import Runtime
 
 flac_only = "--flac-only" in sys.argv
+lpc_order = int(sys.argv[sys.argv.index("--lpc-order") + 1]) if "--lpc-order" in sys.argv else 0
 ROUNDS = 5
 
 
-def workload(name, roots, S, G, batch, sets, flac_frame):
+def engine(roots, n_out, batch, flac_frame, order):
     rt = Runtime(48000.0, 512, device=0); rt.set_option("specialize", 2); rt.set_option("batch_blocks", batch); rt.set_option("flac_frame", flac_frame)
+    if order:
+        rt.set_option("flac_lpc_order", order)
     assert rt.render(*roots)["result"] == 0
-    n_out, frames = S * G, sets * batch * 512
     rt.process_blocks_host(None, n_out, 64 * 512)                # root fades settle: launch sets from here on
+    return rt
+
+
+def lpc_workload(name, roots, S, G, batch, sets, flac_frame):
+    n_out, frames = S * G, sets * batch * 512
+    legs = {f"lpc{lpc_order}": engine(roots, n_out, batch, flac_frame, lpc_order)}
+    if not flac_only:
+        legs["lpc0"] = engine(roots, n_out, batch, flac_frame, 0)
+
+    def flac(rt):
+        streams, _ = rt.process_blocks_flac(None, S, G, frames, 16)
+        return sum(len(b) for b in streams)
+
+    for rt in legs.values():
+        flac(rt)                                                 # warm-up (and the buffers' allocation)
+    if flac_only:
+        flac(legs[f"lpc{lpc_order}"])
+        return
+    t = {k: [] for k in legs}
+    nbytes = {k: 0 for k in legs}
+    for _ in range(ROUNDS):
+        for label in ("lpc0", f"lpc{lpc_order}"):
+            t0 = time.perf_counter(); nbytes[label] += flac(legs[label]); t[label].append(time.perf_counter() - t0)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    for label in ("lpc0", f"lpc{lpc_order}"):
+        print(f"{name} flac_frame {flac_frame} {label:6s} ms/set {' '.join(f'{1e3 * x / sets:8.2f}' for x in t[label])}   median {1e3 * med[label] / sets:8.2f}"
+              f"   frame bytes over {ROUNDS} calls {nbytes[label]}", flush=True)
+    a, b = f"lpc{lpc_order}", "lpc0"
+    print(f"{name} flac_frame {flac_frame} median {a} / {b} {med[a] / med[b]:5.3f}   bytes {a} / {b} {nbytes[a] / nbytes[b]:5.3f}"
+          f"   {a} / s16 {nbytes[a] / (2.0 * n_out * frames * ROUNDS):5.3f}", flush=True)
+
+
+def workload(name, roots, S, G, batch, sets, flac_frame):
+    if lpc_order:
+        return lpc_workload(name, roots, S, G, batch, sets, flac_frame)
+    n_out, frames = S * G, sets * batch * 512
+    rt = engine(roots, n_out, batch, flac_frame, 0)
 
     def pcm():
         streams, _, _ = rt.process_blocks_pcm(None, S, G, frames, "s16")
