@@ -445,7 +445,6 @@ private:
     int ensureHostStaging(size_t outFloats, size_t inFloats);
     // PCM delivery (processBlocksPcm): packed halves behind the float ones (streams, then the set's per-channel statistics), and
     // the pack kernel's row table for the group size in use
-    struct PcmJob;
     unsigned char* hPcm[2] = {nullptr, nullptr}; unsigned char* dPcm[2] = {nullptr, nullptr};
     size_t pcmBytes = 0;
     uint16_t* dPcmRowBase = nullptr; uint32_t pcmTableGroup = 0, pcmRowDwords = 0;
@@ -517,14 +516,33 @@ private:
     int ensureLimiter(size_t channels, size_t outBlocksCap, size_t setFrames);   // (`mu` held, both streams idle)
     int limiterResetLocked(size_t channels);
     void limiterFree();
-    int growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], size_t& have, size_t want);
+    template <class T> int growHalves(T* (&h)[2], T* (&d)[2], size_t& have, size_t want);      // (engine_render.cpp: float and unsigned char)
+    int growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], size_t& have, size_t want) { return growHalves(h, d, have, want); }
     int ensureRowTable(uint16_t*& dev, uint32_t& haveGroup, uint32_t& dwords, uint32_t group);
+    // what a packed delivery counts per channel, summed over the call (peakBits: pcm_pack.h)
+    struct ChannelTally {
+        std::vector<uint32_t> peakBits; std::vector<uint64_t> over, nonfinite;
+        void init(size_t n) { peakBits.assign(n, 0u); over.assign(n, 0u); nonfinite.assign(n, 0u); }
+        void writeTo(PcmChannelStats* stats) const {      // (null: nobody asked)
+            for (size_t c = 0; stats && c < peakBits.size(); ++c) {
+                std::memcpy(&stats[c].peak, &peakBits[c], 4);
+                stats[c].reserved = 0u; stats[c].over = over[c]; stats[c].nonfinite = nonfinite[c];
+            }
+        }
+    };
+    // what a processBlocksPcm call carries through the render
+    struct PcmJob {
+        PcmSpec spec;
+        void* const* streams; size_t nStreams;
+        ChannelTally tally;
+        uint32_t validOf[2] = {0, 0};           // delivered frames of the set in each half
+    };
     // FLAC delivery: the open frame's codes, the set's codes, the candidates' subframes and their bit counts on the device; the frames
     // and their length table go through the packed halves (hPcm / dPcm), the payload copied on a stream of its own once the table is here
     struct FlacJob {
         FlacSpec spec;
         void* const* streams; const size_t* caps; size_t* bytes; size_t nStreams;
-        std::vector<uint32_t> peakBits; std::vector<uint64_t> over, nonfinite;
+        ChannelTally tally;
         uint32_t framesOf[2] = {0, 0};          // FLAC frames of the set in each half
         uint64_t dropLeft = 0, takeLeft = 0;    // of the call's delivered frames still to come
         size_t statsOff = 0, payloadOff = 0, stride = 0;
@@ -567,9 +585,32 @@ private:
     bool flacInFailed(int half);                // the set's error record has arrived: anything in it -> the last error
     int flacInHostImage(const PcmSource& src, uint64_t from, size_t n, std::vector<std::vector<unsigned char>>& images);
     void flacInFree();
-    // the set loop of processBlocksHost / processBlocksPcm (`pcm` null: planar floats only)
+    // A host-buffer render call: its arguments (`pcm` null: planar floats only; `out` may be null with `pcm` or `flac`: nobody asked for
+    // the floats; with `src` the nIn input channels come from its streams and `in` is null) and what both renderers derive from them and
+    // from the options, computed once by hostCall().
+    struct HostCall {
+        const float* const* in; size_t nIn; float* const* out; size_t nOut; size_t numFrames; int64_t sampleTime;
+        PcmJob* pcm; const PcmSource* src; FlacJob* flac;
+        size_t bs, hb;                                  // the engine's block, the host's
+        bool flacSrc; uint32_t flacInB;                 // a FLAC source, its bits
+        uint32_t srcG, srcFmt; size_t srcB;             // the source's group, format (a FLAC source: its image's) and sample bytes
+        bool wantFloat;
+        uint32_t pcmG, pcmFmt; size_t pcmB;
+        bool packed;                                    // PCM or FLAC delivery
+        bool meter, resamp, limit, inres;               // options "loudness_meter", "resample_rate", "limiter", "input_rate" apply to this call
+        resample::Plan rp, inp; limiter::Plan lmp;
+        uint32_t inG, inFmt; size_t inStreams, inB;     // the inputs as streams: planar floats count as nIn one-channel float streams
+        const unsigned char* inStream(size_t s) const { return src ? static_cast<const unsigned char*>(src->streams[s]) : reinterpret_cast<const unsigned char*>(in[s]); }
+    };
+    HostCall hostCall(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
+                      const PcmSource* src, FlacJob* flac) const;
+    // processBlocksHost / Pcm / PcmIo / Flac: decides between the two renderers — taps under a host block longer than the engine's and
+    // ragged slices go host block by host block through process() (renderHostBlocks, engine_host_blocks.cpp); everything else through
+    // the launch-set loop, which is the rest of this function (engine_render.cpp)
     int renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
-                       const PcmSource* src = nullptr, FlacJob* flac = nullptr);      // `src`: the inputs as PCM streams (`in` is null then)
+                       const PcmSource* src = nullptr, FlacJob* flac = nullptr);
+    struct HostCarry;                                   // (engine_host_blocks.cpp: the stages' carried state on the host for a call)
+    int renderHostBlocks(const HostCall& c);
     // enqueue `numBlocks` blocks on `stream` (no synchronise at the end): the body of processBlocks
     int enqueueBlocks(const float* inDev, size_t nIn, float* outDev, size_t nOut, size_t numBlocks, int64_t sampleTime);
 

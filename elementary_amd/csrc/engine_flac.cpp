@@ -84,8 +84,8 @@ int Engine::flacDeliver(FlacJob& job, int half) {
     const unsigned char* h = hPcm[half];
     const pcm_pack::ChannelStats* st = reinterpret_cast<const pcm_pack::ChannelStats*>(h + job.statsOff);
     for (size_t c = 0; c < nOut; ++c) {
-        job.peakBits[c] = std::max(job.peakBits[c], st[c].peakBits);
-        job.over[c] += st[c].over; job.nonfinite[c] += st[c].nonfinite;
+        job.tally.peakBits[c] = std::max(job.tally.peakBits[c], st[c].peakBits);
+        job.tally.over[c] += st[c].over; job.tally.nonfinite[c] += st[c].nonfinite;
     }
     const uint32_t nF = job.framesOf[half];
     if (nF == 0) return kOk;
@@ -140,15 +140,11 @@ int Engine::processBlocksFlac(const PcmSource& src, void* const* outStreams, con
     const size_t nIn = src.nStreams * src.channelsPerStream, nOut = nOutStreams * spec.channelsPerStream;
     FlacJob job;
     job.spec = spec; job.streams = outStreams; job.caps = capacities; job.bytes = bytesOut; job.nStreams = nOutStreams;
-    job.peakBits.assign(nOut, 0u); job.over.assign(nOut, 0u); job.nonfinite.assign(nOut, 0u);
+    job.tally.init(nOut);
     job.dropLeft = spec.drop; job.takeLeft = spec.take;
     const int rc = renderHostSets(nullptr, nIn, nullptr, nOut, numFrames, sampleTime, nullptr, src.nStreams ? &src : nullptr, &job);
     if (rc != kOk) { RenderGuard lock(*this); (void)flacResetLocked(); }       // (the carried codes may be ahead of what was delivered)
-    if (stats)
-        for (size_t c = 0; c < nOut; ++c) {
-            std::memcpy(&stats[c].peak, &job.peakBits[c], 4);
-            stats[c].reserved = 0u; stats[c].over = job.over[c]; stats[c].nonfinite = job.nonfinite[c];
-        }
+    job.tally.writeTo(stats);
     return rc;
 }
 

@@ -1,6 +1,6 @@
 // engine_flac_in.cpp — the host side of FLAC input (input format 4; flac_decode.h, flac_decode.hip): the checks of a FLAC source, the
 // per-set lookup of the covering frames by binary search, the staging halves, the launch, the error record's way back and the host
-// decode of the block-by-block path. The set loop that stages, copies and launches is renderHostSets (engine_render.cpp).
+// decode of the block-by-block path (engine_host_blocks.cpp). The set loop that stages, copies and launches is renderHostSets (engine_render.cpp).
 #include "engine_impl.h"
 
 namespace elemhip {

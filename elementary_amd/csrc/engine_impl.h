@@ -1,5 +1,5 @@
 // engine_impl.h — what more than one of the engine's translation units needs (engine.cpp, engine_nodes.cpp, engine_relay.cpp,
-// engine_render.cpp) and no one else does: included by those files only.
+// engine_render.cpp, engine_host_blocks.cpp) and no one else does: included by those files only.
 #pragma once
 #include "engine.h"
 

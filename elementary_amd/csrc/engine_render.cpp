@@ -1,7 +1,7 @@
 // engine_render.cpp — the per-block launch sequence (process), launch sets (processBlocks / processBlocksHost), the resident
-// kernel's host side and the measurement calls. Everything a render call reaches lives in this unit or inline in engine.h.
+// kernel's host side and the measurement calls. Everything a render call reaches lives in this unit or inline in engine.h, but for the
+// block-by-block host render (engine_host_blocks.cpp).
 #include "engine_impl.h"
-#include "pcm_unpack.h"
 #include "flac_encode.h"
 #include <functional>
 #include <thread>
@@ -1119,31 +1119,8 @@ int Engine::ensureHostStaging(size_t outFloats, size_t inFloats) {
             HIP_OK(hipEventCreateWithFlags(&evOut[k], hipEventDisableTiming));
         }
     }
-    auto grow = [&](float* (&h)[2], float* (&d)[2], size_t& have, size_t want) -> int {
-        if (want <= have) return kOk;
-        HIP_OK(hipStreamSynchronize(stream));
-        HIP_OK(hipStreamSynchronize(ioStream));
-        // the new buffers first: a failed allocation leaves the old pair (and `have`) as they were
-        float* nh[2] = {nullptr, nullptr}; float* nd[2] = {nullptr, nullptr};
-        bool ok = true;
-        for (int k = 0; k < 2 && ok; ++k)
-            ok = hipHostMalloc((void**)&nh[k], want * sizeof(float), hipHostMallocDefault) == hipSuccess && hipMalloc(&nd[k], want * sizeof(float)) == hipSuccess;
-        if (!ok) {
-            for (int k = 0; k < 2; ++k) { if (nh[k]) (void)hipHostFree(nh[k]); if (nd[k]) (void)hipFree(nd[k]); }
-            (void)hipGetLastError();
-            return kHipError;
-        }
-        for (int k = 0; k < 2; ++k) {
-            if (h[k]) (void)hipHostFree(h[k]);
-            if (d[k]) (void)hipFree(d[k]);
-            h[k] = nh[k]; d[k] = nd[k];
-        }
-        have = want;
-        return kOk;
-    };
-    int rc = grow(hStageOut, dStageOut, stageOutFloats, outFloats);
-    if (rc != kOk) return rc;
-    return grow(hStageIn, dStageIn, stageInFloats, inFloats);
+    const int rc = growHalves(hStageOut, dStageOut, stageOutFloats, outFloats);
+    return rc != kOk ? rc : growHalves(hStageIn, dStageIn, stageInFloats, inFloats);
 }
 
 int Engine::ensureRowTable(uint16_t*& dev, uint32_t& haveGroup, uint32_t& dwords, uint32_t group) {
@@ -1158,15 +1135,16 @@ int Engine::ensureRowTable(uint16_t*& dev, uint32_t& haveGroup, uint32_t& dwords
     return kOk;
 }
 
-int Engine::growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], size_t& have, size_t want) {
+// a pinned and a device pair of staging halves, grown to `want` T's (the float halves, and the packed ones through growPackedHalves)
+template <class T> int Engine::growHalves(T* (&h)[2], T* (&d)[2], size_t& have, size_t want) {
     if (want <= have) return kOk;
     HIP_OK(hipStreamSynchronize(stream));
     if (ioStream) HIP_OK(hipStreamSynchronize(ioStream));
     // the new buffers first: a failed allocation leaves the old pair (and `have`) as they were
-    unsigned char* nh[2] = {nullptr, nullptr}; unsigned char* nd[2] = {nullptr, nullptr};
+    T* nh[2] = {nullptr, nullptr}; T* nd[2] = {nullptr, nullptr};
     bool ok = true;
     for (int k = 0; k < 2 && ok; ++k)
-        ok = hipHostMalloc((void**)&nh[k], want, hipHostMallocDefault) == hipSuccess && hipMalloc((void**)&nd[k], want) == hipSuccess;
+        ok = hipHostMalloc((void**)&nh[k], want * sizeof(T), hipHostMallocDefault) == hipSuccess && hipMalloc((void**)&nd[k], want * sizeof(T)) == hipSuccess;
     if (!ok) {
         for (int k = 0; k < 2; ++k) { if (nh[k]) (void)hipHostFree(nh[k]); if (nd[k]) (void)hipFree(nd[k]); }
         (void)hipGetLastError();
@@ -1180,6 +1158,8 @@ int Engine::growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], siz
     have = want;
     return kOk;
 }
+template int Engine::growHalves(float* (&)[2], float* (&)[2], size_t&, size_t);
+template int Engine::growHalves(unsigned char* (&)[2], unsigned char* (&)[2], size_t&, size_t);
 
 int Engine::ensurePcmStaging(size_t bytes, uint32_t group) {
     const int rc = ensureRowTable(dPcmRowBase, pcmTableGroup, pcmRowDwords, group);
@@ -1190,14 +1170,6 @@ int Engine::ensurePcmInStaging(size_t bytes, uint32_t group) {
     const int rc = ensureRowTable(dPcmInRowBase, pcmInTableGroup, pcmInRowDwords, group);
     return rc != kOk ? rc : growPackedHalves(hPcmIn, dPcmIn, pcmInBytes, bytes);
 }
-
-// what a processBlocksPcm call carries through the set loop
-struct Engine::PcmJob {
-    PcmSpec spec;
-    void* const* streams; size_t nStreams;
-    std::vector<uint32_t> peakBits; std::vector<uint64_t> over, nonfinite;      // per channel, summed over the sets
-    uint32_t validOf[2] = {0, 0};                                                // delivered frames of the set in each half
-};
 
 // Runtime::process for a whole offline render (offline-renderer/index.ts:87-133): planar host arrays of `numFrames` frames.
 // Set k (up to `batch_blocks` blocks) is gathered into pinned half k % 2, copied in on the copy stream, rendered on the
@@ -1218,13 +1190,9 @@ int Engine::processBlocksPcm(const float* const* in, size_t nIn, void* const* st
     const size_t nOut = nStreams * spec.channelsPerStream;
     PcmJob job;
     job.spec = spec; job.streams = streams; job.nStreams = nStreams;
-    job.peakBits.assign(nOut, 0u); job.over.assign(nOut, 0u); job.nonfinite.assign(nOut, 0u);
+    job.tally.init(nOut);
     const int rc = nOut ? renderHostSets(in, nIn, planar, nOut, numFrames, sampleTime, &job) : kOk;
-    if (stats)
-        for (size_t c = 0; c < nOut; ++c) {
-            std::memcpy(&stats[c].peak, &job.peakBits[c], 4);
-            stats[c].reserved = 0u; stats[c].over = job.over[c]; stats[c].nonfinite = job.nonfinite[c];
-        }
+    job.tally.writeTo(stats);
     return rc;
 }
 
@@ -1245,266 +1213,62 @@ int Engine::processBlocksPcmIo(const PcmSource& src, void* const* outStreams, si
     const size_t nOut = nOutStreams * outSpec->channelsPerStream;
     PcmJob job;
     job.spec = *outSpec; job.streams = outStreams; job.nStreams = nOutStreams;
-    job.peakBits.assign(nOut, 0u); job.over.assign(nOut, 0u); job.nonfinite.assign(nOut, 0u);
+    job.tally.init(nOut);
     const int rc = nOut ? renderHostSets(nullptr, nIn, planar, nOut, numFrames, sampleTime, &job, from) : kOk;
-    if (stats)
-        for (size_t c = 0; c < nOut; ++c) {
-            std::memcpy(&stats[c].peak, &job.peakBits[c], 4);
-            stats[c].reserved = 0u; stats[c].over = job.over[c]; stats[c].nonfinite = job.nonfinite[c];
-        }
+    job.tally.writeTo(stats);
     return rc;
 }
 
-// (`out` may be null with `pcm`: nobody asked for the planar floats; with `src` the nIn input channels come from its streams, `in` is null)
-int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
-                           const PcmSource* src, FlacJob* flac) {
-    const size_t bs = (size_t)blockSize;
+// what both renderers of a host-buffer call read: the arguments and everything derived from them and from the options, computed once
+Engine::HostCall Engine::hostCall(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
+                                  const PcmSource* src, FlacJob* flac) const {
+    HostCall c{};
+    c.in = in; c.nIn = nIn; c.out = out; c.nOut = nOut; c.numFrames = numFrames; c.sampleTime = sampleTime; c.pcm = pcm; c.src = src; c.flac = flac;
+    c.bs = (size_t)blockSize;
+    c.hb = (size_t)hostBlockSize;       // whole HOST blocks, like the reference's block loop (a host block = hostBlockSize / blockSize engine blocks)
     // a FLAC source (engine_flac_in.cpp) is decoded into the packed input half as the s16 / s24 stream of the same samples: from there
     // on it IS that PCM source
-    const bool flacSrc = src && src->format == flac_decode::kFormat;
-    const uint32_t flacInB = flacSrc ? flacInBits(*src) : 0u;
-    const uint32_t srcG = src ? src->channelsPerStream : 1u, srcFmt = flacSrc ? flac_decode::image_format(flacInB) : src ? src->format : 0u;
-    const size_t srcB = src ? pcm_pack::sample_bytes(srcFmt) : 0;
-    const bool wantFloat = nOut > 0 && out != nullptr;
-    const uint32_t pcmG = pcm ? pcm->spec.channelsPerStream : 1u, pcmFmt = pcm ? pcm->spec.format : 0u;
-    const size_t pcmB = pcm ? pcm_pack::sample_bytes(pcmFmt) : 0;
-    const bool packed = pcm || flac;                 // (FLAC delivery stands where PCM delivery stands: nobody asked for the floats)
-    const bool meter = loudnessOn && nOut > 0;       // option "loudness_meter": the delivered frames of every set go through the meter
+    c.flacSrc = src && src->format == flac_decode::kFormat;
+    c.flacInB = c.flacSrc ? flacInBits(*src) : 0u;
+    c.srcG = src ? src->channelsPerStream : 1u; c.srcFmt = c.flacSrc ? flac_decode::image_format(c.flacInB) : src ? src->format : 0u;
+    c.srcB = src ? pcm_pack::sample_bytes(c.srcFmt) : 0;
+    c.wantFloat = nOut > 0 && out != nullptr;
+    c.pcmG = pcm ? pcm->spec.channelsPerStream : 1u; c.pcmFmt = pcm ? pcm->spec.format : 0u;
+    c.pcmB = pcm ? pcm_pack::sample_bytes(c.pcmFmt) : 0;
+    c.packed = pcm || flac;                 // (FLAC delivery stands where PCM delivery stands: nobody asked for the floats)
+    c.meter = loudnessOn && nOut > 0;       // option "loudness_meter": the delivered frames of every set go through the meter
     // option "resample_rate": what is delivered — floats, packed streams, the meter's frames — is the render converted to the delivery
     // rate; the pack kernel's time (the dither's key) is then the programme's OUTPUT frame index
-    const bool resamp = resampleOn && nOut > 0;
-    const resample::Plan rp = resPlan;
+    c.resamp = resampleOn && nOut > 0;
+    c.rp = resPlan;
     // option "limiter": the delivered frames — converted or not — go through the gain and the limiter before they are packed, metered
     // and copied; frames in = frames out, so neither the dither's key nor any count changes
-    const bool limit = limiterOn && nOut > 0;
-    const limiter::Plan lmp = limPlan;
+    c.limit = limiterOn && nOut > 0;
+    c.lmp = limPlan;
     // option "input_rate": the inputs — planar floats or streams — arrive at another rate and are converted to the engine's in front of
     // the render; a call of numFrames ENGINE frames pulls the input frames [inputs_before(n0), inputs_before(n0 + numFrames)) of the
     // programme. Planar floats count as nIn one-channel float streams: one path for both.
-    const bool inres = inResOn && nIn > 0;
-    const resample::Plan inp = inPlan;
-    const uint32_t inG = src ? srcG : 1u, inFmt = src ? srcFmt : pcm_pack::F32;
-    const size_t inStreams = src ? src->nStreams : nIn, inB = pcm_pack::sample_bytes(inFmt);
-    auto inStream = [&](size_t s) { return src ? static_cast<const unsigned char*>(src->streams[s]) : reinterpret_cast<const unsigned char*>(in[s]); };
-    // whole HOST blocks, like the reference's block loop (a host block = hostBlockSize / blockSize engine blocks)
-    const size_t hb = (size_t)hostBlockSize;
+    c.inres = inResOn && nIn > 0;
+    c.inp = inPlan;
+    c.inG = src ? c.srcG : 1u; c.inFmt = src ? c.srcFmt : pcm_pack::F32;
+    c.inStreams = src ? src->nStreams : nIn; c.inB = pcm_pack::sample_bytes(c.inFmt);
+    return c;
+}
+
+int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,
+                           const PcmSource* src, FlacJob* flac) {
+    const HostCall call = hostCall(in, nIn, out, nOut, numFrames, sampleTime, pcm, src, flac);
+    const size_t bs = call.bs, hb = call.hb;
     bool tapSlices = hb % bs != 0;          // ragged slices (a host block that no k divides evenly): launch sets hold whole engine blocks
     if (hb != bs && !tapSlices) { std::lock_guard<std::mutex> lock(mu); tapSlices = !tapNodeIds.empty(); }
-    if (tapSlices) {
-        // taps under a host block longer than the engine's: every slice needs its own stretch of the shared tap buffers (setTapSlice),
-        // which launch sets do not do — host block by host block through process()
-        std::vector<const float*> ip(nIn);
-        std::vector<float*> op(nOut);
-        std::vector<float> tailIn, tailOut;
-        std::vector<uint8_t*> sp(pcm ? pcm->nStreams : 0);
-        std::vector<const unsigned char*> srcAt(src ? src->nStreams : 0);
-        std::vector<std::vector<unsigned char>> flacImg;
-        // the meter's carried state comes to the host for the call: the floats are here, the header's scalar loop meters them
-        std::vector<loudness::ChannelState> meterState(meter ? nOut : 0);
-        auto meterSync = [&](bool toHost) -> int {
-            RenderGuard lock(*this);
-            if (hipSetDevice(device) != hipSuccess) return kHipError;
-            if (toHost) { const int rc = ensureLoudness(nOut, 0); if (rc != kOk) return rc; }
-            HIP_OK(hipStreamSynchronize(stream));
-            if (toHost) HIP_OK(hipMemcpy(meterState.data(), dLoudState, nOut * sizeof(loudness::ChannelState), hipMemcpyDeviceToHost));
-            else HIP_OK(hipMemcpy(dLoudState, meterState.data(), nOut * sizeof(loudness::ChannelState), hipMemcpyHostToDevice));
-            return kOk;
-        };
-        if (meter) { const int rc = meterSync(true); if (rc != kOk) return rc; }
-        // the converter's carried frames come to the host for the call as well: the header's scalar loop converts, the same bits
-        std::vector<float> resHist(resamp ? nOut * (size_t)rp.H : 0), resOut;
-        auto resSync = [&](bool toHost) -> int {
-            RenderGuard lock(*this);
-            if (hipSetDevice(device) != hipSuccess) return kHipError;
-            if (toHost) { const int rc = ensureResample(nOut, 0); if (rc != kOk) return rc; }
-            HIP_OK(hipStreamSynchronize(stream));
-            if (toHost) HIP_OK(hipMemcpy(resHist.data(), dResHist[resHistCur], resHist.size() * sizeof(float), hipMemcpyDeviceToHost));
-            else HIP_OK(hipMemcpy(dResHist[resHistCur], resHist.data(), resHist.size() * sizeof(float), hipMemcpyHostToDevice));
-            return kOk;
-        };
-        auto resFail = [&]() { if (resamp) { RenderGuard lock(*this); (void)resampleResetLocked(0); } };
-        if (resamp) { const int rc = resSync(true); if (rc != kOk) return rc; }
-        // and so does the limiter's state: the header's scalar loop limits, the same bits
-        std::vector<unsigned char> limState;
-        std::vector<limiter::GroupStats> limStats;
-        std::vector<float> limOut;
-        auto limSync = [&](bool toHost) -> int {
-            RenderGuard lock(*this);
-            if (hipSetDevice(device) != hipSuccess) return kHipError;
-            if (toHost) {
-                const int rc = ensureLimiter(nOut, 0, 0);
-                if (rc != kOk) return rc;
-                limState.resize(limiter::state_bytes(lmp, (uint32_t)nOut)); limStats.resize(limiter::group_count(lmp, (uint32_t)nOut));
-            }
-            HIP_OK(hipStreamSynchronize(stream));
-            if (toHost) {
-                HIP_OK(hipMemcpy(limState.data(), dLimState[limCur], limState.size(), hipMemcpyDeviceToHost));
-                HIP_OK(hipMemcpy(limStats.data(), dLimStats, limStats.size() * sizeof(limiter::GroupStats), hipMemcpyDeviceToHost));
-            } else {
-                HIP_OK(hipMemcpy(dLimState[limCur], limState.data(), limState.size(), hipMemcpyHostToDevice));
-                HIP_OK(hipMemcpy(dLimStats, limStats.data(), limStats.size() * sizeof(limiter::GroupStats), hipMemcpyHostToDevice));
-            }
-            return kOk;
-        };
-        auto limFail = [&]() { if (limit) { RenderGuard lock(*this); (void)limiterResetLocked(0); } };
-        if (limit) { const int rc = limSync(true); if (rc != kOk) { resFail(); if (meter) (void)meterSync(false); return rc; } }
-        // the input converter's carried frames likewise: unpack_host decodes, the header's scalar pull loop converts, the kernel's bits
-        std::vector<float> inHist(inres ? nIn * (size_t)inp.H : 0), inX;
-        auto inSync = [&](bool toHost) -> int {
-            RenderGuard lock(*this);
-            if (hipSetDevice(device) != hipSuccess) return kHipError;
-            if (toHost) { const int rc = ensureInputResample(nIn); if (rc != kOk) return rc; }
-            HIP_OK(hipStreamSynchronize(stream));
-            if (toHost) HIP_OK(hipMemcpy(inHist.data(), dInHist[inHistCur], inHist.size() * sizeof(float), hipMemcpyDeviceToHost));
-            else HIP_OK(hipMemcpy(dInHist[inHistCur], inHist.data(), inHist.size() * sizeof(float), hipMemcpyHostToDevice));
-            return kOk;
-        };
-        auto inFail = [&]() { if (inres) { RenderGuard lock(*this); (void)inputResampleResetLocked(0); } };
-        if (inres) { const int rc = inSync(true); if (rc != kOk) { resFail(); limFail(); if (meter) (void)meterSync(false); return rc; } }
-        // FLAC delivery: the open frame's codes come to the host too; the floats are quantised here and the header's scalar twin encodes
-        // every frame they complete — the kernel's functions, the kernel's bytes
-        std::vector<std::vector<int32_t>> flacCodes;
-        auto flacSync = [&](bool toHost) -> int {
-            RenderGuard lock(*this);
-            if (hipSetDevice(device) != hipSuccess) return kHipError;
-            if (toHost) { const int rc = ensureFlac(*flac, 0); if (rc != kOk) return rc; flacCodes.assign(nOut, std::vector<int32_t>(flacOpen)); }
-            HIP_OK(hipStreamSynchronize(stream));
-            for (size_t c = 0; c < nOut; ++c) {
-                int32_t* dev = dFlacCarry + c * flac_encode::kMaxFrame;
-                if (toHost) { if (flacOpen) HIP_OK(hipMemcpy(flacCodes[c].data(), dev, flacOpen * sizeof(int32_t), hipMemcpyDeviceToHost)); }
-                else if (!flacCodes[c].empty()) HIP_OK(hipMemcpy(dev, flacCodes[c].data(), flacCodes[c].size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            }
-            if (!toHost) flacOpen = (uint32_t)flacCodes[0].size();
-            return kOk;
-        };
-        auto flacHost = [&](const float* got, size_t gotStride, size_t nd, int64_t gotTime) -> int {
-            std::lock_guard<std::mutex> lock(mu);
-            const uint64_t lead = std::min<uint64_t>(flac->dropLeft, nd), enter = std::min<uint64_t>(flac->takeLeft, nd - lead);
-            flac->dropLeft -= lead; flac->takeLeft -= enter;
-            const uint32_t G = flac->spec.channelsPerStream, bits = flac->spec.bits, ff = flacFF;
-            for (size_t c = 0; c < nOut; ++c) {
-                const uint32_t k0 = pcm_pack::channel_key(flac->spec.seed, (uint32_t)c);
-                pcm_pack::ChannelStats st{flac->peakBits[c], 0u, 0u};
-                for (size_t f = (size_t)lead; f < (size_t)(lead + enter); ++f) {
-                    const float x = got[c * gotStride + f];
-                    st = pcm_pack::stats_fold(x, st);
-                    flacCodes[c].push_back(pcm_pack::quantise(x, bits, flac->spec.dither ? pcm_pack::dither(k0, gotTime + (int64_t)f) : 0.0f));
-                }
-                flac->peakBits[c] = st.peakBits; flac->over[c] += st.over; flac->nonfinite[c] += st.nonfinite;
-            }
-            flacFrames += enter;
-            const size_t nF = flacCodes[0].size() / ff;
-            if (nF == 0) return kOk;
-            if (flacEmitted + nF > 0x7FFFFFFFull) return kInvariantViolation;
-            std::vector<uint32_t> lens(nF);
-            for (size_t s = 0; s < flac->nStreams; ++s) {
-                const int32_t* planar[flac_encode::kMaxChannels];
-                for (uint32_t g = 0; g < G; ++g) planar[g] = flacCodes[s * G + g].data();
-                size_t count = 0;
-                const size_t n = flac_encode::encode_host(planar, G, nF * ff, ff, bits, flacRate, (uint32_t)flacEmitted, false,
-                                                          static_cast<uint8_t*>(flac->streams[s]) + flac->bytes[s], flac->caps[s] - flac->bytes[s], lens.data(), &count, flacLpc);
-                if (n == (size_t)-1 || count != nF) return kInvariantViolation;
-                flac->bytes[s] += n;
-                flacFrameBytes[s].insert(flacFrameBytes[s].end(), lens.begin(), lens.end());
-            }
-            for (size_t c = 0; c < nOut; ++c) flacCodes[c].erase(flacCodes[c].begin(), flacCodes[c].begin() + (ptrdiff_t)(nF * ff));
-            flacEmitted += nF;
-            return kOk;
-        };
-        if (flac) { const int rc = flacSync(true); if (rc != kOk) { resFail(); limFail(); inFail(); if (meter) (void)meterSync(false); return rc; } }
-        size_t inOff = 0;                       // input frames of this call consumed so far
-        size_t outOff = 0;                      // delivered frames of this call so far
-        for (size_t f0 = 0; f0 < numFrames; f0 += hb) {
-            const size_t nf = std::min(hb, numFrames - f0);
-            for (size_t c = 0; c < nIn; ++c) ip[c] = src ? nullptr : in[c] + f0;
-            for (size_t c = 0; c < nOut; ++c) op[c] = wantFloat ? out[c] + f0 : nullptr;
-            if (nf < hb || packed || meter || resamp || limit) {
-                // the last, partly filled host block is still a whole block to the engine (offline-renderer/index.ts:104-131: inputs
-                // padded with zeros, the frames beyond the caller's arrays dropped); a PCM call renders every host block here
-                tailOut.assign(nOut * hb, 0.0f);
-                for (size_t c = 0; c < nOut; ++c) op[c] = tailOut.data() + c * hb;
-            }
-            int flacInRc = kOk;       // a FLAC source is decoded on the host in front of unpack_host (decode_host): the kernels' bits
-            if (inres) {
-                // the stretch this host block's nf engine frames pull, from the input cursor on: decoded where it is PCM, then converted
-                // into the block's rows (zeros behind nf)
-                std::lock_guard<std::mutex> lock(mu);
-                const size_t ni = (size_t)(resample::inputs_before(inp, inFramesOut + nf) - inFramesIn), stride = std::max<size_t>(ni, 1);
-                tailIn.assign(nIn * hb, 0.0f);
-                if (flacSrc) flacInRc = flacInHostImage(*src, inOff, ni, flacImg);
-                if (src && flacInRc == kOk) {
-                    inX.resize(nIn * stride);
-                    for (size_t s = 0; s < src->nStreams; ++s) srcAt[s] = flacSrc ? flacImg[s].data() : inStream(s) + inOff * srcG * srcB;
-                    pcm_unpack::unpack_host(srcFmt, srcG, (uint32_t)src->nStreams, srcAt.data(), ni, inX.data(), stride, ni);
-                }
-                for (size_t c = 0; c < nIn && flacInRc == kOk; ++c) {
-                    (void)resample::resample_in_host(inp, inTable.data(), inRowBase.data(), inHist.data() + c * inp.H, src ? inX.data() + c * stride : in[c] + inOff,
-                                                     inFramesOut, nf, tailIn.data() + c * hb);
-                    ip[c] = tailIn.data() + c * hb;
-                }
-                inOff += ni; inFramesIn += ni; inFramesOut += nf;
-            } else if (src) {
-                // the inputs are needed on the host: the header's scalar loop unpacks them — the kernel's functions, the kernel's floats
-                tailIn.resize(nIn * hb);
-                if (flacSrc) { std::lock_guard<std::mutex> lock(mu); flacInRc = flacInHostImage(*src, f0, nf, flacImg); }
-                for (size_t s = 0; s < src->nStreams && flacInRc == kOk; ++s)
-                    srcAt[s] = flacSrc ? flacImg[s].data() : static_cast<const unsigned char*>(src->streams[s]) + f0 * srcG * srcB;
-                if (flacInRc == kOk) pcm_unpack::unpack_host(srcFmt, srcG, (uint32_t)src->nStreams, srcAt.data(), nf, tailIn.data(), hb, hb);
-                for (size_t c = 0; c < nIn; ++c) ip[c] = tailIn.data() + c * hb;
-            } else if (nf < hb) {
-                tailIn.assign(nIn * hb, 0.0f);
-                for (size_t c = 0; c < nIn; ++c) { std::memcpy(tailIn.data() + c * hb, in[c] + f0, nf * sizeof(float)); ip[c] = tailIn.data() + c * hb; }
-            }
-            const int rc = flacInRc != kOk ? flacInRc : process(ip.data(), nIn, op.data(), nOut, hb, sampleTime + (int64_t)f0);
-            if (rc != kOk) { if (meter) (void)meterSync(false); resFail(); limFail(); inFail(); return rc; }
-            // what is delivered of this host block: its nf frames, or their conversion
-            const float* got = tailOut.data();
-            size_t gotStride = hb, nd = nf, at = f0;
-            int64_t gotTime = sampleTime + (int64_t)f0;
-            if (resamp) {
-                std::lock_guard<std::mutex> lock(mu);
-                nd = (size_t)(resample::outputs_before(rp, resFramesIn + nf) - resample::outputs_before(rp, resFramesIn));
-                gotStride = std::max<size_t>(nd, 1);
-                resOut.resize(nOut * gotStride);
-                for (size_t c = 0; c < nOut; ++c)
-                    (void)resample::resample_host(rp, resTable.data(), resRowBase.data(), resHist.data() + c * rp.H, tailOut.data() + c * hb, nf, resFramesIn,
-                                                  resOut.data() + c * gotStride);
-                got = resOut.data(); at = outOff; gotTime = (int64_t)resFramesOut;
-                resFramesIn += nf; resFramesOut += nd;
-            }
-            if (limit && nd) {
-                std::lock_guard<std::mutex> lock(mu);
-                limOut.resize(nOut * gotStride);
-                limiter::limiter_host(limMeter, lmp, (uint32_t)nOut, limState.data(), limStats.data(), got, gotStride, nd, limFrames, limOut.data(), gotStride);
-                got = limOut.data();
-                limFrames += nd;
-            }
-            if (meter) {
-                std::lock_guard<std::mutex> lock(mu);
-                for (size_t c = 0; c < nOut; ++c)
-                    loudness::meter_host(loudPlan, meterState[c], got + c * gotStride, nd, loudFrames, [&](double ms) { loudSeries[c].push_back(ms); });
-                loudFrames += nd;
-            }
-            if ((nf < hb || packed || meter || resamp || limit) && wantFloat) for (size_t c = 0; c < nOut; ++c) std::memcpy(out[c] + at, got + c * gotStride, nd * sizeof(float));
-            if (pcm) {
-                // the floats are on the host: the header's scalar loop packs them — the kernel's functions, the kernel's bits
-                for (size_t s = 0; s < pcm->nStreams; ++s) sp[s] = static_cast<uint8_t*>(pcm->streams[s]) + at * pcmG * pcmB;
-                pcm_pack::pack_host(pcmFmt, pcmG, (uint32_t)pcm->nStreams, pcm->spec.dither != 0u, pcm->spec.seed, got, gotStride, nd,
-                                    gotTime, sp.data(), pcm->peakBits.data(), pcm->over.data(), pcm->nonfinite.data());
-            }
-            if (flac) {
-                const int rf = flacHost(got, gotStride, nd, gotTime);
-                if (rf != kOk) { if (meter) (void)meterSync(false); resFail(); limFail(); inFail(); return rf; }
-            }
-            outOff += nd;
-        }
-        int rc = meter ? meterSync(false) : kOk;
-        if (flac) { const int rf = flacSync(false); if (rc == kOk) rc = rf; }
-        if (resamp) { const int rr = resSync(false); if (rc == kOk) rc = rr; if (rc != kOk) resFail(); }
-        if (limit) { const int rl = limSync(false); if (rc == kOk) rc = rl; if (rc != kOk) limFail(); }
-        if (inres) { const int ri = inSync(false); if (rc == kOk) rc = ri; if (rc != kOk) inFail(); }
-        return rc;
-    }
+    if (tapSlices) return renderHostBlocks(call);     // (taps under a host block longer than the engine's: engine_host_blocks.cpp)
+    // the launch-set loop, under the names it has always read the call by
+    const bool flacSrc = call.flacSrc, wantFloat = call.wantFloat, packed = call.packed, meter = call.meter, resamp = call.resamp, limit = call.limit, inres = call.inres;
+    const uint32_t flacInB = call.flacInB, srcG = call.srcG, srcFmt = call.srcFmt, pcmG = call.pcmG, pcmFmt = call.pcmFmt, inG = call.inG, inFmt = call.inFmt;
+    const size_t srcB = call.srcB, pcmB = call.pcmB, inStreams = call.inStreams, inB = call.inB;
+    const resample::Plan rp = call.rp, inp = call.inp;
+    const limiter::Plan lmp = call.lmp;
+    auto inStream = [&](size_t s) { return call.inStream(s); };
     const size_t numBlocks = ((numFrames + hb - 1) / hb) * (hb / bs);
     if (numBlocks == 0) return kOk;
     size_t setBlocks, outCapFrames = 0, outCapBlocks = 0;     // what a set delivers at most: frames, and whole blocks of the converted half
@@ -1618,8 +1382,8 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         });
         const pcm_pack::ChannelStats* st = reinterpret_cast<const pcm_pack::ChannelStats*>(src + pcm->nStreams * stride);
         for (size_t c = 0; c < nOut; ++c) {
-            pcm->peakBits[c] = std::max(pcm->peakBits[c], st[c].peakBits);
-            pcm->over[c] += st[c].over; pcm->nonfinite[c] += st[c].nonfinite;
+            pcm->tally.peakBits[c] = std::max(pcm->tally.peakBits[c], st[c].peakBits);
+            pcm->tally.over[c] += st[c].over; pcm->tally.nonfinite[c] += st[c].nonfinite;
         }
     };
     auto deliverLoudness = [&](size_t k) {   // the sums of the sub-blocks set k completed -> the programme's series
