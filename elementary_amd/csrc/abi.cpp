@@ -302,6 +302,25 @@ int elemhip_add_shared_resource(elemhip_t* h, const char* name, const float* con
     return h->engine.addSharedResource(name, ch, nCh, nSamples) ? 1 : 0;
 }
 
+int elemhip_add_shared_resource_pcm(elemhip_t* h, const char* name, const elemhip_resource_src* src, int* inserted) {
+    if (inserted) *inserted = 0;
+    if (!h || !name || !src) return elemhip::kInvalidInstructionFormat;
+    const Engine::ResourceSrc rs{src->format, src->channels, src->sample_rate, src->frames, src->data, src->bytes,
+                                 reinterpret_cast<const Engine::FlacIn*>(src->flac)};
+    bool done = false;
+    const int rc = h->engine.addSharedResourcePcm(name, rs, &done);
+    if (inserted) *inserted = done ? 1 : 0;
+    return rc;
+}
+
+int elemhip_shared_resource_info(elemhip_t* h, const char* name, uint32_t* channels, uint64_t* frames) {
+    return h && name ? h->engine.sharedResourceInfo(name, channels, frames) : elemhip::kInvalidInstructionFormat;
+}
+
+int elemhip_shared_resource_read(elemhip_t* h, const char* name, uint32_t channel, uint64_t first, uint64_t count, float* out) {
+    return h && name ? h->engine.sharedResourceRead(name, channel, first, count, out) : elemhip::kInvalidInstructionFormat;
+}
+
 void elemhip_prune_shared_resources(elemhip_t* h) { if (h) h->engine.pruneSharedResources(); }
 size_t elemhip_gc(elemhip_t* h, int32_t* out, size_t cap) { return h ? h->engine.gc(out, cap) : 0; }
 size_t elemhip_last_gc(elemhip_t* h, int32_t* out, size_t cap) { return h ? h->engine.lastGc(out, cap) : 0; }

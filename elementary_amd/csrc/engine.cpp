@@ -203,6 +203,7 @@ Engine::~Engine() {
     if (dFft) (void)hipFree(dFft);
     if (hFft) (void)hipHostFree(hFft);
     for (void* t : dFftTables) if (t) (void)hipFree(t);
+    resourceLoadFree();
     if (ownStream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -231,13 +232,13 @@ uint32_t Engine::allocRec() {
 // reads as an empty buffer (AudioBufferResource.h:32-40).
 int Engine::ensureResourceChannelOnDevice(const ResourcePtr& r, uint32_t ch, const void** ptr, uint32_t* len) {
     *ptr = nullptr; *len = 0;
-    if (!r || ch >= r->channels.size()) return kOk;
-    *len = (uint32_t)r->channels[ch].size();
+    if (!r || ch >= r->numChannels()) return kOk;
+    *len = (uint32_t)r->frames(ch);
     if (ch == 0) { int rc = ensureResourceOnDevice(r); *ptr = r->dev.ptr; return rc; }
     if (r->devCh.size() <= ch) r->devCh.resize(ch + 1);
     DevBuf& d = r->devCh[ch];
-    if (!d.ptr) {
-        const size_t floats = std::max<size_t>(r->channels[ch].size(), (size_t)blockSize);
+    if (!d.ptr) {                                   // (a resource made on the device has every row already)
+        const size_t floats = std::max<size_t>(r->frames(ch), (size_t)blockSize);
         if (dry) { d.ptr = std::calloc(floats, sizeof(float)); std::memcpy(d.ptr, r->channels[ch].data(), r->channels[ch].size() * 4); }
         else {
             HIP_OK(hipMalloc(&d.ptr, floats * sizeof(float)));
@@ -324,7 +325,7 @@ int Engine::ensureFftTables(uint32_t size) {
 
 int Engine::ensureResourceOnDevice(const ResourcePtr& r) {
     if (r->dev.ptr) return kOk;
-    const size_t have = r->channels.empty() ? 0 : r->channels[0].size();
+    const size_t have = r->frames(0);
     const size_t floats = std::max<size_t>(have, (size_t)blockSize);
     void* p = nullptr;
     if (dry) { r->dev.ptr = std::calloc(floats, sizeof(float)); r->dev.bytes = floats * sizeof(float); return kOk; }
@@ -495,6 +496,7 @@ void Engine::pruneSharedResources() {   // SharedResource.h:94-102
             for (DevBuf& d : it->second->devCh) if (d.ptr) { if (dry) std::free(d.ptr); else deferredFree.push_back(d.ptr); }
             it->second->dev.ptr = nullptr;
             for (DevBuf& d : it->second->devCh) d.ptr = nullptr;
+            it->second->onDevice = false;
             it = resources.erase(it);
         } else ++it;
     }
@@ -553,6 +555,12 @@ int Engine::setOption(const std::string& key, double value) {
         if (frame ? !flac_encode::frame_ok(v) : !flac_encode::bits_ok(v)) return kInvalidPropertyValue;
         if (frame && flacStreams != 0u && v != flacFF) return kInvalidPropertyValue;
         (frame ? flacFrameOpt : flacBitsOpt) = v;
+        return kOk;
+    }
+    // resource_load.h: source frames per staged piece of addSharedResourcePcm (64 .. 2^24, default 2^20). The resource's bits do not depend on it.
+    if (key == "resource_load_frames") {
+        if (!(value >= (double)resource_load::kMinPiece) || value > (double)resource_load::kMaxPiece || value != std::floor(value)) return kInvalidPropertyValue;
+        resourceLoadFramesOpt = (uint32_t)value;
         return kOk;
     }
     if (key == "batch_blocks") { batchBlocks = std::max(1, std::min(1024, (int)value)); return kOk; }      // blocks per multi-block launch (1 = off)

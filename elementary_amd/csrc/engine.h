@@ -69,6 +69,13 @@ struct Resource {
     DevBuf dev;                 // channel 0, uploaded lazily
     std::vector<DevBuf> devCh;  // channels >= 1 (multi-output nodes), uploaded lazily; devCh[0] unused
     bool isTap = false;         // created by getTapResource (mutable feedback buffer)
+    // made on the device from a file's bytes (Engine::addSharedResourcePcm, resource_load.h): every channel's row is in `dev` / `devCh`
+    // already, and `channels` stays empty until something needs the floats on the host (Engine::resourceHost fetches them once)
+    bool onDevice = false;
+    uint32_t deviceChannels = 0;
+    uint64_t deviceFrames = 0;
+    size_t numChannels() const { return onDevice ? deviceChannels : channels.size(); }
+    size_t frames(size_t ch) const { return onDevice ? (ch < deviceChannels ? (size_t)deviceFrames : 0) : (ch < channels.size() ? channels[ch].size() : 0); }
 };
 using ResourcePtr = std::shared_ptr<Resource>;
 
@@ -312,6 +319,16 @@ public:
 
     bool addSharedResource(const std::string& name, const float* const* ch, size_t nCh, size_t nSamples);
     void pruneSharedResources();
+    // A shared resource from a file's own bytes (resource_load.h; option "resource_load_frames"): one interleaved stream of `channels`
+    // channels and `frames` frames of format 1 s16 / 2 packed s24 / 3 f32 in `data`, or 4 FLAC in `flac` (position .. position + frames,
+    // cut at the stream's end), at `sampleRate` Hz (0: the engine's). Decoded — and, at another rate, converted with the centred filter —
+    // on the GPU into the resource's device rows, piece by piece on a stream of its own; the render lock is taken only to insert the
+    // finished resource, so process() is not held up. A handle without a device runs load_host(). *inserted false: the name is taken.
+    struct ResourceSrc { uint32_t format, channels; double sampleRate; uint64_t frames; const void* data; uint64_t bytes; const FlacIn* flac; };
+    int addSharedResourcePcm(const std::string& name, const ResourceSrc& src, bool* inserted);
+    int sharedResourceInfo(const std::string& name, uint32_t* channels, uint64_t* frames);
+    // the floats the nodes see: frames [first, first + count) of `channel` (kInvalidPropertyValue: no such name, channel or range)
+    int sharedResourceRead(const std::string& name, uint32_t channel, uint64_t first, uint64_t count, float* out);
     size_t gc(int32_t* out, size_t cap);
     size_t lastGc(int32_t* out, size_t cap);          // the ids the most recent gc() pruned (ascending)
     bool hasNode(int32_t id);
@@ -585,6 +602,28 @@ private:
     bool flacInFailed(int half);                // the set's error record has arrived: anything in it -> the last error
     int flacInHostImage(const PcmSource& src, uint64_t from, size_t n, std::vector<std::vector<unsigned char>>& images);
     void flacInFree();
+    // The resource loader (engine_resource_load.cpp): everything below is touched under `ctl` only and by the loader's own stream —
+    // never by a render. Two staging halves (pinned: the piece as it lies in the file; device: the FLAC bytes, and the PCM image the
+    // load kernels read), an event per half, the FLAC decoder's scratch, the last rate pair's tables and the last group's row table.
+    uint32_t resourceLoadFramesOpt = 1u << 20;      // option "resource_load_frames"
+    hipStream_t loadStream = nullptr;
+    hipEvent_t loadDone[2] = {nullptr, nullptr};
+    unsigned char* hLoad[2] = {nullptr, nullptr}; unsigned char* dLoadFlac[2] = {nullptr, nullptr}; unsigned char* dLoadImage[2] = {nullptr, nullptr};
+    size_t hLoadBytes = 0, dLoadFlacBytes = 0, dLoadImageBytes = 0;
+    FlacInError* hLoadErr = nullptr; FlacInError* dLoadErr = nullptr;      // one per half
+    void* dLoadSubs = nullptr; uint32_t* dLoadState = nullptr; int32_t* dLoadScratch = nullptr;
+    size_t loadFrameCap = 0, loadScratchCap = 0;
+    resample::Plan loadPlan{};                      // L == 0: no tables yet
+    std::vector<float> loadTable; std::vector<int32_t> loadRowBase;
+    float* dLoadTable = nullptr; int32_t* dLoadRowBase = nullptr;
+    uint16_t* dLoadRowTable = nullptr; uint32_t loadRowGroup = 0, loadRowDwords = 0;
+    int resourceLoadTables(const resample::Plan& p);
+    int resourceLoadGrow(size_t pinned, size_t flacBytes, size_t imageBytes, size_t frames, size_t scratchInts, uint32_t G);
+    int resourceLoadDevice(const ResourceSrc& src, uint32_t fmt, uint64_t N, const resample::Plan* plan, Resource& r);
+    int resourceLoadHost(const ResourceSrc& src, uint32_t fmt, uint64_t N, const resample::Plan* plan, Resource& r);
+    void resourceLoadFree();
+    // the host floats of a resource: `channels`, fetched from the device rows first where the resource was made there (`mu` held)
+    const std::vector<std::vector<float>>& resourceHost(const ResourcePtr& r);
     // A host-buffer render call: its arguments (`pcm` null: planar floats only; `out` may be null with `pcm` or `flac`: nobody asked for
     // the floats; with `src` the nIn input channels come from its streams and `in` is null) and what both renderers derive from them and
     // from the options, computed once by hostCall().

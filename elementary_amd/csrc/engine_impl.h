@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "launch.h"
+#include "resource_load.h"
 
 namespace elemhip {
 

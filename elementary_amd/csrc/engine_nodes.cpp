@@ -31,7 +31,7 @@ static const std::unordered_map<std::string, uint16_t>& opTable() {
 // TwoStageFFTConvolver per `path` assignment). Builds the conv:: state: header + IR partition spectra.
 int Engine::setConvolverIr(Node& n, const ResourcePtr& res) {
     std::vector<float> h;
-    if (!res->channels.empty()) h = res->channels[0];
+    if (res->numChannels()) h = resourceHost(res)[0];
     // trailing |h| < 1e-6 is dropped by the two-stage convolver as a whole and again by each of its
     // three uniform convolvers over ir[0:4096), ir[4096:8192), ir[8192:) (fftconv_oracle.h)
     size_t len = h.size();
@@ -261,7 +261,7 @@ int Engine::bindResource(Node& n, const Value& v) {
     if (rc == kOk) n.res = r;
     return rc;
 }
-static uint32_t resourceFrames(const Node& n) { return (uint32_t)(n.res->channels.empty() ? 0 : n.res->channels[0].size()); }
+static uint32_t resourceFrames(const Node& n) { return (uint32_t)n.res->frames(0); }
 
 // `count` words into a fresh ring of the node (seq / sparseq / sparseq2 / sampleseq tables)
 int Engine::uploadRing(Node& n, const void* words, size_t count) {

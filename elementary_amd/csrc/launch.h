@@ -192,6 +192,21 @@ struct FlacDecodeArgs {
 // (the host's copies of the two tables are checked against the buffers' sizes before anything is launched)
 hipError_t launch_flac_decode(hipStream_t s, const FlacDecodeArgs& a, const FlacInFrame* hostFrames, const FlacInStream* hostStreams,
                               size_t stagedBytes, size_t scratchInts);
+// ---- resource loader (resource_load.hip): a staged piece of a source file into the resource's planar rows, resource_load.h ----
+struct ResourceLoadArgs {
+    const unsigned char* src;       // the staged piece, 16-byte aligned, `srcBytes` (whole 16-byte lines): sample (f, g) of its frame f lies at
+                                    // head + (f * G + g) * sample bytes — source frames [in0, in0 + validIn) of the file's totalIn
+    float*          rows[32];       // the resource's channel rows, `rowFloats` floats each, zeroed before the first piece
+    const uint16_t* rowTable;       // pcm_pack_row_table(G) on the device (copy)
+    const float*    table;          // resample::make_tables: [plan.T][plan.L] (convert)
+    const int32_t*  rowBase;        // [plan.L] (convert)
+    uint64_t        in0, out0;      // the piece's first staged source frame / first written resource frame
+    uint64_t        totalIn, srcBytes, rowFloats;
+    uint32_t        G, head, validIn, validOut, rowDwords, pad;
+    resample::Plan  plan;           // fin = the file's rate, fout = the engine's (convert)
+};
+hipError_t launch_resource_copy(hipStream_t s, const ResourceLoadArgs& a, uint32_t format);         // the file's rate is the engine's
+hipError_t launch_resource_convert(hipStream_t s, const ResourceLoadArgs& a, uint32_t format);
 hipError_t launch_bus_sum(hipStream_t s, float* dst, const float* const* partials, uint32_t count, size_t n);   // dst = ((p0 + p1) + p2) + ... (rank order)
 
 } // namespace elemhip

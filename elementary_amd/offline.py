@@ -691,6 +691,27 @@ class OfflineRenderer:
         for k, v in vfs.items():
             self._rt.add_shared_resource(k, v)
 
+    def update_virtual_file_system_files(self, files: Dict[str, str], resample: bool = True) -> Dict[str, bool]:
+        """Shared resources straight from audio files, decoded on the GPU (``Runtime.add_shared_resource_pcm``): ``{name: path}``. A
+        file that starts with ``fLaC`` is read by ``FlacReader`` (its compressed frames cross the host link), anything else by
+        ``WavReader`` (s16 / s24 / f32). A file whose rate is not the engine's is converted with the centred filter, so it plays at its
+        own pitch and length; ``resample=False`` takes its samples as they are, as ``update_virtual_file_system`` does with floats.
+        Returns ``{name: inserted}`` (False: the name was taken)."""
+        from .flac import FlacReader
+        from .wav import WavReader
+        done = {}
+        for name, path in files.items():
+            with open(path, "rb") as f:
+                is_flac = f.read(4) == b"fLaC"
+            reader = FlacReader(path) if is_flac else WavReader(path)
+            try:
+                rate = reader.sample_rate if resample else None
+                data = reader.read(reader.frames)
+                done[name] = self._rt.add_shared_resource_pcm(name, data, None if is_flac else reader.fmt, reader.channels, rate)
+            finally:
+                reader.close()
+        return done
+
     def prune_virtual_file_system(self) -> None:
         self._rt.prune_shared_resources()
 

@@ -114,6 +114,12 @@ def load_library() -> C.CDLL:
         lib.elemhip_flac_decode.restype = C.c_int
         lib.elemhip_flac_in_error.argtypes = [C.c_void_p, _u32p, _u64p, _u32p]
         lib.elemhip_flac_in_error.restype = C.c_int
+        lib.elemhip_add_shared_resource_pcm.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(_ResourceSrc), C.POINTER(C.c_int)]
+        lib.elemhip_add_shared_resource_pcm.restype = C.c_int
+        lib.elemhip_shared_resource_info.argtypes = [C.c_void_p, C.c_char_p, _u32p, _u64p]
+        lib.elemhip_shared_resource_info.restype = C.c_int
+        lib.elemhip_shared_resource_read.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_float)]
+        lib.elemhip_shared_resource_read.restype = C.c_int
         _lib = lib
     return _lib
 
@@ -192,6 +198,11 @@ def flac_encode(codes, bits: int = 16, flac_frame: int = 4096, sample_rate: int 
 class _FlacIn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("bytes", C.c_uint64), ("frame_offsets", C.c_void_p), ("frame_first_samples", C.c_void_p),
                 ("frames", C.c_uint64), ("channels", C.c_uint32), ("bits", C.c_uint32), ("total_samples", C.c_uint64), ("position", C.c_uint64)]
+
+
+class _ResourceSrc(C.Structure):
+    _fields_ = [("format", C.c_uint32), ("channels", C.c_uint32), ("sample_rate", C.c_double), ("frames", C.c_uint64), ("data", C.c_void_p),
+                ("bytes", C.c_uint64), ("flac", C.POINTER(_FlacIn))]
 
 
 FLAC_IN_REASONS = {1: "bad CRC", 2: "reserved value", 3: "bits missing", 4: "non-zero padding", 5: "sample out of range", 6: "unsupported"}
@@ -322,6 +333,69 @@ class Runtime(CRuntime):
             raise ElemHipError(f"elemhip_create failed: {describe(code)} (code {code})")
         super().__init__(lib, "elemhip_", C.c_void_p(h), sample_rate, block_size)
         self.device = int(device)
+
+    # -- shared resources from a file's bytes (resource_load.h) ------------------------------
+    def add_shared_resource_pcm(self, name: str, data, fmt=None, channels: Optional[int] = None, sample_rate: Optional[float] = None) -> bool:
+        """``elemhip_add_shared_resource_pcm``: a shared resource from interleaved samples as a file holds them, decoded on the GPU —
+        ``data`` int16 ``[frames, channels]`` ('s16'), uint8 ``[frames, channels, 3]`` ('s24'), float32 ``[frames, channels]`` ('f32')
+        or raw bytes of ``fmt`` with ``channels`` given; or a ``FlacChunk`` (``FlacReader.read``), whose frames are decoded there too.
+        ``sample_rate`` other than the engine's (None: the engine's): the resource is converted with the centred filter and holds
+        ``ceil(frames * L / M)`` frames. Returns False where the name is taken; raises ``ElemHipError`` with ``.code`` otherwise
+        (8 a malformed source, 6 no plan for the rate pair or too many frames, 106 a FLAC frame that does not decode)."""
+        import numpy as np
+        src = _ResourceSrc()
+        src.sample_rate = 0.0 if sample_rate is None else float(sample_rate)
+        if isinstance(data, FlacChunk):
+            st = data.struct()
+            src.format, src.channels, src.frames, src.flac = 4, data.channels, data.count, C.pointer(st)
+        else:
+            code = pcm_format(fmt) if fmt is not None else 0
+            if isinstance(data, (bytes, bytearray, memoryview)):
+                a = np.frombuffer(data, dtype=np.uint8)
+            else:
+                a = np.ascontiguousarray(data)
+                if channels is None and a.ndim >= 2:
+                    channels = a.shape[1]
+                if fmt is None:
+                    code = {np.dtype(np.int16): 1, np.dtype(np.uint8): 2, np.dtype(np.float32): 3}.get(a.dtype, 0)
+                a = a.reshape(-1).view(np.uint8)
+            G = int(channels) if channels is not None else 1
+            width = {1: 2, 2: 3, 3: 4}.get(code, 1) * max(G, 1)
+            src.format, src.channels, src.frames, src.data, src.bytes = code, G, a.size // width, a.ctypes.data, a.size
+        done = C.c_int(0)
+        rc = self._lib.elemhip_add_shared_resource_pcm(self._h, name.encode(), C.byref(src), C.byref(done))
+        if rc != 0:
+            err = ElemHipError(f"elemhip_add_shared_resource_pcm failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return bool(done.value)
+
+    def shared_resource_info(self, name: str) -> Dict[str, int]:
+        """``elemhip_shared_resource_info``: ``{'channels', 'frames'}`` of any shared resource."""
+        ch, fr = C.c_uint32(0), C.c_uint64(0)
+        rc = self._lib.elemhip_shared_resource_info(self._h, name.encode(), C.byref(ch), C.byref(fr))
+        if rc != 0:
+            err = ElemHipError(f"elemhip_shared_resource_info failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return {"channels": int(ch.value), "frames": int(fr.value)}
+
+    def shared_resource_read(self, name: str, channel: Optional[int] = None, first: int = 0, count: Optional[int] = None):
+        """``elemhip_shared_resource_read``: the floats the nodes see — one channel's frames ``[first, first + count)``, or with
+        ``channel`` None all channels as ``[channels, count]``."""
+        import numpy as np
+        info = self.shared_resource_info(name)
+        n = info["frames"] - int(first) if count is None else int(count)
+        chans = range(info["channels"]) if channel is None else [int(channel)]
+        out = np.zeros((len(chans), max(n, 0)), dtype=np.float32)
+        for i, c in enumerate(chans):
+            rc = self._lib.elemhip_shared_resource_read(self._h, name.encode(), c, int(first), max(n, 0) if n >= 0 else (1 << 63),
+                                                        out[i].ctypes.data_as(C.POINTER(C.c_float)))
+            if rc != 0:
+                err = ElemHipError(f"elemhip_shared_resource_read failed: {describe(rc)} (code {rc})")
+                err.code = rc
+                raise err
+        return out if channel is None else out[0]
 
     # -- offline / throughput path --------------------------------------------------------
     def process_blocks(self, num_blocks: int, num_outputs: int, out_ptr: int = 0, in_ptr: int = 0, num_inputs: int = 0,

@@ -326,6 +326,33 @@ int elemhip_flac_in_error(elemhip_t*, uint32_t* stream, uint64_t* frame, uint32_
 
 /* bool addSharedResource(name, unique_ptr<SharedResource>)       Runtime.h:83,461-465 (insert-only) */
 int    elemhip_add_shared_resource(elemhip_t*, const char* name, const float* const* channels, size_t nCh, size_t nSamples);
+/* EXTENSION (no counterpart in the reference): a shared resource from a file's own bytes, decoded — and, where the file's rate is not
+ * the engine's, converted — on the GPU into the resource's device rows (elementary_amd/csrc/resource_load.hip; the arithmetic:
+ * resource_load.h). The source is ONE interleaved stream of `channels` channels (1 .. 32) and `frames` frames:
+ *   format 1 s16 / 2 packed s24 / 3 f32   `data` holds frames * channels samples (`bytes` of them at least), little-endian
+ *   format 4 FLAC                         `flac` points at an elemhip_flac_in (what FLAC input reads, see above; 1 .. 8 channels): stream
+ *                                         samples [position, position + frames), cut at the table's closing entry
+ * sample_rate 0 or the engine's: channel g, frame f of the resource is the decoded sample (f, g) — the bits elemhip_add_shared_resource
+ * leaves for the same floats. Another (integral) rate: the resource holds ceil(frames * L / M) frames (L / M = engine rate / file rate
+ * in lowest terms) of the delivery converter's Kaiser-windowed sinc, CENTRED: frame 0 of the file lies at frame 0 of the resource, no
+ * latency to take out; in front of and behind the file is silence. The bits do not depend on option "resource_load_frames" (the piece
+ * of the file, in frames, that is staged at a time; 64 .. 2^24, default 2^20). The call does not hold process() up: the render lock
+ * is taken only to insert the finished resource. Such a resource has no floats on the host until something needs them (convolve).
+ * Returns 0 with *inserted = 1, or = 0 where the name is taken (insert-only, the old resource untouched), else
+ *   8   a format outside 1 .. 4, 0 or more than 32 channels, a NULL field, fewer `bytes` than frames * channels samples, a malformed
+ *       FLAC table
+ *   6   a rate pair without a plan (L <= 1024, 2 * ceil(32 * max(1, M / L)) <= 1024 taps, L <= 8 M, both rates integral) or a
+ *       resource of more than 2^31 - 1 frames
+ *   106 a FLAC frame that does not decode (elemhip_flac_in_error names it, stream 0); nothing is inserted
+ * Not done: STREAMINFO's MD5 is not verified, and resources added as floats are never converted.
+ *   elemhip_shared_resource_info   channels and frames (of channel 0) of any resource; 6: no such name
+ *   elemhip_shared_resource_read   frames [first, first + count) of `channel` as the nodes see them; a resource shorter than the engine's
+ *                                  block can be read up to the block size (the device row's zero padding); 6: no such name, channel or range */
+typedef struct elemhip_resource_src { uint32_t format, channels; double sample_rate; uint64_t frames; const void* data; uint64_t bytes;
+                                      const elemhip_flac_in* flac; } elemhip_resource_src;
+int    elemhip_add_shared_resource_pcm(elemhip_t*, const char* name, const elemhip_resource_src* src, int* inserted);
+int    elemhip_shared_resource_info(elemhip_t*, const char* name, uint32_t* channels, uint64_t* frames);
+int    elemhip_shared_resource_read(elemhip_t*, const char* name, uint32_t channel, uint64_t first, uint64_t count, float* out);
 /* void pruneSharedResources()                                    Runtime.h:89,467-471 */
 void   elemhip_prune_shared_resources(elemhip_t*);
 /* std::set<NodeId> gc()                                          Runtime.h:76,220-272

@@ -203,6 +203,18 @@ public:
     bool addSharedResource(std::string const& name, const float* const* channels, size_t nCh, size_t nSamples) {
         return elemhip_add_shared_resource(h, name.c_str(), channels, nCh, nSamples) != 0;
     }
+    // EXTENSION: the resource from a file's own bytes, decoded (and rate-converted) on the GPU — elemhip_add_shared_resource_pcm.
+    // Returns the engine's code; *inserted false where the name is taken.
+    int addSharedResourcePcm(std::string const& name, const elemhip_resource_src& src, bool* inserted = nullptr) {
+        int done = 0;
+        const int rc = elemhip_add_shared_resource_pcm(h, name.c_str(), &src, &done);
+        if (inserted) *inserted = done != 0;
+        return rc;
+    }
+    int sharedResourceInfo(std::string const& name, uint32_t* channels, uint64_t* frames) { return elemhip_shared_resource_info(h, name.c_str(), channels, frames); }
+    int sharedResourceRead(std::string const& name, uint32_t channel, uint64_t first, uint64_t count, float* out) {
+        return elemhip_shared_resource_read(h, name.c_str(), channel, first, count, out);
+    }
     void pruneSharedResources() { elemhip_prune_shared_resources(h); }                    // Runtime.h:89
     std::vector<std::string> getSharedResourceMapKeys() {                                 // Runtime.h:94
         std::string j = text([&](char* b, size_t c) { return elemhip_shared_resource_keys_json(h, b, c); });
