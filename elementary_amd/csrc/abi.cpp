@@ -1,4 +1,5 @@
 // abi.cpp — the extern "C" surface declared in include/elemhip.h.
+#include <algorithm>
 #include <atomic>
 #include <cstring>
 #include <mutex>
@@ -229,6 +230,42 @@ int elemhip_flac_reset(elemhip_t* h) { return h ? h->engine.flacReset() : elemhi
 int elemhip_flac_lpc_order(elemhip_t* h, uint32_t* order) {
     if (!h || !order) return elemhip::kInvalidInstructionFormat;
     *order = h->engine.flacLpcOrder();
+    return elemhip::kOk;
+}
+
+int elemhip_flac_md5(elemhip_t* h, uint8_t* digests, size_t capacity, uint32_t* state) {
+    return h ? h->engine.flacMd5Read(digests, capacity, state) : elemhip::kInvalidInstructionFormat;
+}
+
+size_t elemhip_flac_md5_record_bytes(void) { return sizeof(flac_md5::Record); }
+
+int elemhip_flac_md5_init(uint8_t* record) {
+    if (!record) return elemhip::kInvalidInstructionFormat;
+    flac_md5::Record r;
+    flac_md5::init(r);
+    std::memcpy(record, &r, sizeof r);
+    return elemhip::kOk;
+}
+
+int elemhip_flac_md5_update(uint8_t* record, const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t bits) {
+    if (!record || (frames && !planar) || channels == 0u || channels > flac_encode::kMaxChannels || !flac_md5::bits_ok(bits)) return elemhip::kInvalidInstructionFormat;
+    for (uint32_t c = 0; c < channels && frames; ++c) if (!planar[c]) return elemhip::kInvalidInstructionFormat;
+    flac_md5::Record r;
+    std::memcpy(&r, record, sizeof r);           // (the caller's bytes need not be aligned)
+    const int32_t* at[flac_encode::kMaxChannels];
+    for (size_t f0 = 0; f0 < frames; f0 += (size_t)1 << 30) {       // (an update counts its frames in 32 bits)
+        for (uint32_t c = 0; c < channels; ++c) at[c] = planar[c] + f0;
+        flac_md5::update_codes(r, at, channels, 0u, std::min<size_t>((size_t)1 << 30, frames - f0), bits);
+    }
+    std::memcpy(record, &r, sizeof r);
+    return elemhip::kOk;
+}
+
+int elemhip_flac_md5_final(const uint8_t* record, uint8_t digest[16]) {
+    if (!record || !digest) return elemhip::kInvalidInstructionFormat;
+    flac_md5::Record r;
+    std::memcpy(&r, record, sizeof r);
+    flac_md5::final(r, digest);
     return elemhip::kOk;
 }
 

@@ -549,6 +549,14 @@ int Engine::setOption(const std::string& key, double value) {
         flacLpcOpt = (uint32_t)value;
         return kOk;
     }
+    // flac_md5.h: 1 — every stream of a FLAC programme carries its STREAMINFO MD5 on the device; 0, the default: not one launch, allocation
+    // or byte differs. The programme keeps the value it started with.
+    if (key == "flac_md5") {
+        if (value != 0.0 && value != 1.0) return kInvalidPropertyValue;
+        if (flacStreams != 0u && (uint32_t)value != flacMd5) return kInvalidPropertyValue;
+        flacMd5Opt = (uint32_t)value;
+        return kOk;
+    }
     if (key == "flac_frame" || key == "flac_bits") {
         const bool frame = key == "flac_frame";
         const uint32_t v = value >= 0.0 && value <= 65536.0 && value == std::floor(value) ? (uint32_t)value : 0u;

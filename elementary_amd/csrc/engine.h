@@ -30,6 +30,7 @@
 #include "resample.h"
 #include "limiter.h"
 #include "flac_decode.h"
+#include "flac_md5.h"
 
 namespace elemhip {
 
@@ -293,7 +294,7 @@ public:
     // maxReduction[group] (the largest d behind a delivered gain, 0 .. 1) / limitedFrames[group] (frames with g < 1): `capacity` entries each
     int limiterRead(LimiterInfo* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity);
     int limiterReset();
-    // FLAC delivery (flac_encode.h; options "flac_frame" 256 .. 4096, default 4096, "flac_bits" 16 / 24 and "flac_lpc_order" 0 .. 12): the host-buffer render
+    // FLAC delivery (flac_encode.h; options "flac_frame" 256 .. 4096, default 4096, "flac_bits" 16 / 24, "flac_lpc_order" 0 .. 12 and "flac_md5" 0 / 1): the host-buffer render
     // delivered as RFC 9639 frames of a fixed block size, encoded on the GPU in the pack kernel's place (flac_encode.hip) — behind the
     // converter and the limiter, next to the meter. The sample values are processBlocksPcm's codes for the same render. The programme is
     // the frames FLAC calls delivered since creation or flacReset; FLAC frame j holds its frames [j F, (j + 1) F). A call returns the
@@ -311,6 +312,10 @@ public:
     int flacReset();
     // option "flac_lpc_order" (flac_lpc.h; 0 .. 12, default 0: none): the open programme's, else the option's
     uint32_t flacLpcOrder();
+    // option "flac_md5" (flac_md5.h; 0, the default: off — no launch, no buffer, not one byte differs; 1): every stream of a programme carries
+    // a running MD5 of its s16 / s24 bytes on the device (flac_md5.hip), which flacFlush finalises. state 0: the option is off in the
+    // programme, or there is none; 1: running, the digests zero; 2: final. digests: [streams][16], `capacity` streams of room (null: the state only).
+    int flacMd5Read(uint8_t* digests, size_t capacity, uint32_t* state);
     // render `numBlocks` blocks with a HIP event pair around every kernel launch; msOut[l] = mean
     // duration of launch level l (l < numLevels), msOut[numLevels] = epilogue. Returns levels + 1.
     int timeLaunches(size_t nOut, size_t numBlocks, float* msOut, size_t cap);
@@ -566,6 +571,15 @@ private:
     };
     uint32_t flacFrameOpt = 4096, flacBitsOpt = 16, flacLpcOpt = 0;
     uint32_t flacLpc = 0;       // the programme's LPC order (flac_lpc.h), taken with flacFF
+    uint32_t flacMd5Opt = 0, flacMd5 = 0;       // option "flac_md5", and the programme's, taken with flacFF
+    bool flacMd5Final = false;                  // flacFlush has brought the digests over
+    std::vector<uint8_t> flacDigests;           // [flacStreams][16] once final
+    unsigned char* dFlacMd5 = nullptr;          // flacMd5Cap records (flac_md5::Record), then as many 16-byte digests
+    size_t flacMd5Cap = 0;
+    flac_md5::Record* flacMd5Records() const { return reinterpret_cast<flac_md5::Record*>(dFlacMd5); }
+    uint8_t* flacMd5Digests() const { return dFlacMd5 + flacMd5Cap * sizeof(flac_md5::Record); }
+    int flacMd5Launch(uint32_t first, uint32_t count, bool finish);        // (`mu` held) on `stream`
+    int flacMd5Finish();                                                   // (`mu` held) pad, chain, digests -> flacDigests
     uint32_t flacFF = 0, flacBits = 0, flacG = 0, flacStreams = 0, flacRate = 0, flacOpen = 0;      // the programme (flacStreams 0: none yet)
     bool flacFlushed = false;
     uint64_t flacFrames = 0, flacEmitted = 0;   // programme frames delivered; FLAC frames emitted per stream

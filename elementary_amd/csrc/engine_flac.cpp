@@ -1,4 +1,4 @@
-// engine_flac.cpp — the host side of FLAC delivery (options "flac_frame", "flac_bits", "flac_lpc_order"; flac_encode.h, flac_encode.hip): the programme's
+// engine_flac.cpp — the host side of FLAC delivery (options "flac_frame", "flac_bits", "flac_lpc_order", "flac_md5"; flac_encode.h, flac_encode.hip, flac_md5.hip): the programme's
 // state, the device buffers' life, the hand-over of a set's frames to the caller's buffers, the flush, the read-out and the reset. The
 // set loop that launches the kernels is renderHostSets (engine_render.cpp).
 #include "engine_impl.h"
@@ -14,13 +14,17 @@ void Engine::flacFree() {
     if (dFlacSlots) (void)hipFree(dFlacSlots);
     if (dFlacSubBits) (void)hipFree(dFlacSubBits);
     if (flacStream) (void)hipStreamDestroy(flacStream);
+    if (dFlacMd5) (void)hipFree(dFlacMd5);
+    dFlacMd5 = nullptr; flacMd5Cap = 0;
     dFlacCarry = dFlacCodes = nullptr; dFlacSlots = dFlacSubBits = nullptr; flacStream = nullptr;
     flacCarryCh = flacCodesCh = flacCodesCap = flacSlotCount = flacSlotWords = 0;
 }
 
-// a new programme: nothing open, frame number 0; its shape is set by the first call (`mu` held)
+// a new programme: nothing open, frame number 0; its shape is set by the first call (`mu` held), which also starts the streams'
+// MD5 records anew (ensureFlac: the device is current there, and nothing of the old programme is in flight)
 int Engine::flacResetLocked() {
-    flacFF = flacBits = flacG = flacStreams = flacRate = flacOpen = flacLpc = 0;
+    flacFF = flacBits = flacG = flacStreams = flacRate = flacOpen = flacLpc = flacMd5 = 0;
+    flacMd5Final = false; flacDigests.clear();
     flacFlushed = false; flacFrames = flacEmitted = 0;
     flacFrameBytes.clear();
     return kOk;
@@ -36,6 +40,19 @@ int Engine::ensureFlac(FlacJob& job, size_t setFrames) {
         if (!(rate >= 1.0) || rate > 1048575.0 || rate != std::floor(rate)) return kInvalidPropertyValue;       // (STREAMINFO holds 20 bits of Hz)
         flacFF = flacFrameOpt; flacLpc = flacLpcOpt; flacBits = bits; flacG = G; flacStreams = S; flacRate = (uint32_t)rate; flacOpen = 0;
         flacFrameBytes.assign(S, std::vector<uint32_t>());
+        flacMd5 = flacMd5Opt;
+        if (flacMd5) {          // S records at their initial value, the digests behind them
+            HIP_OK(hipStreamSynchronize(stream));
+            if (S > flacMd5Cap) {
+                if (dFlacMd5) (void)hipFree(dFlacMd5);
+                dFlacMd5 = nullptr; flacMd5Cap = 0;
+                HIP_OK(hipMalloc((void**)&dFlacMd5, (size_t)S * (sizeof(flac_md5::Record) + 16u)));
+                flacMd5Cap = S;
+            }
+            std::vector<flac_md5::Record> fresh(S);
+            for (flac_md5::Record& r : fresh) flac_md5::init(r);
+            HIP_OK(hipMemcpy(dFlacMd5, fresh.data(), (size_t)S * sizeof(flac_md5::Record), hipMemcpyHostToDevice));
+        }
     } else if (flacBits != bits || flacG != G || flacStreams != S || flacRate != (uint32_t)deliveryRate()) return kInvalidPropertyValue;
     const uint32_t ff = flacFF;
     const size_t cap = (size_t)ff - 1u + setFrames, maxF = cap / ff, slotCount = (size_t)S * maxF * fe::candidates(G), words = fe::slot_words(ff, bits);
@@ -154,7 +171,11 @@ int Engine::flacFlush(void* const* outStreams, const size_t* capacities, size_t*
     RenderGuard lock(*this);
     if (flacFlushed) return kInvalidPropertyValue;
     for (size_t s = 0; s < nOutStreams; ++s) if (bytesOut) bytesOut[s] = 0;
-    if (flacStreams == 0 || flacOpen == 0) { flacFlushed = true; return kOk; }
+    if (flacStreams == 0 || flacOpen == 0) {          // (a programme whose frames were all dropped still has a digest: the empty message's)
+        if (flacStreams != 0u && flacMd5) { const int rc = flacMd5Finish(); if (rc != kOk) return rc; }
+        flacFlushed = true;
+        return kOk;
+    }
     if (nOutStreams != flacStreams || !outStreams || !capacities || !bytesOut) return kInvalidInstructionFormat;
     const uint32_t fb = fe::frame_bound(flacOpen, flacG, flacBits);
     for (size_t s = 0; s < nOutStreams; ++s) { if (!outStreams[s]) return kInvalidInstructionFormat; if (capacities[s] < fb) return kTooManyChannels; }
@@ -188,7 +209,40 @@ int Engine::flacFlush(void* const* outStreams, const size_t* capacities, size_t*
         bytesOut[s] = len;
         flacFrameBytes[s].push_back(len);
     }
+    if (flacMd5) { rc = flacMd5Finish(); if (rc != kOk) return rc; }       // (the open frame's codes were hashed when they were staged)
     flacEmitted += 1; flacOpen = 0; flacFlushed = true;
+    return kOk;
+}
+
+// the set's new codes [first, first + count) of every channel enter their stream's digest, on `stream` behind the stage kernel
+int Engine::flacMd5Launch(uint32_t first, uint32_t count, bool finish) {
+    FlacMd5Args a{};
+    a.codes = dFlacCodes; a.records = flacMd5Records(); a.digests = flacMd5Digests();
+    a.cap = (uint32_t)flacCodesCap; a.G = flacG; a.numStreams = flacStreams; a.bits = flacBits; a.first = first; a.count = count; a.finish = finish ? 1u : 0u;
+    if (flacStreams > flacMd5Cap) return kInvariantViolation;
+    HIP_OK(launch_flac_md5(stream, a));
+    return kOk;
+}
+
+int Engine::flacMd5Finish() {
+    if (hipSetDevice(device) != hipSuccess) return kHipError;
+    const int rc = flacMd5Launch(0u, 0u, true);
+    if (rc != kOk) return rc;
+    flacDigests.assign((size_t)flacStreams * 16u, 0u);
+    HIP_OK(hipMemcpyAsync(flacDigests.data(), flacMd5Digests(), flacDigests.size(), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    flacMd5Final = true;
+    return kOk;
+}
+
+int Engine::flacMd5Read(uint8_t* digests, size_t capacity, uint32_t* state) {
+    RenderGuard lock(*this);
+    const uint32_t st = flacStreams == 0u || !flacMd5 ? 0u : flacMd5Final ? 2u : 1u;
+    if (state) *state = st;
+    if (!digests || st == 0u) return kOk;
+    if (capacity < flacStreams) return kInvalidPropertyValue;
+    if (st == 2u) std::memcpy(digests, flacDigests.data(), (size_t)flacStreams * 16u);
+    else std::memset(digests, 0, (size_t)flacStreams * 16u);
     return kOk;
 }
 

@@ -6,6 +6,7 @@
 #include "engine_impl.h"
 #include "pcm_unpack.h"
 #include "flac_encode.h"
+#include "flac_md5.h"
 #include <functional>
 
 namespace elemhip {
@@ -31,6 +32,7 @@ struct Engine::HostCarry {
     std::vector<float> resHist, inHist;
     std::vector<unsigned char> limState; std::vector<limiter::GroupStats> limStats;
     std::vector<std::vector<int32_t>> flacCodes;        // FLAC delivery: the open frame's codes per channel
+    std::vector<flac_md5::Record> flacMd5;              // ... and, with option "flac_md5", the streams' running digests
     std::vector<Carried> stages;
     size_t opened = 0;                                  // stages [0, opened) are open
 
@@ -53,9 +55,12 @@ struct Engine::HostCarry {
              [this] { return std::vector<Span>{{inHist.data(), e.dInHist[e.inHistCur], inHist.size() * sizeof(float)}}; },
              Carried::kReset, [this] { return e.inputResampleResetLocked(0); }, nullptr},
             // FLAC delivery: the open frame's codes (processBlocksFlac resets the programme itself when the call fails)
-            {c.flac != nullptr, [this] { const int rc = e.ensureFlac(*c.flac, 0); if (rc == kOk) flacCodes.assign(c.nOut, std::vector<int32_t>(e.flacOpen)); return rc; },
+            {c.flac != nullptr, [this] { const int rc = e.ensureFlac(*c.flac, 0);
+                                         if (rc == kOk) { flacCodes.assign(c.nOut, std::vector<int32_t>(e.flacOpen)); flacMd5.resize(e.flacMd5 ? e.flacStreams : 0u); }
+                                         return rc; },
              [this] { std::vector<Span> s;
                       for (auto& codes : flacCodes) s.push_back({codes.data(), e.dFlacCarry + s.size() * flac_encode::kMaxFrame, codes.size() * sizeof(int32_t)});
+                      if (!flacMd5.empty()) s.push_back({flacMd5.data(), e.dFlacMd5, flacMd5.size() * sizeof(flac_md5::Record)});
                       return s; },
              Carried::kNothing, nullptr, [this] { e.flacOpen = (uint32_t)flacCodes[0].size(); }},
         };
@@ -108,6 +113,12 @@ struct Engine::HostCarry {
                 flacCodes[ch].push_back(pcm_pack::quantise(x, bits, flac->spec.dither ? pcm_pack::dither(k0, gotTime + (int64_t)f) : 0.0f));
             }
             flac->tally.peakBits[ch] = st.peakBits; flac->tally.over[ch] += st.over; flac->tally.nonfinite[ch] += st.nonfinite;
+        }
+        // the codes that entered go into their streams' digests, as flac_md5.hip takes a launch set's
+        for (size_t s = 0; s < flacMd5.size(); ++s) {
+            const int32_t* planar[flac_encode::kMaxChannels];
+            for (uint32_t g = 0; g < G; ++g) planar[g] = flacCodes[s * G + g].data();
+            flac_md5::update_codes(flacMd5[s], planar, G, (uint32_t)(flacCodes[s * G].size() - (size_t)enter), enter, bits);
         }
         e.flacFrames += enter;
         const size_t nF = flacCodes[0].size() / ff;

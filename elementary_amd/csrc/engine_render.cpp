@@ -1570,6 +1570,8 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 sa.blockSize = (uint32_t)bs; sa.numChannels = (uint32_t)nOut; sa.validFrames = (uint32_t)enter; sa.srcOffset = (uint32_t)lead; sa.open = flacOpen;
                 sa.cap = (uint32_t)flacCodesCap; sa.bits = flac->spec.bits; sa.dither = flac->spec.dither ? 1u : 0u; sa.seed = flac->spec.seed;
                 HOST_TRY(launch_flac_stage(stream, sa));
+                // the codes that entered with this set go into their streams' MD5 where they lie (the carried ones did when they were staged)
+                if (flacMd5 && enter > 0u) { const int rm = flacMd5Launch(flacOpen, (uint32_t)enter, false); if (rm != kOk) { result = rm; break; } }
                 FlacEncodeArgs ea{};
                 ea.codes = dFlacCodes; ea.slots = dFlacSlots; ea.subBits = dFlacSubBits; ea.dst = dPcm[half] + flac->payloadOff;
                 ea.frameBytes = reinterpret_cast<uint32_t*>(dPcm[half]); ea.streamStride = flac->stride; ea.cap = (uint32_t)flacCodesCap;

@@ -7,6 +7,7 @@
 #include "resample.h"
 #include "limiter.h"
 #include "flac_decode.h"
+#include "flac_md5.h"
 
 namespace elemhip {
 
@@ -173,6 +174,14 @@ struct FlacEncodeArgs {
     uint32_t        lpcOrder;       // flac_lpc.h: 0 (no LPC candidates) .. 12
 };
 hipError_t launch_flac_encode(hipStream_t s, const FlacEncodeArgs& a);      // the encode kernel, then the assemble kernel
+// ---- the STREAMINFO MD5 of FLAC delivery (flac_md5.hip): behind the stage kernel, flac_md5.h ----
+struct FlacMd5Args {
+    const int32_t*  codes;          // [numStreams * G][cap]: frames [first, first + count) of every channel enter their stream's digest
+    flac_md5::Record* records;      // [numStreams], carried from launch to launch
+    uint8_t*        digests;        // [numStreams][16], 4-byte aligned: written with `finish`
+    uint32_t        cap, G, numStreams, bits, first, count, finish /* pad, append the bit length, write the digests */, pad;
+};
+hipError_t launch_flac_md5(hipStream_t s, const FlacMd5Args& a);
 // ---- FLAC input (flac_decode.hip): in front of the unpack kernel or the input-rate converter, flac_decode.h ----
 using FlacInFrame = flac_decode::FrameRec;
 using FlacInStream = flac_decode::StreamRec;

@@ -2,8 +2,9 @@
 host twin ``runtime.flac_encode``): the ``fLaC`` marker and a STREAMINFO block in front, the frames appended as they come, and at
 ``close`` the smallest / largest frame size and the total sample count patched into STREAMINFO.
 
-The STREAMINFO MD5 stays all zero — "not computed" in RFC 9639's words: the unencoded samples never reach the host, and that is the
-point of encoding on the GPU. Decoders accept it and skip their check.
+The STREAMINFO MD5 comes from the engine too: with option ``flac_md5`` = 1 every stream's digest runs on the GPU next to the encoder
+and ``Runtime.flac_read()['md5']`` holds it after the flush (``patch(md5=...)``); no unencoded sample reaches the host for it. Without
+the option the field stays all zero — "not computed" in RFC 9639's words; decoders accept that and skip their check.
 
 ``FlacReader`` — the other direction: a FLAC file as an input of the offline render, indexed on the host and decoded on the GPU."""
 from __future__ import annotations
@@ -12,13 +13,17 @@ import struct
 from typing import Iterable, Optional
 
 
-def streaminfo(flac_frame: int, bits: int, channels: int, sample_rate: int, total_samples: int = 0, min_frame: int = 0, max_frame: int = 0) -> bytes:
-    """The 34 bytes of a STREAMINFO block for a fixed-block-size stream."""
+def streaminfo(flac_frame: int, bits: int, channels: int, sample_rate: int, total_samples: int = 0, min_frame: int = 0, max_frame: int = 0,
+               md5: bytes = bytes(16)) -> bytes:
+    """The 34 bytes of a STREAMINFO block for a fixed-block-size stream; ``md5``: the 16 bytes of the unencoded samples' digest (all
+    zero: not computed)."""
+    if len(md5) != 16:
+        raise ValueError("an MD5 is 16 bytes")
     if not (1 <= channels <= 8) or not (4 <= bits <= 32) or not (0 < sample_rate < (1 << 20)) or not (0 <= total_samples < (1 << 36)):
         raise ValueError("STREAMINFO cannot hold these stream parameters")
     v = (int(sample_rate) << 44) | ((int(channels) - 1) << 41) | ((int(bits) - 1) << 36) | int(total_samples)
     return (struct.pack(">HH", int(flac_frame), int(flac_frame)) + int(min_frame).to_bytes(3, "big") + int(max_frame).to_bytes(3, "big")
-            + v.to_bytes(8, "big") + bytes(16))
+            + v.to_bytes(8, "big") + bytes(md5))
 
 
 class FlacReader:
@@ -28,7 +33,8 @@ class FlacReader:
     ``n`` samples, their slice of the table and the position — the compressed bytes are what crosses the host link, the samples are
     decoded on the GPU (``flac_decode.hip``). Fixed-block-size streams of 8 / 12 / 16 / 20 / 24 bits with blocks of up to 16384 samples.
 
-    The STREAMINFO MD5 is NOT verified: the decoded samples never reach the host. Every frame's CRC-16 is. Unlike ``WavReader``,
+    The STREAMINFO MD5 is NOT verified: the decoded samples never reach the host; ``md5`` holds the 16 bytes the file announces (all
+    zero: none). Every frame's CRC-16 is. Unlike ``WavReader``,
     which streams, the whole (compressed) file is read into memory at construction: the index needs every frame header."""
 
     def __init__(self, path):
@@ -50,12 +56,13 @@ class FlacReader:
                 body = raw[pos + 4:pos + 4 + size]
                 v = int.from_bytes(body[10:18], "big")
                 info = {"min_block": struct.unpack(">H", body[0:2])[0], "max_block": struct.unpack(">H", body[2:4])[0],
-                        "rate": v >> 44, "channels": ((v >> 41) & 7) + 1, "bits": ((v >> 36) & 31) + 1, "total": v & ((1 << 36) - 1)}
+                        "md5": bytes(body[18:34]), "rate": v >> 44, "channels": ((v >> 41) & 7) + 1, "bits": ((v >> 36) & 31) + 1, "total": v & ((1 << 36) - 1)}
             pos += 4 + size
         if info["min_block"] != info["max_block"]:
             raise ValueError("variable block size streams are not read")
         self.sample_rate, self.channels, self.bits, self.flac_frame = info["rate"], info["channels"], info["bits"], info["max_block"]
         self.fmt = "flac"
+        self.md5 = info["md5"]
         self._data = np.frombuffer(raw, dtype=np.uint8)[pos:]
         self._off, self._first = flac_index(self._data, self.channels, self.bits, self.flac_frame)
         self.frames = int(self._first[-1])                  # samples per channel ("frames" as WavReader counts them)
@@ -101,6 +108,7 @@ class FlacWriter:
         self.frames = 0
         self.total_samples = 0
         self.min_frame = self.max_frame = 0
+        self.md5 = bytes(16)
         self._sized = True
         self._f = open(path, "wb")
         self._f.write(b"fLaC" + bytes([0x80]) + (34).to_bytes(3, "big") + streaminfo(self.flac_frame, self.bits, self.channels, self.sample_rate))
@@ -119,9 +127,14 @@ class FlacWriter:
         self.min_frame = min(sizes + ([self.min_frame] if self.min_frame else []))
         self.max_frame = max(sizes + [self.max_frame])
 
-    def patch(self, frames: int, min_frame: int, max_frame: int, total_samples: int) -> None:
-        """The STREAMINFO figures from elsewhere (``Runtime.flac_read``) for frames that were written without their lengths."""
+    def patch(self, frames: int, min_frame: int, max_frame: int, total_samples: int, md5: Optional[bytes] = None) -> None:
+        """The STREAMINFO figures from elsewhere (``Runtime.flac_read``) for frames that were written without their lengths; ``md5``:
+        the stream's digest (``flac_read()['md5'][s]`` at ``md5_state`` 2, or a ``FlacMd5`` digest), which ``close`` writes."""
         self.frames, self.min_frame, self.max_frame, self.total_samples, self._sized = int(frames), int(min_frame), int(max_frame), int(total_samples), True
+        if md5 is not None:
+            if len(md5) != 16:
+                raise ValueError("an MD5 is 16 bytes")
+            self.md5 = bytes(md5)
 
     def close(self, total_samples: Optional[int] = None) -> None:
         if self._f is None:
@@ -129,7 +142,7 @@ class FlacWriter:
         total_samples = self.total_samples if total_samples is None else total_samples
         lo, hi = (self.min_frame, self.max_frame) if self._sized else (0, 0)
         self._f.seek(8)
-        self._f.write(streaminfo(self.flac_frame, self.bits, self.channels, self.sample_rate, int(total_samples), lo, hi))
+        self._f.write(streaminfo(self.flac_frame, self.bits, self.channels, self.sample_rate, int(total_samples), lo, hi, self.md5))
         self._f.close()
         self._f = None
 

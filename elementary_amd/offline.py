@@ -346,7 +346,8 @@ class OfflineRenderer:
     def _flac_files(self, paths, pull, total: int, skip: int, keep: int, bits: int, S: int, G: int, dither_seed, chunk: int, in_fmt=None):
         """``total`` frames rendered in chunks into one FLAC file per stream: a new FLAC programme that leaves the first ``skip``
         delivered frames out and holds ``keep`` (frames cannot be cut on the host: the engine leaves them out in front of the
-        encoder), flushed at the end; STREAMINFO patched from ``flac_read``. ``pull(m)``: the inputs of the next ``m`` engine frames."""
+        encoder), flushed at the end; STREAMINFO patched from ``flac_read`` — with the streams' MD5 where the engine carries option
+        ``flac_md5``. ``pull(m)``: the inputs of the next ``m`` engine frames."""
         from .flac import FlacWriter
         self._rt.flac_reset()
         frame = int(self._rt.flac_read()["flac_frame"])
@@ -369,7 +370,8 @@ class OfflineRenderer:
                 wtr.write(data)
             got = self._rt.flac_read()
             for s, wtr in enumerate(writers):
-                wtr.patch(got["stream_frames"][s], got["min_frame_bytes"][s], got["max_frame_bytes"][s], got["total_samples"][s])
+                wtr.patch(got["stream_frames"][s], got["min_frame_bytes"][s], got["max_frame_bytes"][s], got["total_samples"][s],
+                          md5=got["md5"][s] if got["md5_state"] == 2 else None)
         finally:
             for wtr in writers:
                 wtr.close()
@@ -379,8 +381,8 @@ class OfflineRenderer:
                    dither_seed: Optional[int] = None, chunk_frames: int = 1 << 20):
         """``write_wav`` into FLAC files (16 or 24 ``bits``), encoded on the GPU: one file per stream of ``channels_per_stream`` channels
         (1 .. 8; default all output channels in one file), block size = option ``flac_frame``. The samples a decoder gets back are
-        those of ``write_wav`` in 's16' / 's24' with the same ``dither_seed``. The STREAMINFO MD5 is all zero ("not computed"): the
-        unencoded samples never reach the host. Returns the statistics as ``write_wav`` does, over the frames in the files."""
+        those of ``write_wav`` in 's16' / 's24' with the same ``dither_seed``. The STREAMINFO MD5 is computed on the GPU where the engine factory sets
+        option ``flac_md5`` = 1; without it the field is all zero ("not computed"). Returns the statistics as ``write_wav`` does, over the frames in the files."""
         G = self.num_out if channels_per_stream is None else int(channels_per_stream)
         S = self.num_out // max(G, 1)
         paths = self._stream_paths(path, S)

@@ -107,6 +107,17 @@ def load_library() -> C.CDLL:
         lib.elemhip_flac_encode_lpc.restype = C.c_int
         lib.elemhip_flac_lpc_order.argtypes = [C.c_void_p, _u32p]
         lib.elemhip_flac_lpc_order.restype = C.c_int
+        _u8p = C.POINTER(C.c_uint8)
+        lib.elemhip_flac_md5.argtypes = [C.c_void_p, _u8p, C.c_size_t, _u32p]
+        lib.elemhip_flac_md5.restype = C.c_int
+        lib.elemhip_flac_md5_record_bytes.argtypes = []
+        lib.elemhip_flac_md5_record_bytes.restype = C.c_size_t
+        lib.elemhip_flac_md5_init.argtypes = [_u8p]
+        lib.elemhip_flac_md5_init.restype = C.c_int
+        lib.elemhip_flac_md5_update.argtypes = [_u8p, C.POINTER(C.POINTER(C.c_int32)), C.c_uint32, C.c_size_t, C.c_uint32]
+        lib.elemhip_flac_md5_update.restype = C.c_int
+        lib.elemhip_flac_md5_final.argtypes = [_u8p, _u8p]
+        lib.elemhip_flac_md5_final.restype = C.c_int
         _u64p = C.POINTER(C.c_uint64)
         lib.elemhip_flac_index.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p, C.c_size_t, _szp]
         lib.elemhip_flac_index.restype = C.c_int
@@ -193,6 +204,44 @@ def flac_encode(codes, bits: int = 16, flac_frame: int = 4096, sample_rate: int 
         err.code = rc
         raise err
     return out[:nbytes.value].tobytes(), lens[:nframes.value].copy()
+
+
+class FlacMd5:
+    """The host twin of the MD5 FLAC delivery computes on the GPU (option ``flac_md5``; ``elemhip_flac_md5_init`` / ``_update`` /
+    ``_final``): the digest of one stream's codes as STREAMINFO wants it — for every frame, then channel, the low ``bits / 8`` bytes of
+    the code, little-endian. ``update(codes[G, n], bits)`` may be called piece by piece; ``digest()`` leaves the record as it is."""
+
+    def __init__(self):
+        import numpy as np
+        self._lib = load_library()
+        self.record = np.zeros(int(self._lib.elemhip_flac_md5_record_bytes()), dtype=np.uint8)
+        self._check(self._lib.elemhip_flac_md5_init(self._p()), "init")
+
+    def _p(self):
+        return self.record.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    @staticmethod
+    def _check(rc, what):
+        if rc != 0:
+            err = ElemHipError(f"elemhip_flac_md5_{what} failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+
+    def update(self, codes, bits: int = 16) -> "FlacMd5":
+        import numpy as np
+        a = np.ascontiguousarray(codes, dtype=np.int32)
+        if a.ndim == 1:
+            a = a[None, :]
+        ch, n = int(a.shape[0]), int(a.shape[1])
+        rows = (C.POINTER(C.c_int32) * max(1, ch))(*[a[c].ctypes.data_as(C.POINTER(C.c_int32)) for c in range(ch)])
+        self._check(self._lib.elemhip_flac_md5_update(self._p(), rows, ch, n, int(bits)), "update")
+        return self
+
+    def digest(self) -> bytes:
+        import numpy as np
+        out = np.zeros(16, dtype=np.uint8)
+        self._check(self._lib.elemhip_flac_md5_final(self._p(), out.ctypes.data_as(C.POINTER(C.c_uint8))), "final")
+        return out.tobytes()
 
 
 class _FlacIn(C.Structure):
@@ -650,9 +699,11 @@ class Runtime(CRuntime):
 
     def flac_read(self) -> Dict[str, Any]:
         """``elemhip_flac_read``: the FLAC programme so far — ``{'flac_frame', 'bits', 'channels_per_stream', 'streams', 'sample_rate',
-        'flushed', 'frames', 'lpc_order', 'stream_frames', 'total_samples', 'min_frame_bytes', 'max_frame_bytes', 'frame_bytes'}``: the
-        last five one entry per stream (the STREAMINFO fields; ``frame_bytes`` a uint32 array of every frame's byte length);
-        ``lpc_order`` (``elemhip_flac_lpc_order``) the programme's option ``flac_lpc_order``."""
+        'flushed', 'frames', 'lpc_order', 'md5_state', 'stream_frames', 'total_samples', 'min_frame_bytes', 'max_frame_bytes',
+        'frame_bytes', 'md5'}``: the last six one entry per stream (the STREAMINFO fields; ``frame_bytes`` a uint32 array of every
+        frame's byte length); ``lpc_order`` (``elemhip_flac_lpc_order``) the programme's option ``flac_lpc_order``. ``md5_state``
+        (``elemhip_flac_md5``, option ``flac_md5``): 0 — the option is off in the programme, or there is none; 1 — the digests are
+        running on the GPU, ``md5`` all zero; 2 — final after ``flac_flush``: ``md5`` holds every stream's 16 bytes."""
         import numpy as np
         info = _FlacInfo()
         rc = self._lib.elemhip_flac_read(self._h, C.byref(info), None, 0, None, 0)
@@ -674,11 +725,15 @@ class Runtime(CRuntime):
         lpc = C.c_uint32(0)
         if rc == 0:
             rc = self._lib.elemhip_flac_lpc_order(self._h, C.byref(lpc))
+        md5_state, digests = C.c_uint32(0), np.zeros((max(1, S), 16), dtype=np.uint8)
+        if rc == 0:
+            rc = self._lib.elemhip_flac_md5(self._h, digests.ctypes.data_as(C.POINTER(C.c_uint8)), S, C.byref(md5_state))
         if rc != 0:
             err = ElemHipError(f"elemhip_flac_read failed: {describe(rc)} (code {rc})")
             err.code = rc
             raise err
-        return {"flac_frame": int(info.flac_frame), "lpc_order": int(lpc.value), "bits": int(info.bits), "channels_per_stream": int(info.channels_per_stream), "streams": S,
+        return {"flac_frame": int(info.flac_frame), "lpc_order": int(lpc.value), "md5_state": int(md5_state.value),
+                "md5": [digests[s].tobytes() for s in range(S)], "bits": int(info.bits), "channels_per_stream": int(info.channels_per_stream), "streams": S,
                 "sample_rate": int(info.sample_rate), "flushed": bool(info.flushed), "frames": int(info.frames),
                 "stream_frames": [int(per[s].frames) for s in range(S)], "total_samples": [int(per[s].total_samples) for s in range(S)],
                 "min_frame_bytes": [int(per[s].min_frame_bytes) for s in range(S)], "max_frame_bytes": [int(per[s].max_frame_bytes) for s in range(S)],

@@ -271,8 +271,20 @@ int elemhip_limiter_reset(elemhip_t*);
  *                        6 for a code outside the sample size or a frame number above 2^31 - 1.
  *   elemhip_flac_encode_lpc  the same with an LPC order (0 .. 12, else code 6): the twin of a programme with option "flac_lpc_order"
  *   elemhip_flac_lpc_order   the open programme's LPC order, or the option's where none is open
- * A stream needs "fLaC" and a STREAMINFO block in front (elementary_amd/flac.py writes them); its MD5 is left zero — "not computed":
- * the unencoded samples never reach the host. */
+ * A stream needs "fLaC" and a STREAMINFO block in front (elementary_amd/flac.py writes them). Its MD5 is left zero — "not computed":
+ * the unencoded samples never reach the host — unless option "flac_md5" = 1 (integral, 0 or 1; 0, the default: no launch, no buffer,
+ * not one byte differs): then every stream of a programme carries a running MD5 on the GPU (elementary_amd/csrc/flac_md5.hip, one wave
+ * per stream behind the stage kernel of every launch set; the arithmetic: flac_md5.h) over exactly the bytes
+ * elemhip_process_blocks_pcm would deliver for it in s16 / s24, and elemhip_flac_flush finalises it there: 16 bytes per stream come back,
+ * no sample does. MD5 chains its 64-byte blocks, so one stream hashes at the speed of one wave, about 76 MB/s, on the render's own stream (profiles/r07/flac_md5.txt:
+ * +14 ms on a 44 ms set of 128 mono streams, +7 ms on a 1.15 ms set of one stereo stream, where it is several times the render). Like "flac_frame" the programme keeps the value it
+ * started with (code 6 until elemhip_flac_reset); a call that fails starts a new digest with the new programme.
+ *   elemhip_flac_md5   state 0: the option is off in the programme, or there is none; 1: running, the digests all zero; 2: final, after
+ *                      elemhip_flac_flush (a programme none of whose frames entered has the empty message's digest). digests (NULL, or
+ *                      [streams][16] with room for `capacity` streams; code 6 when that is too small): what STREAMINFO's last 16 bytes hold
+ *   elemhip_flac_md5_init / _update / _final / _record_bytes   pure host arithmetic, no handle: the digest of planar int32 codes of one
+ *                      stream as the GPU computes it — for frame f, then channel, the low bits / 8 bytes of the code, little-endian. `record`:
+ *                      elemhip_flac_md5_record_bytes() bytes of the caller's; _final leaves it as it is, so the updates may go on. */
 typedef struct elemhip_flac_spec { uint32_t bits /* 16, 24; 0: option "flac_bits" */, channels_per_stream, dither /*0 none, 1 TPDF*/, seed;
                                    uint64_t drop, take; /* 0, UINT64_MAX: every delivered frame */ } elemhip_flac_spec;
 typedef struct elemhip_flac_info { uint32_t flac_frame, bits, channels_per_stream, streams, sample_rate, flushed; uint64_t frames; } elemhip_flac_info;
@@ -291,6 +303,11 @@ int elemhip_flac_encode_lpc(const int32_t* const* planar, uint32_t channels, siz
                             uint32_t firstFrameNumber, int flush, uint8_t* out, size_t capacity, size_t* bytesOut, uint32_t* frameBytes, size_t frameCap,
                             size_t* framesOut, uint32_t lpcOrder);
 int elemhip_flac_lpc_order(elemhip_t*, uint32_t* order);
+int elemhip_flac_md5(elemhip_t*, uint8_t* digests /*[streams][16]*/, size_t capacity, uint32_t* state);
+size_t elemhip_flac_md5_record_bytes(void);
+int elemhip_flac_md5_init(uint8_t* record);
+int elemhip_flac_md5_update(uint8_t* record, const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t bits /* 16, 24 */);
+int elemhip_flac_md5_final(const uint8_t* record, uint8_t digest[16]);
 
 /* EXTENSION (no counterpart in the reference): the same render FED with FLAC, decoded on the GPU in front of the unpack kernel (or
  * the input-rate converter) of every launch set (elementary_amd/csrc/flac_decode.hip; the arithmetic: flac_decode.h). Input format

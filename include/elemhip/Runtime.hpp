@@ -195,6 +195,15 @@ public:
                                        frameBytes, frameCap, framesOut, lpcOrder);
     }
     int flacLpcOrder(uint32_t* order) { return elemhip_flac_lpc_order(h, order); }
+    // ... with the STREAMINFO MD5 computed on the GPU (setOption("flac_md5", 1)): state 0 off / no programme, 1 running, 2 final after
+    // flacFlush; digests [streams][16]. The host twins digest planar codes of one stream the same way.
+    int flacMd5(uint8_t* digests, size_t capacity, uint32_t* state) { return elemhip_flac_md5(h, digests, capacity, state); }
+    static size_t flacMd5RecordBytes() { return elemhip_flac_md5_record_bytes(); }
+    static int flacMd5Init(uint8_t* record) { return elemhip_flac_md5_init(record); }
+    static int flacMd5Update(uint8_t* record, const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t bits) {
+        return elemhip_flac_md5_update(record, planar, channels, frames, bits);
+    }
+    static int flacMd5Final(const uint8_t* record, uint8_t digest[16]) { return elemhip_flac_md5_final(record, digest); }
     static int loudnessGate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
         return elemhip_loudness_gate(meanSquares, channels, subBlocks, weights, out);
     }
