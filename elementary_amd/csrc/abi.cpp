@@ -130,7 +130,7 @@ int elemhip_process_blocks_pcm(elemhip_t* h, const float* const* in, size_t nIn,
     if (!h || !spec) return elemhip::kInvalidInstructionFormat;
     static_assert(sizeof(elemhip_pcm_channel_stats) == sizeof(Engine::PcmChannelStats) && sizeof(elemhip_pcm_spec) == sizeof(Engine::PcmSpec), "same layout");
     const Engine::PcmSpec sp{spec->format, spec->channels_per_stream, spec->dither, spec->seed};
-    return h->engine.processBlocksPcm(in, nIn, streams, nStreams, planar, numFrames, st, sp, reinterpret_cast<Engine::PcmChannelStats*>(stats));
+    return h->engine.noiseShapeAfter(h->engine.processBlocksPcm(in, nIn, streams, nStreams, planar, numFrames, st, sp, reinterpret_cast<Engine::PcmChannelStats*>(stats)));
 }
 
 int elemhip_process_blocks_pcm_io(elemhip_t* h, const void* const* inStreams, size_t nInStreams, const elemhip_pcm_in_spec* inSpec,
@@ -140,8 +140,8 @@ int elemhip_process_blocks_pcm_io(elemhip_t* h, const void* const* inStreams, si
     const Engine::PcmSource src{inSpec ? inSpec->format : 0u, inSpec ? inSpec->channels_per_stream : 0u, inStreams, nInStreams};
     Engine::PcmSpec sp{};
     if (outSpec) sp = Engine::PcmSpec{outSpec->format, outSpec->channels_per_stream, outSpec->dither, outSpec->seed};
-    return h->engine.processBlocksPcmIo(src, outStreams, nOutStreams, outSpec ? &sp : nullptr, planar, nPlanar, numFrames, st,
-                                        reinterpret_cast<Engine::PcmChannelStats*>(stats));
+    return h->engine.noiseShapeAfter(h->engine.processBlocksPcmIo(src, outStreams, nOutStreams, outSpec ? &sp : nullptr, planar, nPlanar, numFrames, st,
+                                                                  reinterpret_cast<Engine::PcmChannelStats*>(stats)));
 }
 
 int elemhip_loudness_read(elemhip_t* h, elemhip_loudness_info* info, double* meanSquares, size_t capacity, double* truePeak, float* samplePeak) {
@@ -197,14 +197,46 @@ int elemhip_limiter_read(elemhip_t* h, elemhip_limiter_info* info, double* maxRe
 
 int elemhip_limiter_reset(elemhip_t* h) { return h ? h->engine.limiterReset() : elemhip::kInvalidInstructionFormat; }
 
+int elemhip_noise_shape_set(elemhip_t* h, const float* coeffs, uint32_t count) {
+    return h ? h->engine.noiseShapeSet(coeffs, count) : elemhip::kInvalidInstructionFormat;
+}
+
+int elemhip_noise_shape_read(elemhip_t* h, elemhip_noise_shape_info* info, int32_t* cq, uint64_t* saturated, size_t capacity) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    Engine::NoiseShapeInfo ni{};
+    const int rc = h->engine.noiseShapeRead(&ni, cq, saturated, capacity);
+    if (info) { info->taps = ni.taps; info->channels = ni.channels; info->frames = ni.frames; }
+    return rc;
+}
+
+int elemhip_noise_shape_reset(elemhip_t* h) { return h ? h->engine.noiseShapeReset() : elemhip::kInvalidInstructionFormat; }
+
+size_t elemhip_noise_shape_state_bytes(void) { return sizeof(noise_shape::ChannelState); }
+
+int elemhip_noise_shape_host(const float* coeffs, uint32_t count, uint32_t bits, int dither, uint32_t seed, uint32_t channel0, int64_t time0,
+                             const float* planar, uint32_t channels, size_t stride, size_t frames, uint8_t* state, int32_t* codes) {
+    namespace ns = noise_shape;
+    int32_t cq[ns::kMaxTaps] = {};
+    if (!ns::quantise_coeffs(coeffs, count, cq)) return elemhip::kInvalidPropertyValue;
+    if (!ns::bits_ok(bits) || (channels && frames && (!planar || !codes)) || (frames > stride && channels > 1u)) return elemhip::kInvalidInstructionFormat;
+    std::vector<ns::ChannelState> st(channels);
+    if (state) {
+        std::memcpy(st.data(), state, channels * sizeof(ns::ChannelState));           // (the caller's bytes need not be aligned)
+        for (auto& s : st) for (int32_t& e : s.e) e = std::max(-ns::kErrMax, std::min(ns::kErrMax, e));      // what the recurrence itself keeps
+    }
+    ns::shape_host(cq, count, bits, dither != 0, seed, channel0, time0, planar, channels, stride, frames, st.data(), codes);
+    if (state) std::memcpy(state, st.data(), channels * sizeof(ns::ChannelState));
+    return elemhip::kOk;
+}
+
 int elemhip_process_blocks_flac(elemhip_t* h, const void* const* inStreams, size_t nInStreams, const elemhip_pcm_in_spec* inSpec,
                                 void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams, const elemhip_flac_spec* spec,
                                 size_t numFrames, int64_t st, elemhip_pcm_channel_stats* stats) {
     if (!h || !spec || (nInStreams && (!inStreams || !inSpec))) return elemhip::kInvalidInstructionFormat;
     static_assert(sizeof(elemhip_flac_spec) == sizeof(Engine::FlacSpec), "same layout");
     const Engine::PcmSource src{nInStreams ? inSpec->format : 0u, nInStreams ? inSpec->channels_per_stream : 0u, inStreams, nInStreams};
-    return h->engine.processBlocksFlac(src, outStreams, capacities, bytesOut, nOutStreams, *reinterpret_cast<const Engine::FlacSpec*>(spec), numFrames, st,
-                                       reinterpret_cast<Engine::PcmChannelStats*>(stats));
+    return h->engine.noiseShapeAfter(h->engine.processBlocksFlac(src, outStreams, capacities, bytesOut, nOutStreams, *reinterpret_cast<const Engine::FlacSpec*>(spec),
+                                                                 numFrames, st, reinterpret_cast<Engine::PcmChannelStats*>(stats)));
 }
 
 size_t elemhip_flac_bound(size_t frames, uint32_t channelsPerStream, uint32_t bits) { return (size_t)flac_encode::stream_bound(frames, channelsPerStream, bits); }

@@ -193,6 +193,7 @@ Engine::~Engine() {
     resampleFree();
     inputResampleFree();
     limiterFree();
+    noiseShapeFree();
     flacFree();
     flacInFree();
     if (ioStream) (void)hipStreamDestroy(ioStream);

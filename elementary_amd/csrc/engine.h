@@ -31,6 +31,7 @@
 #include "limiter.h"
 #include "flac_decode.h"
 #include "flac_md5.h"
+#include "noise_shape.h"
 
 namespace elemhip {
 
@@ -294,6 +295,18 @@ public:
     // maxReduction[group] (the largest d behind a delivered gain, 0 .. 1) / limitedFrames[group] (frames with g < 1): `capacity` entries each
     int limiterRead(LimiterInfo* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity);
     int limiterReset();
+    // Noise-shaped requantisation (noise_shape.h; off by default: no launch, no buffer, not one byte differs): with `count` = 1 .. 12
+    // coefficients set, the s16 / s24 codes of processBlocksPcm / PcmIo / Flac come from an error-feedback quantiser with the noise
+    // transfer function 1 - sum c_k z^-k, behind the limiter and in front of the pack kernel or the FLAC stage kernel (noise_shape.hip;
+    // the header's scalar loop where those calls render host block by host block). Float delivery launches nothing. The programme is
+    // the frames those calls quantised since the coefficients were set or the last reset; a call of another channel count, and a call
+    // that fails, start a new one. A set that is refused (noise_shape::quantise_coeffs) changes nothing; count 0 turns it off.
+    struct NoiseShapeInfo { uint32_t taps, channels; uint64_t frames; };
+    int noiseShapeSet(const float* coeffs, uint32_t count);
+    // cq: the quantised coefficients, saturated[channel]: the error clamps so far; `capacity` entries each (either may be null)
+    int noiseShapeRead(NoiseShapeInfo* info, int32_t* cq, uint64_t* saturated, size_t capacity);
+    int noiseShapeReset();
+    int noiseShapeAfter(int rc);      // behind a packed delivery call: a call that failed, wherever it did, starts a new programme; returns rc
     // FLAC delivery (flac_encode.h; options "flac_frame" 256 .. 4096, default 4096, "flac_bits" 16 / 24, "flac_lpc_order" 0 .. 12 and "flac_md5" 0 / 1): the host-buffer render
     // delivered as RFC 9639 frames of a fixed block size, encoded on the GPU in the pack kernel's place (flac_encode.hip) — behind the
     // converter and the limiter, next to the meter. The sample values are processBlocksPcm's codes for the same render. The programme is
@@ -538,6 +551,17 @@ private:
     int ensureLimiter(size_t channels, size_t outBlocksCap, size_t setFrames);   // (`mu` held, both streams idle)
     int limiterResetLocked(size_t channels);
     void limiterFree();
+    // noise-shaped requantisation (noiseShapeSet): the channels' carried states on the device, updated in place by the one stream that
+    // touches them, and the set's codes in a buffer shaped like the float halves; the programme's clock on the host
+    uint32_t nsTaps = 0;                   // 0: off
+    int32_t nsCq[noise_shape::kMaxTaps] = {};
+    noise_shape::ChannelState* dNsState = nullptr; size_t nsStateCap = 0;
+    int32_t* dNsCodes = nullptr; size_t nsCodesCap = 0;
+    uint32_t nsChannels = 0;               // channels of the programme (0: none yet)
+    uint64_t nsFrames = 0;
+    int ensureNoiseShape(size_t channels, size_t codes);             // (`mu` held) a programme of `channels`, room for `codes` codes
+    int noiseShapeResetLocked();
+    void noiseShapeFree();
     template <class T> int growHalves(T* (&h)[2], T* (&d)[2], size_t& have, size_t want);      // (engine_render.cpp: float and unsigned char)
     int growPackedHalves(unsigned char* (&h)[2], unsigned char* (&d)[2], size_t& have, size_t want) { return growHalves(h, d, have, want); }
     int ensureRowTable(uint16_t*& dev, uint32_t& haveGroup, uint32_t& dwords, uint32_t group);
@@ -652,6 +676,7 @@ private:
         bool packed;                                    // PCM or FLAC delivery
         bool meter, resamp, limit, inres;               // options "loudness_meter", "resample_rate", "limiter", "input_rate" apply to this call
         resample::Plan rp, inp; limiter::Plan lmp;
+        bool shape; uint32_t shapeBits, shapeDither, shapeSeed;      // noiseShapeSet applies to this call: s16 / s24 / FLAC delivery
         uint32_t inG, inFmt; size_t inStreams, inB;     // the inputs as streams: planar floats count as nIn one-channel float streams
         const unsigned char* inStream(size_t s) const { return src ? static_cast<const unsigned char*>(src->streams[s]) : reinterpret_cast<const unsigned char*>(in[s]); }
     };

@@ -33,6 +33,7 @@ struct Engine::HostCarry {
     std::vector<unsigned char> limState; std::vector<limiter::GroupStats> limStats;
     std::vector<std::vector<int32_t>> flacCodes;        // FLAC delivery: the open frame's codes per channel
     std::vector<flac_md5::Record> flacMd5;              // ... and, with option "flac_md5", the streams' running digests
+    std::vector<noise_shape::ChannelState> shapeState;  // noise-shaped requantisation: the channels' errors
     std::vector<Carried> stages;
     size_t opened = 0;                                  // stages [0, opened) are open
 
@@ -54,6 +55,10 @@ struct Engine::HostCarry {
             {c.inres, [this] { inHist.resize(c.nIn * (size_t)c.inp.H); return e.ensureInputResample(c.nIn); },
              [this] { return std::vector<Span>{{inHist.data(), e.dInHist[e.inHistCur], inHist.size() * sizeof(float)}}; },
              Carried::kReset, [this] { return e.inputResampleResetLocked(0); }, nullptr},
+            // the error-feedback quantiser's states
+            {c.shape, [this] { shapeState.resize(c.nOut); return e.ensureNoiseShape(c.nOut, 0); },
+             [this] { return std::vector<Span>{{shapeState.data(), e.dNsState, shapeState.size() * sizeof(noise_shape::ChannelState)}}; },
+             Carried::kReset, [this] { return e.noiseShapeResetLocked(); }, nullptr},
             // FLAC delivery: the open frame's codes (processBlocksFlac resets the programme itself when the call fails)
             {c.flac != nullptr, [this] { const int rc = e.ensureFlac(*c.flac, 0);
                                          if (rc == kOk) { flacCodes.assign(c.nOut, std::vector<int32_t>(e.flacOpen)); flacMd5.resize(e.flacMd5 ? e.flacStreams : 0u); }
@@ -98,7 +103,8 @@ struct Engine::HostCarry {
 
     // FLAC delivery of a host block's nd delivered frames: quantised here behind the open frame's codes, and the header's scalar twin
     // encodes every frame they complete
-    int encodeFlac(const float* got, size_t gotStride, size_t nd, int64_t gotTime) {
+    // (`shaped`: null, or the codes of `got`'s frames where noise_shape::shape_host left them, rows gotStride apart)
+    int encodeFlac(const float* got, size_t gotStride, size_t nd, int64_t gotTime, const int32_t* shaped) {
         std::lock_guard<std::mutex> lock(e.mu);
         FlacJob* flac = c.flac;
         const uint64_t lead = std::min<uint64_t>(flac->dropLeft, nd), enter = std::min<uint64_t>(flac->takeLeft, nd - lead);
@@ -110,7 +116,8 @@ struct Engine::HostCarry {
             for (size_t f = (size_t)lead; f < (size_t)(lead + enter); ++f) {
                 const float x = got[ch * gotStride + f];
                 st = pcm_pack::stats_fold(x, st);
-                flacCodes[ch].push_back(pcm_pack::quantise(x, bits, flac->spec.dither ? pcm_pack::dither(k0, gotTime + (int64_t)f) : 0.0f));
+                flacCodes[ch].push_back(shaped ? shaped[ch * gotStride + f]
+                                               : pcm_pack::quantise(x, bits, flac->spec.dither ? pcm_pack::dither(k0, gotTime + (int64_t)f) : 0.0f));
             }
             flac->tally.peakBits[ch] = st.peakBits; flac->tally.over[ch] += st.over; flac->tally.nonfinite[ch] += st.nonfinite;
         }
@@ -150,6 +157,7 @@ int Engine::renderHostBlocks(const HostCall& c) {
     std::vector<const float*> ip(nIn);
     std::vector<float*> op(nOut);
     std::vector<float> tailIn, tailOut, inX, resOut, limOut;
+    std::vector<int32_t> shaped;
     std::vector<uint8_t*> sp(pcm ? pcm->nStreams : 0);
     std::vector<const unsigned char*> srcAt(src ? src->nStreams : 0);
     std::vector<std::vector<unsigned char>> flacImg;
@@ -227,15 +235,24 @@ int Engine::renderHostBlocks(const HostCall& c) {
                 loudness::meter_host(loudPlan, carry.meterState[ch], got + ch * gotStride, nd, loudFrames, [&](double ms) { loudSeries[ch].push_back(ms); });
             loudFrames += nd;
         }
+        if (c.shape && nd) {
+            // the floats are on the host: the header's scalar loop quantises all nd of them — the kernel's functions, the kernel's bits
+            std::lock_guard<std::mutex> lock(mu);
+            shaped.resize(nOut * gotStride);
+            noise_shape::shape_host(nsCq, nsTaps, c.shapeBits, c.shapeDither != 0u, c.shapeSeed, 0u, gotTime, got, (uint32_t)nOut, gotStride, nd,
+                                    carry.shapeState.data(), shaped.data());
+            nsFrames += nd;
+        }
+        const int32_t* codes = c.shape && nd ? shaped.data() : nullptr;
         if ((nf < hb || staged) && c.wantFloat) for (size_t ch = 0; ch < nOut; ++ch) std::memcpy(out[ch] + at, got + ch * gotStride, nd * sizeof(float));
         if (pcm) {
             // the floats are on the host: the header's scalar loop packs them — the kernel's functions, the kernel's bits
             for (size_t s = 0; s < pcm->nStreams; ++s) sp[s] = static_cast<uint8_t*>(pcm->streams[s]) + at * c.pcmG * c.pcmB;
             pcm_pack::pack_host(c.pcmFmt, c.pcmG, (uint32_t)pcm->nStreams, pcm->spec.dither != 0u, pcm->spec.seed, got, gotStride, nd,
-                                gotTime, sp.data(), pcm->tally.peakBits.data(), pcm->tally.over.data(), pcm->tally.nonfinite.data());
+                                gotTime, sp.data(), pcm->tally.peakBits.data(), pcm->tally.over.data(), pcm->tally.nonfinite.data(), codes);
         }
         if (c.flac) {
-            const int rf = carry.encodeFlac(got, gotStride, nd, gotTime);
+            const int rf = carry.encodeFlac(got, gotStride, nd, gotTime, codes);
             if (rf != kOk) { carry.abandon(); return rf; }
         }
         outOff += nd;

@@ -1245,6 +1245,12 @@ Engine::HostCall Engine::hostCall(const float* const* in, size_t nIn, float* con
     // and copied; frames in = frames out, so neither the dither's key nor any count changes
     c.limit = limiterOn && nOut > 0;
     c.lmp = limPlan;
+    // noiseShapeSet: the s16 / s24 codes of a PCM or FLAC delivery come from the error-feedback quantiser, behind the limiter; float
+    // delivery and calls that deliver planar floats only are not quantised at all
+    c.shape = nsTaps > 0u && nOut > 0 && (flac || (pcm && c.pcmFmt != pcm_pack::F32));
+    c.shapeBits = flac ? flac->spec.bits : c.pcmFmt == pcm_pack::S16 ? 16u : 24u;
+    c.shapeDither = flac ? (flac->spec.dither ? 1u : 0u) : pcm ? (pcm->spec.dither ? 1u : 0u) : 0u;
+    c.shapeSeed = flac ? flac->spec.seed : pcm ? pcm->spec.seed : 0u;
     // option "input_rate": the inputs — planar floats or streams — arrive at another rate and are converted to the engine's in front of
     // the render; a call of numFrames ENGINE frames pulls the input frames [inputs_before(n0), inputs_before(n0 + numFrames)) of the
     // programme. Planar floats count as nIn one-channel float streams: one path for both.
@@ -1263,7 +1269,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
     if (hb != bs && !tapSlices) { std::lock_guard<std::mutex> lock(mu); tapSlices = !tapNodeIds.empty(); }
     if (tapSlices) return renderHostBlocks(call);     // (taps under a host block longer than the engine's: engine_host_blocks.cpp)
     // the launch-set loop, under the names it has always read the call by
-    const bool flacSrc = call.flacSrc, wantFloat = call.wantFloat, packed = call.packed, meter = call.meter, resamp = call.resamp, limit = call.limit, inres = call.inres;
+    const bool flacSrc = call.flacSrc, wantFloat = call.wantFloat, packed = call.packed, meter = call.meter, resamp = call.resamp, limit = call.limit, inres = call.inres, shape = call.shape;
     const uint32_t flacInB = call.flacInB, srcG = call.srcG, srcFmt = call.srcFmt, pcmG = call.pcmG, pcmFmt = call.pcmFmt, inG = call.inG, inFmt = call.inFmt;
     const size_t srcB = call.srcB, pcmB = call.pcmB, inStreams = call.inStreams, inB = call.inB;
     const resample::Plan rp = call.rp, inp = call.inp;
@@ -1333,6 +1339,10 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         }
         if (flac) {
             rc = ensureFlac(*flac, outCapFrames);
+            if (rc != kOk) return rc;
+        }
+        if (shape) {
+            rc = ensureNoiseShape(nOut, std::max(setBlocks, outCapBlocks) * nOut * bs);
             if (rc != kOk) return rc;
         }
     }
@@ -1537,6 +1547,20 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 got = dLim[half];
                 limFrames += valid;
             }
+            const int32_t* shaped = nullptr;
+            if (shape && valid) {
+                // the error-feedback quantiser behind the limiter, in front of the pack kernel or the FLAC stage kernel, on the same
+                // stream: all of the set's delivered frames (a FLAC call's `drop` discards codes, not state) at the dither's time. The
+                // states are updated in place and the codes lie in one buffer: this stream's kernels touch them, in order, nobody else.
+                NoiseShapeArgs a{};
+                a.src = got; a.dst = dNsCodes; a.state = dNsState; a.time0 = gotTime;
+                a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nOut; a.validFrames = (uint32_t)valid;
+                a.bits = call.shapeBits; a.dither = call.shapeDither; a.seed = call.shapeSeed; a.taps = nsTaps;
+                std::memcpy(a.cq, nsCq, sizeof a.cq);
+                HOST_TRY(launch_noise_shape(stream, a));
+                shaped = dNsCodes;
+                nsFrames += valid;
+            }
             size_t pcmCopy = 0;
             if (pcm) {
                 // the pack kernel behind the set's last level, on the same stream: the output block is still warm in L2. Its packed
@@ -1549,7 +1573,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 a.rowBase = dPcmRowBase; a.time0 = gotTime; a.streamStride = stride;
                 a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nOut; a.G = pcmG; a.numStreams = (uint32_t)pcm->nStreams;
                 a.validFrames = (uint32_t)valid; a.tilesPerBlock = pcm_pack::tiles_per_block((uint32_t)bs, pcmG); a.rowDwords = pcmRowDwords;
-                a.dither = pcm->spec.dither ? 1u : 0u; a.seed = pcm->spec.seed;
+                a.dither = pcm->spec.dither ? 1u : 0u; a.seed = pcm->spec.seed; a.shaped = shaped;
                 HOST_TRY(launch_pcm_pack(stream, a, pcmFmt));
                 pcmCopy = statsOff + nOut * sizeof(pcm_pack::ChannelStats);
             }
@@ -1568,7 +1592,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 FlacStageArgs sa{};
                 sa.src = got; sa.carry = dFlacCarry; sa.codes = dFlacCodes; sa.stats = fst; sa.time0 = gotTime;
                 sa.blockSize = (uint32_t)bs; sa.numChannels = (uint32_t)nOut; sa.validFrames = (uint32_t)enter; sa.srcOffset = (uint32_t)lead; sa.open = flacOpen;
-                sa.cap = (uint32_t)flacCodesCap; sa.bits = flac->spec.bits; sa.dither = flac->spec.dither ? 1u : 0u; sa.seed = flac->spec.seed;
+                sa.cap = (uint32_t)flacCodesCap; sa.bits = flac->spec.bits; sa.dither = flac->spec.dither ? 1u : 0u; sa.seed = flac->spec.seed; sa.shaped = shaped;
                 HOST_TRY(launch_flac_stage(stream, sa));
                 // the codes that entered with this set go into their streams' MD5 where they lie (the carried ones did when they were staged)
                 if (flacMd5 && enter > 0u) { const int rm = flacMd5Launch(flacOpen, (uint32_t)enter, false); if (rm != kOk) { result = rm; break; } }
@@ -1636,6 +1660,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         if (meter && result != kOk) (void)loudnessResetLocked(loudChannels);
         if (resamp && result != kOk) (void)resampleResetLocked(0);      // likewise: the clock may be ahead of what was delivered
         if (limit && result != kOk) (void)limiterResetLocked(0);
+        if (shape && result != kOk) (void)noiseShapeResetLocked();
         if (inres && result != kOk) (void)inputResampleResetLocked(0);   // and the input programme: its clock may be ahead of what was rendered
     }
     return result;

@@ -39,9 +39,10 @@ __global__ __launch_bounds__(fe::kThreads) void elemhip_flac_stage(FlacStageArgs
         if (i < a.open) codes[i] = a.carry[(size_t)c * fe::kMaxFrame + i];
         else if (i < total) {
             const uint32_t f = i - a.open + a.srcOffset, b = f / a.blockSize;
-            const float x = a.src[((size_t)b * a.numChannels + c) * a.blockSize + (f - b * a.blockSize)];
+            const size_t at = ((size_t)b * a.numChannels + c) * a.blockSize + (f - b * a.blockSize);
+            const float x = a.src[at];
             acc = pp::stats_fold(x, acc);
-            codes[i] = pp::quantise(x, a.bits, a.dither ? pp::dither(k0, a.time0 + (int64_t)f) : 0.0f);
+            codes[i] = a.shaped ? a.shaped[at] : pp::quantise(x, a.bits, a.dither ? pp::dither(k0, a.time0 + (int64_t)f) : 0.0f);
         }
     }
     uint32_t peak = acc.peakBits, over = acc.over, nonf = acc.nonfinite;

@@ -8,6 +8,7 @@
 #include "limiter.h"
 #include "flac_decode.h"
 #include "flac_md5.h"
+#include "noise_shape.h"
 
 namespace elemhip {
 
@@ -82,6 +83,7 @@ struct PcmPackArgs {
     int64_t         time0;          // sample time of the set's first frame (the dither's key)
     uint64_t        streamStride;
     uint32_t        blockSize, numChannels, G, numStreams, validFrames, tilesPerBlock, rowDwords, dither, seed;
+    const int32_t*  shaped;         // null, or the set's codes where its floats lie in `src` (noise_shape.hip): taken in place of quantising
 };
 uint32_t pcm_pack_row_table(uint32_t G, uint16_t* out);      // out[G]; returns PcmPackArgs::rowDwords
 hipError_t launch_pcm_pack(hipStream_t s, const PcmPackArgs& a, uint32_t format);
@@ -159,6 +161,7 @@ struct FlacStageArgs {
     int64_t         time0;          // sample time of frame 0 of `src` (the dither's key)
     uint32_t        blockSize, numChannels, validFrames, open, cap, bits, dither, seed;
     uint32_t        srcOffset;      // frames of `src` in front of the validFrames that stay out of the programme
+    const int32_t*  shaped;         // null, or the set's codes where its floats lie in `src` (noise_shape.hip): taken in place of quantising
 };
 hipError_t launch_flac_stage(hipStream_t s, const FlacStageArgs& a);
 // the codes behind the last whole frame become the next set's carry
@@ -182,6 +185,16 @@ struct FlacMd5Args {
     uint32_t        cap, G, numStreams, bits, first, count, finish /* pad, append the bit length, write the digests */, pad;
 };
 hipError_t launch_flac_md5(hipStream_t s, const FlacMd5Args& a);
+// ---- noise-shaped requantisation (noise_shape.hip): behind the limiter, in front of the pack kernel or the FLAC stage kernel, noise_shape.h ----
+struct NoiseShapeArgs {
+    const float*    src;            // the set's delivered frames, [block][numChannels][blockSize]: validFrames of them
+    int32_t*        dst;            // the same shape: the code of a sample lies where its float lies
+    noise_shape::ChannelState* state;   // [numChannels], carried from set to set, updated in place
+    int64_t         time0;          // sample time of frame 0 of `src` (the dither's key)
+    uint32_t        blockSize, numChannels, validFrames, bits, dither, seed, taps, pad;
+    int32_t         cq[noise_shape::kMaxTaps];
+};
+hipError_t launch_noise_shape(hipStream_t s, const NoiseShapeArgs& a);
 // ---- FLAC input (flac_decode.hip): in front of the unpack kernel or the input-rate converter, flac_decode.h ----
 using FlacInFrame = flac_decode::FrameRec;
 using FlacInStream = flac_decode::StreamRec;

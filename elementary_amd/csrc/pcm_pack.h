@@ -180,9 +180,11 @@ PCM_FD uint64_t stream_stride(uint64_t frames, uint32_t G, uint32_t fmt) { retur
 
 // ---- the scalar loop ---------------------------------------------------------------------------------------------------------------
 // planar[c] + frame -> streams[s] at frame * G + g, frames [0, n) at absolute time t0; stats (peakBits / over / nonfinite per channel)
-// are ADDED to. `planar` rows are `stride` floats apart.
+// are ADDED to. `planar` rows are `stride` floats apart. `shaped` (null: none): the s16 / s24 codes of the same frames, laid out like
+// `planar` (noise_shape.h), taken in place of quantising; the statistics are still the floats'.
 inline void pack_host(uint32_t fmt, uint32_t G, uint32_t nStreams, bool dith, uint32_t seed, const float* planar, size_t stride,
-                      size_t n, int64_t t0, uint8_t* const* streams, uint32_t* peakBits, uint64_t* over, uint64_t* nonfinite) {
+                      size_t n, int64_t t0, uint8_t* const* streams, uint32_t* peakBits, uint64_t* over, uint64_t* nonfinite,
+                      const int32_t* shaped = nullptr) {
     const uint32_t B = sample_bytes(fmt);
     for (uint32_t s = 0; s < nStreams; ++s)
         for (uint32_t g = 0; g < G; ++g) {
@@ -192,7 +194,8 @@ inline void pack_host(uint32_t fmt, uint32_t G, uint32_t nStreams, bool dith, ui
             for (size_t f = 0; f < n; ++f) {
                 const float x = row[f];
                 st = stats_fold(x, st);
-                const uint32_t code = encode(fmt, x, dith && fmt != F32 ? dither(k0, t0 + (int64_t)f) : 0.0f);
+                const uint32_t code = shaped && fmt != F32 ? (uint32_t)shaped[(size_t)c * stride + f]
+                                                           : encode(fmt, x, dith && fmt != F32 ? dither(k0, t0 + (int64_t)f) : 0.0f);
                 uint8_t* d = streams[s] + (f * G + g) * B;
                 for (uint32_t k = 0; k < B; ++k) d[k] = (uint8_t)(code >> (8u * k));
             }

@@ -43,6 +43,7 @@ __global__ __launch_bounds__(pp::kThreads) void elemhip_pcm_pack(PcmPackArgs a) 
         const uint32_t m = (uint32_t)(reinterpret_cast<uintptr_t>(row) >> 2) & 3u;
         const int32_t first = pp::quad_first(q, m);
         uint32_t* dst = rows + a.rowBase[g];
+        const int32_t* shaped = FMT != pp::F32 && a.shaped ? a.shaped + ((size_t)b * a.numChannels + c) * bs + f0 : nullptr;
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         auto in = [&](int32_t f) { return f >= 0 && (uint32_t)f < n; };
         if (pp::quad_whole(first, n)) v = *reinterpret_cast<const float4*>(row + first);
@@ -58,6 +59,7 @@ __global__ __launch_bounds__(pp::kThreads) void elemhip_pcm_pack(PcmPackArgs a) 
         auto sample = [&](int32_t f, float x) {
             if (!in(f)) return;
             acc = pp::stats_fold(x, acc);
+            if (shaped) { dst[f] = (uint32_t)shaped[f]; return; }       // (noise_shape.hip has quantised the set)
             float d = 0.0f;
             if (FMT != pp::F32 && a.dither) {
                 const uint64_t t = (uint64_t)(tTile + f);

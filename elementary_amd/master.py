@@ -21,7 +21,7 @@ def _reader(path):
 
 
 def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, target_lufs: float = -14.0, ceiling_dbtp: float = -1.0,
-               fmt: str = "s24", block_size: int = 512, oversample: int = 1, **limiter) -> Dict[str, Any]:
+               fmt: str = "s24", block_size: int = 512, oversample: int = 1, noise_shape=None, **limiter) -> Dict[str, Any]:
     """``in_path`` -> ``out_path`` (format ``fmt`` — 's16', 's24', 'f32', or 'flac16' / 'flac24' for a FLAC file encoded on the GPU —
     the input's rate and channel count) at ``target_lufs`` integrated loudness under a
     true-peak ceiling of ``ceiling_dbtp``. ``limiter``: further limiter parameters (``lookahead_ms``, ``release_ms``, ``link``).
@@ -45,6 +45,8 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
         raise ValueError(f"unknown limiter parameters: {sorted(unknown)}")
     with _reader(str(in_path)) as r:
         rate, channels, frames, in_fmt = float(r.sample_rate), int(r.channels), int(r.frames), r.fmt
+    from .noise_shape import resolve
+    shape = None if fmt == "f32" else resolve(noise_shape, rate)      # (refused here, before anything is rendered)
     sil_fmt = "s16" if in_fmt == "flac" else in_fmt      # (silence is fed as PCM: a FLAC input is decoded to PCM on the GPU anyway)
 
     def renderer(**kw):
@@ -88,10 +90,11 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
     if not np.isfinite(measured["integrated_lufs"]):
         raise ValueError("the input passes no loudness gate: no gain brings it to a target")
     gain_db = float(target_lufs) - float(measured["integrated_lufs"])
-    second = renderer(limiter=dict(params, gain_db=gain_db))
+    second = renderer(limiter=dict(params, gain_db=gain_db), noise_shape=shape)
     stats = second.process_wav(str(in_path), str(out_path), fmt)
     lim = second.limiter()
-    return {"input_lufs": float(measured["integrated_lufs"]), "input_true_peak_dbtp": float(measured["true_peak_dbtp"]),
+    shaped = {"saturated": int(np.sum(second.noise_shape()["saturated"]))} if shape else {}
+    return {**shaped, "input_lufs": float(measured["integrated_lufs"]), "input_true_peak_dbtp": float(measured["true_peak_dbtp"]),
             "output_lufs": float(stats["integrated_lufs"]), "output_true_peak_dbtp": float(stats["true_peak_dbtp"]), "gain_db": gain_db,
             "max_reduction_db": float(lim["max_reduction_db"]), "max_reduction": float(np.max(lim["max_reduction"], initial=0.0)),
             "limited_frames": int(np.sum(lim["limited_frames"])), "over": int(np.sum(stats["over"])), "nonfinite": int(np.sum(stats["nonfinite"]))}

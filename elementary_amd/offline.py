@@ -27,7 +27,7 @@ class OfflineRenderer:
     def initialize(self, num_input_channels: int = 0, num_output_channels: int = 2, sample_rate: float = 44100,
                    block_size: int = 512, virtual_file_system: Optional[Dict[str, np.ndarray]] = None,
                    event_history_blocks: int = 0, capture_history_blocks: int = 0, loudness_meter: bool = False,
-                   output_sample_rate: Optional[float] = None, limiter=None, input_sample_rate: Optional[float] = None) -> None:
+                   output_sample_rate: Optional[float] = None, limiter=None, input_sample_rate: Optional[float] = None, noise_shape=None) -> None:
         """``event_history_blocks`` (no counterpart in the reference; 0 = off): engine option of the same name — `scope` and `fft`
         nodes keep a device ring long enough for a relay window of that many blocks, so ``process`` still renders launch sets of
         that size with such a listener attached (engines without ``set_option`` relay after every block anyway).
@@ -54,7 +54,14 @@ class OfflineRenderer:
         frames; a call of ``m`` of them consumes ``runtime.input_resample_frames(m)`` input frames from where the last one stopped,
         and inputs that end early are padded with silence. ``process_wav`` then takes files at this rate, with that latency taken
         out. With ``sample_rate`` = 4 x 44100 and both rates 44100, a 44.1 kHz file is processed with fourfold oversampling. An
-        engine without the option raises ``RuntimeError``."""
+        engine without the option raises ``RuntimeError``.
+        ``noise_shape`` (likewise; None: off): a preset of ``elementary_amd.noise_shape`` ('first', 'second', 'lipshitz5',
+        'fweighted9', 'modified_e9') or up to 12 raw coefficients c_1 .. c_K — the s16 / s24 samples of ``process_pcm``,
+        ``process_pcm_io``, ``write_wav``, ``write_flac`` and ``process_wav`` come from an error-feedback quantiser on the GPU
+        (``Runtime.noise_shape``) behind the limiter, whose error is the dither's shaped by 1 - sum c_k z^-k: out of the 2 - 5 kHz
+        region, towards the top of the band. The three psychoacoustic presets are 44.1 kHz designs and raise ``ValueError`` unless the
+        delivery rate is 44100 or 48000; raw coefficients are taken at any rate. With ``dither_seed=None`` the shaping runs
+        undithered: deterministic, and idle tones are possible. Float delivery is never touched."""
         self.num_in = int(num_input_channels)
         self.num_out = int(num_output_channels)
         self.block_size = int(block_size)
@@ -101,6 +108,16 @@ class OfflineRenderer:
             except RuntimeError as e:
                 raise RuntimeError(f"this engine cannot take {float(input_sample_rate):g} Hz inputs at {self.sample_rate:g} Hz") from e
             self.input_sample_rate = float(input_sample_rate)
+        from . import noise_shape as _ns
+        shape = _ns.resolve(noise_shape, self.output_sample_rate)
+        self._noise_shape = shape is not None
+        if self._noise_shape:
+            if not hasattr(self._rt, "noise_shape"):
+                raise RuntimeError("this engine has no noise shaping (Runtime.noise_shape)")
+            try:
+                self._rt.noise_shape(shape)
+            except RuntimeError as e:
+                raise ValueError(f"this engine refuses the noise-shaping coefficients {shape}") from e
         self._time = 0
         for k, v in (virtual_file_system or {}).items():
             self._rt.add_shared_resource(k, v)
@@ -467,6 +484,8 @@ class OfflineRenderer:
         delivered frame off. ``input_frames``: ``num_frames`` counts frames of an input file, which render ceil(F L / M) engine
         frames (L / M = engine rate / input rate)."""
         limiting = getattr(self, "_limiter", False)
+        if getattr(self, "_noise_shape", False):
+            self._rt.noise_shape_reset()        # (a file is a programme of its own for the error feedback too)
         if getattr(self, "_inres", False):
             self._rt.input_resample_reset()
             iinfo = self._rt.input_resample_read()
@@ -492,6 +511,16 @@ class OfflineRenderer:
             self._rt.limiter_reset()
             lat += self._rt.limiter_read()["latency_frames"]
         return int(num_frames) + -((-lat * down) // up), lat, -((-int(num_frames) * up) // down)
+
+    def noise_shape(self) -> Dict[str, Any]:
+        """The noise shaping's coefficients and counts (``initialize(noise_shape=...)``): ``Runtime.noise_shape_read()``."""
+        if not getattr(self, "_noise_shape", False):
+            raise RuntimeError("noise shaping is off: initialize(noise_shape=...)")
+        return self._rt.noise_shape_read()
+
+    def noise_shape_reset(self) -> None:
+        """A new programme for the noise shaping: errors zero, counts zero."""
+        self._rt.noise_shape_reset()
 
     def loudness_reset(self) -> None:
         """A new programme for the loudness meter: time 0, zero filter state, no peaks."""

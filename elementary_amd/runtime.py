@@ -119,6 +119,18 @@ def load_library() -> C.CDLL:
         lib.elemhip_flac_md5_final.argtypes = [_u8p, _u8p]
         lib.elemhip_flac_md5_final.restype = C.c_int
         _u64p = C.POINTER(C.c_uint64)
+        _fp, _i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        lib.elemhip_noise_shape_set.argtypes = [C.c_void_p, _fp, C.c_uint32]
+        lib.elemhip_noise_shape_set.restype = C.c_int
+        lib.elemhip_noise_shape_read.argtypes = [C.c_void_p, C.POINTER(_NoiseShapeInfo), _i32p, _u64p, C.c_size_t]
+        lib.elemhip_noise_shape_read.restype = C.c_int
+        lib.elemhip_noise_shape_reset.argtypes = [C.c_void_p]
+        lib.elemhip_noise_shape_reset.restype = C.c_int
+        lib.elemhip_noise_shape_state_bytes.argtypes = []
+        lib.elemhip_noise_shape_state_bytes.restype = C.c_size_t
+        lib.elemhip_noise_shape_host.argtypes = [_fp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int64, _fp, C.c_uint32, C.c_size_t,
+                                                 C.c_size_t, _u8p, _i32p]
+        lib.elemhip_noise_shape_host.restype = C.c_int
         lib.elemhip_flac_index.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p, C.c_size_t, _szp]
         lib.elemhip_flac_index.restype = C.c_int
         lib.elemhip_flac_decode.argtypes = [C.POINTER(_FlacIn), C.c_size_t, C.POINTER(C.POINTER(C.c_int32)), _szp, _u32p]
@@ -204,6 +216,36 @@ def flac_encode(codes, bits: int = 16, flac_frame: int = 4096, sample_rate: int 
         err.code = rc
         raise err
     return out[:nbytes.value].tobytes(), lens[:nframes.value].copy()
+
+
+class _NoiseShapeInfo(C.Structure):
+    _fields_ = [("taps", C.c_uint32), ("channels", C.c_uint32), ("frames", C.c_uint64)]
+
+
+def noise_shape_host(coeffs, x, bits: int = 16, dither_seed: Optional[int] = None, channel0: int = 0, time0: int = 0, state=None):
+    """``elemhip_noise_shape_host``: the scalar twin of the noise-shaping kernel, pure host arithmetic — ``x`` float32
+    ``[channels, frames]`` at absolute frame ``time0`` (row c = channel ``channel0 + c`` of the dither's key) -> ``(codes, state)``:
+    int32 ``[channels, frames]`` and the carried state, uint8 ``[channels, 64]`` (int32 ``e[12]`` newest first, uint64 ``saturated``,
+    8 bytes reserved). ``state``: the one a former call returned, or None at a programme's start. ``dither_seed`` None: no dither."""
+    import numpy as np
+    lib = load_library()
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    if a.ndim == 1:
+        a = a[None, :]
+    ch, n = a.shape
+    c = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(-1)
+    sb = int(lib.elemhip_noise_shape_state_bytes())
+    st = np.zeros((ch, sb), dtype=np.uint8) if state is None else np.array(state, dtype=np.uint8).reshape(ch, sb)
+    codes = np.zeros((ch, n), dtype=np.int32)
+    fp = C.POINTER(C.c_float)
+    rc = lib.elemhip_noise_shape_host(c.ctypes.data_as(fp), c.size, int(bits), 0 if dither_seed is None else 1,
+                                      0 if dither_seed is None else int(dither_seed) & 0xFFFFFFFF, int(channel0), int(time0), a.ctypes.data_as(fp), ch,
+                                      max(n, 1), n, st.ctypes.data_as(C.POINTER(C.c_uint8)), codes.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        err = ElemHipError(f"elemhip_noise_shape_host failed: {describe(rc)} (code {rc})")
+        err.code = rc
+        raise err
+    return codes, st
 
 
 class FlacMd5:
@@ -902,6 +944,42 @@ class Runtime(CRuntime):
         rc = self._lib.elemhip_limiter_reset(self._h)
         if rc != 0:
             err = ElemHipError(f"elemhip_limiter_reset failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+
+    def noise_shape(self, coeffs) -> None:
+        """``elemhip_noise_shape_set``: the error-feedback coefficients c_1 .. c_K (1 .. 12 of them) of s16 / s24 / FLAC delivery, or
+        None / an empty list to turn the shaping off (the default). Starts a new programme. A set the engine refuses (more than 12,
+        a non-finite one, too large a sum) raises with ``.code`` 6 and changes nothing."""
+        import numpy as np
+        c = np.zeros(0, dtype=np.float32) if coeffs is None else np.ascontiguousarray(coeffs, dtype=np.float32).reshape(-1)
+        rc = self._lib.elemhip_noise_shape_set(self._h, c.ctypes.data_as(C.POINTER(C.c_float)) if c.size else None, c.size)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_noise_shape_set failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+
+    def noise_shape_read(self) -> Dict[str, Any]:
+        """``elemhip_noise_shape_read``: ``taps`` (0: off), ``coeffs_q`` (int32: the coefficients times 2048, rounded), the programme's
+        ``channels`` (0 before its first call) and ``frames``, and ``saturated`` (uint64 per channel: the error clamps so far)."""
+        import numpy as np
+        info = _NoiseShapeInfo()
+        rc = self._lib.elemhip_noise_shape_read(self._h, C.byref(info), None, None, 0)
+        cq, sat = np.zeros(int(info.taps), dtype=np.int32), np.zeros(int(info.channels), dtype=np.uint64)
+        if rc == 0 and info.taps:
+            rc = self._lib.elemhip_noise_shape_read(self._h, C.byref(info), cq.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    sat.ctypes.data_as(C.POINTER(C.c_uint64)) if sat.size else None, max(cq.size, sat.size))
+        if rc != 0:
+            err = ElemHipError(f"elemhip_noise_shape_read failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return {"taps": int(info.taps), "coeffs_q": cq, "channels": int(info.channels), "frames": int(info.frames), "saturated": sat}
+
+    def noise_shape_reset(self) -> None:
+        """``elemhip_noise_shape_reset``: a new programme (errors zero, counts zero)."""
+        rc = self._lib.elemhip_noise_shape_reset(self._h)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_noise_shape_reset failed: {describe(rc)} (code {rc})")
             err.code = rc
             raise err
 

@@ -236,6 +236,33 @@ typedef struct elemhip_limiter_info { uint32_t lookahead_frames, latency_frames,
 int elemhip_limiter_read(elemhip_t*, elemhip_limiter_info* info, double* maxReduction, uint64_t* limitedFrames, size_t capacity);
 int elemhip_limiter_reset(elemhip_t*);
 
+/* EXTENSION (no counterpart in the reference): noise-shaped requantisation on the GPU (elementary_amd/csrc/noise_shape.hip; the
+ * arithmetic: noise_shape.h). With coefficients c_1 .. c_K set (1 <= K <= 12), the s16 / s24 codes that elemhip_process_blocks_pcm,
+ * elemhip_process_blocks_pcm_io and elemhip_process_blocks_flac deliver come from an error-feedback quantiser behind the limiter, whose
+ * requantisation error has the spectrum of plain TPDF dither times the noise transfer function 1 - sum c_k z^-k. The dither (the call's
+ * dither flag and seed) is the pack kernel's, keyed on the absolute frame and the channel, at 8 fraction bits; without it the shaping is
+ * deterministic and idle tones are possible. Coefficients are quantised once, cq_k = floor(c_k * 2048 + 0.5); code 6, and nothing
+ * changes, for K > 12, a non-finite c_k or sum |cq_k| > 131071. Errors are clamped to 64 LSB, and every clamp is counted per channel.
+ * count = 0, the default, turns it off: no launch, no buffer, not one byte differs. Float delivery is never touched; the statistics and
+ * the loudness meter keep reading the floats. FLAC frames decode to the PCM path's codes and the STREAMINFO MD5 is that of its bytes, as
+ * without shaping; a FLAC call's `drop` discards codes, not state.
+ * The programme — the frames those calls quantised, in call order, since the coefficients were set or elemhip_noise_shape_reset — gives
+ * the same bytes however it is cut into calls and launch sets. A call of another channel count, and a call that fails, start a new one.
+ *   elemhip_noise_shape_read   taps (0: off), the programme's channels and frames; cq (the quantised coefficients) and saturated (the
+ *                              clamps per channel), `capacity` entries each, either may be null
+ *   elemhip_noise_shape_reset  a new programme: errors zero, counts zero
+ *   elemhip_noise_shape_host   the scalar twin, without a handle: rows of `planar` (`stride` floats apart, row c = channel channel0 + c
+ *                              of the dither's key) at absolute frame time0 -> codes (the same layout); state: null, or
+ *                              channels * elemhip_noise_shape_state_bytes() bytes, in-out, zero at a programme's start
+ *                              (int32 e[12], newest first; uint64 saturated; 8 bytes reserved) */
+typedef struct elemhip_noise_shape_info { uint32_t taps, channels; uint64_t frames; } elemhip_noise_shape_info;
+int elemhip_noise_shape_set(elemhip_t*, const float* coeffs, uint32_t count);
+int elemhip_noise_shape_read(elemhip_t*, elemhip_noise_shape_info* info, int32_t* cq, uint64_t* saturated, size_t capacity);
+int elemhip_noise_shape_reset(elemhip_t*);
+size_t elemhip_noise_shape_state_bytes(void);
+int elemhip_noise_shape_host(const float* coeffs, uint32_t count, uint32_t bits, int dither, uint32_t seed, uint32_t channel0, int64_t time0,
+                             const float* planar, uint32_t channels, size_t stride, size_t frames, uint8_t* state, int32_t* codes);
+
 /* EXTENSION (no counterpart in the reference): the same render delivered as FLAC, encoded on the GPU in the pack kernel's place
  * (elementary_amd/csrc/flac_encode.hip; the arithmetic and the decision rules: flac_encode.h) — behind the delivery-rate converter and
  * the limiter, next to the meter. RFC 9639 "subset" streams of a fixed block size (option "flac_frame": 256, 512, 1024, 2048 or 4096,

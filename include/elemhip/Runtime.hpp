@@ -161,6 +161,12 @@ public:
         return elemhip_limiter_read(h, info, maxReduction, limitedFrames, capacity);
     }
     int limiterReset() { return elemhip_limiter_reset(h); }
+    // EXTENSION: noise-shaped requantisation of s16 / s24 / FLAC delivery (count 0: off)
+    int noiseShapeSet(const float* coeffs, uint32_t count) { return elemhip_noise_shape_set(h, coeffs, count); }
+    int noiseShapeRead(elemhip_noise_shape_info* info, int32_t* cq, uint64_t* saturated, size_t capacity) {
+        return elemhip_noise_shape_read(h, info, cq, saturated, capacity);
+    }
+    int noiseShapeReset() { return elemhip_noise_shape_reset(h); }
     // EXTENSION: the block loop delivered as FLAC frames encoded on the GPU (elemhip_process_blocks_flac; setOption("flac_frame" /
     // "flac_bits")): inputs as processBlocksPcmIo takes them, per output stream a buffer of at least flacBound(frames delivered,
     // channels_per_stream, bits) bytes; bytesOut[s] = the bytes of the FLAC frames the call completed. flacFlush closes the programme
