@@ -229,6 +229,53 @@ int elemhip_noise_shape_host(const float* coeffs, uint32_t count, uint32_t bits,
     return elemhip::kOk;
 }
 
+int elemhip_spectrum_set(elemhip_t* h, const elemhip_spectrum_spec* spec) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    if (!spec) return h->engine.spectrumSet(nullptr);
+    const Engine::SpectrumSpec sp{spec->size, spec->hop, spec->center, spec->bands, spec->window, spec->band_first, spec->band_count, spec->weights};
+    return h->engine.spectrumSet(&sp);
+}
+
+int elemhip_spectrum_read(elemhip_t* h, elemhip_spectrum_info* info, float* out, size_t capacity, double* sums, size_t sumCapacity) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    static_assert(sizeof(elemhip_spectrum_info) == sizeof(Engine::SpectrumInfo), "same layout");
+    Engine::SpectrumInfo si{};
+    const int rc = h->engine.spectrumRead(&si, out, capacity, sums, sumCapacity);
+    if (info) std::memcpy(info, &si, sizeof si);
+    return rc;
+}
+
+int elemhip_spectrum_flush(elemhip_t* h) { return h ? h->engine.spectrumFlush() : elemhip::kInvalidInstructionFormat; }
+
+int elemhip_spectrum_reset(elemhip_t* h) { return h ? h->engine.spectrumReset() : elemhip::kInvalidInstructionFormat; }
+
+uint64_t elemhip_spectrum_frames(uint32_t size, uint32_t hop, int center, uint64_t n, int flushed) {
+    if (!ffr::size_ok(size) || hop == 0u || hop > size) return 0u;
+    const uint32_t P = center ? size / 2u : 0u;
+    return flushed ? spectrum::frames_total(n, size, hop, P) : spectrum::frames_complete(n, size, hop, P);
+}
+
+int elemhip_spectrum_host(const elemhip_spectrum_spec* spec, const float* planar, uint32_t channels, size_t stride, size_t frames, uint64_t n0,
+                          uint64_t j0, uint64_t j1, float* tail, double* sums, float* out) {
+    if (!spec || !spec->window || !spectrum::spec_ok(spec->size, spec->hop, spec->bands, spec->band_first, spec->band_count) || (spec->bands && !spec->weights))
+        return elemhip::kInvalidPropertyValue;
+    if (j1 < j0 || (channels && (!tail || !sums || (frames && !planar) || (j1 > j0 && !out))) || (frames > stride && channels > 1u)) return elemhip::kInvalidInstructionFormat;
+    const uint32_t S = spec->size, B = spec->bands, P = spec->center ? S / 2u : 0u;
+    // every frame asked for must start within the carried frames and end within what zero padding may complete
+    if (j1 > j0 && ((int64_t)(j0 * spec->hop) - (int64_t)P < (int64_t)n0 - (int64_t)(S - 1u))) return elemhip::kInvalidPropertyValue;
+    std::vector<double> tw(2u * S);
+    ffr::make_twiddles(S, reinterpret_cast<ffr::c2*>(tw.data()));
+    std::vector<uint32_t> offset(B);
+    uint32_t nw = 0;
+    for (uint32_t b = 0; b < B; ++b) { offset[b] = nw; nw += spec->band_count[b]; }
+    const spectrum::Plan p{S, spec->hop, P, B ? B : S / 2u + 1u, B, spec->window, tw.data(), spec->band_first, spec->band_count, offset.data(), spec->weights};
+    for (uint32_t c = 0; c < channels; ++c)
+        spectrum::analyse_host(p, tail + (size_t)c * (S - 1u), planar + (size_t)c * stride, frames, n0, j0, j1, out + (size_t)c * (size_t)(j1 - j0) * p.cols, sums + (size_t)c * p.cols);
+    return elemhip::kOk;
+}
+
+uint64_t elemhip_spectrum_launches(void) { return elemhip::spectrum_launches(); }
+
 int elemhip_process_blocks_flac(elemhip_t* h, const void* const* inStreams, size_t nInStreams, const elemhip_pcm_in_spec* inSpec,
                                 void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams, const elemhip_flac_spec* spec,
                                 size_t numFrames, int64_t st, elemhip_pcm_channel_stats* stats) {

@@ -194,6 +194,7 @@ Engine::~Engine() {
     inputResampleFree();
     limiterFree();
     noiseShapeFree();
+    spectrumFree(true);
     flacFree();
     flacInFree();
     if (ioStream) (void)hipStreamDestroy(ioStream);

@@ -32,6 +32,7 @@
 #include "flac_decode.h"
 #include "flac_md5.h"
 #include "noise_shape.h"
+#include "spectrum.h"
 
 namespace elemhip {
 
@@ -307,6 +308,24 @@ public:
     int noiseShapeRead(NoiseShapeInfo* info, int32_t* cq, uint64_t* saturated, size_t capacity);
     int noiseShapeReset();
     int noiseShapeAfter(int rc);      // behind a packed delivery call: a call that failed, wherever it did, starts a new programme; returns rc
+    // Spectrum analyser (spectrum.h; off by default: no launch, no buffer, not one byte differs): with a spec set, what processBlocksHost /
+    // Pcm / PcmIo / Flac deliver — behind the converter and the limiter, the floats the meter reads, before any quantisation — is framed
+    // per channel (frame j = programme frames [j hop - P, j hop - P + size), P = size / 2 when centred, zeros outside the programme),
+    // windowed and transformed behind every launch set's last level (spectrum.hip; the header's scalar twin where those calls render
+    // host block by host block) into power spectra (size / 2 + 1 columns) or band sums (`bands` rows of first bin, count and `count`
+    // float weights, the weights of all rows behind one another). Frames leave when their last sample was delivered and queue up on the
+    // host until spectrumRead drains them; spectrumFlush pads with zeros and ends the programme: the next analysed call starts a new
+    // one, as do spectrumReset, a call with another channel count and a call that fails — and a new programme drops what was not read.
+    // A null spec turns the analyser off. A spec that is refused (spectrum::spec_ok) changes nothing.
+    struct SpectrumSpec { uint32_t size, hop, center, bands; const double* window; const uint32_t* bandFirst; const uint32_t* bandCount; const float* weights; };
+    struct SpectrumInfo { uint32_t channels, columns, size, hop, center, bands, flushed, reserved; uint64_t firstFrame, queued, frames, delivered; };
+    int spectrumSet(const SpectrumSpec* spec);
+    // info.queued frames from info.firstFrame on wait in the queue. `out` (null: nothing is drained), `capacity` floats: receives
+    // [channel][queued][columns] and the queue is emptied (too small: kInvalidPropertyValue, nothing drained). `sums` (null, or
+    // `sumCapacity` doubles): [channel][columns], the running sums over every frame emitted so far. The programme is not disturbed.
+    int spectrumRead(SpectrumInfo* info, float* out, size_t capacity, double* sums, size_t sumCapacity);
+    int spectrumFlush();
+    int spectrumReset();
     // FLAC delivery (flac_encode.h; options "flac_frame" 256 .. 4096, default 4096, "flac_bits" 16 / 24, "flac_lpc_order" 0 .. 12 and "flac_md5" 0 / 1): the host-buffer render
     // delivered as RFC 9639 frames of a fixed block size, encoded on the GPU in the pack kernel's place (flac_encode.hip) — behind the
     // converter and the limiter, next to the meter. The sample values are processBlocksPcm's codes for the same render. The programme is
@@ -500,6 +519,24 @@ private:
     double* dLoudSeg = nullptr; double* dLoudEnergy = nullptr; size_t loudSegCap = 0, loudSegChannels = 0;
     double* dLoudOut[2] = {nullptr, nullptr}; double* hLoudOut[2] = {nullptr, nullptr}; size_t loudOutStride = 0, loudOutChannels = 0;
     uint32_t loudCountOf[2] = {0, 0};      // sub-blocks the set in each half completed
+    // spectrum analyser (spectrumSet): the tables on both sides; per channel two copies of the last size - 1 delivered frames and the
+    // running sums on the device; per half the frames a set completes (device, pinned); the emitted frames nobody has read yet
+    bool spcOn = false, spcFlushed = false;
+    spectrum::Plan spcPlan{}, spcPlanDev{};          // host pointers (the vectors below) / device pointers (dSpcTables)
+    uint32_t spcCenter = 0;
+    std::vector<double> spcWindow, spcTwiddles; std::vector<uint32_t> spcBandIdx; std::vector<float> spcWeights;
+    unsigned char* dSpcTables = nullptr;
+    uint32_t spcChannels = 0;              // channels of the programme (0: none yet)
+    uint64_t spcFrames = 0, spcEmitted = 0;         // programme frames delivered / analyser frames emitted so far
+    float* dSpcTail[2] = {nullptr, nullptr}; int spcTailCur = 0; double* dSpcSums = nullptr; size_t spcStateCap = 0;
+    float* dSpcOut[2] = {nullptr, nullptr}; float* hSpcOut[2] = {nullptr, nullptr}; size_t spcOutCap = 0, spcOutChannels = 0;   // (cap: frames per channel)
+    uint32_t spcCountOf[2] = {0, 0};       // frames the set in each half completed
+    std::vector<std::vector<float>> spcQueue; uint64_t spcQueueFirst = 0;      // [channel]: frames x columns; the index of the first one
+    static constexpr size_t kSpcHalfBytes = 256u << 20;                       // the most a pinned half may hold
+    size_t spectrumSetFrames(size_t deliveredFrames) const { return deliveredFrames / spcPlan.hop + 2; }     // frames a set of that many completes at most
+    int ensureSpectrum(size_t channels, size_t setFrames);      // (`mu` held) a programme of `channels`; halves for sets of `setFrames` (0: none)
+    int spectrumResetLocked(size_t channels);
+    void spectrumFree(bool tables);
     int ensureLoudness(size_t channels, size_t setFrames);      // (`mu` held, both streams idle)
     int loudnessResetLocked(size_t channels);
     void loudnessFree();
@@ -677,6 +714,7 @@ private:
         bool meter, resamp, limit, inres;               // options "loudness_meter", "resample_rate", "limiter", "input_rate" apply to this call
         resample::Plan rp, inp; limiter::Plan lmp;
         bool shape; uint32_t shapeBits, shapeDither, shapeSeed;      // noiseShapeSet applies to this call: s16 / s24 / FLAC delivery
+        bool spectrum;                                  // spectrumSet applies to this call
         uint32_t inG, inFmt; size_t inStreams, inB;     // the inputs as streams: planar floats count as nIn one-channel float streams
         const unsigned char* inStream(size_t s) const { return src ? static_cast<const unsigned char*>(src->streams[s]) : reinterpret_cast<const unsigned char*>(in[s]); }
     };

@@ -34,6 +34,7 @@ struct Engine::HostCarry {
     std::vector<std::vector<int32_t>> flacCodes;        // FLAC delivery: the open frame's codes per channel
     std::vector<flac_md5::Record> flacMd5;              // ... and, with option "flac_md5", the streams' running digests
     std::vector<noise_shape::ChannelState> shapeState;  // noise-shaped requantisation: the channels' errors
+    std::vector<float> spcTail; std::vector<double> spcSums;      // the spectrum analyser: the carried frames, the running sums
     std::vector<Carried> stages;
     size_t opened = 0;                                  // stages [0, opened) are open
 
@@ -68,6 +69,13 @@ struct Engine::HostCarry {
                       if (!flacMd5.empty()) s.push_back({flacMd5.data(), e.dFlacMd5, flacMd5.size() * sizeof(flac_md5::Record)});
                       return s; },
              Carried::kNothing, nullptr, [this] { e.flacOpen = (uint32_t)flacCodes[0].size(); }},
+            // the spectrum analyser: the carried frames and the running sums; a failed call starts a new programme
+            {c.spectrum, [this] { const int rc = e.ensureSpectrum(c.nOut, 0);
+                                  if (rc == kOk) { spcTail.resize(c.nOut * (size_t)(e.spcPlan.size - 1u)); spcSums.resize(c.nOut * (size_t)e.spcPlan.cols); }
+                                  return rc; },
+             [this] { return std::vector<Span>{{spcTail.data(), e.dSpcTail[e.spcTailCur], spcTail.size() * sizeof(float)},
+                                               {spcSums.data(), e.dSpcSums, spcSums.size() * sizeof(double)}}; },
+             Carried::kReset, [this] { return e.spectrumResetLocked(e.spcChannels); }, nullptr},
         };
     }
 
@@ -153,10 +161,10 @@ int Engine::renderHostBlocks(const HostCall& c) {
     const float* const* in = c.in; float* const* out = c.out;
     const size_t nIn = c.nIn, nOut = c.nOut, hb = c.hb, numFrames = c.numFrames;
     const PcmSource* src = c.src; PcmJob* pcm = c.pcm;
-    const bool staged = c.packed || c.meter || c.resamp || c.limit;      // every host block renders into tailOut: a stage reads it there
+    const bool staged = c.packed || c.meter || c.resamp || c.limit || c.spectrum;      // every host block renders into tailOut: a stage reads it there
     std::vector<const float*> ip(nIn);
     std::vector<float*> op(nOut);
-    std::vector<float> tailIn, tailOut, inX, resOut, limOut;
+    std::vector<float> tailIn, tailOut, inX, resOut, limOut, spcOut;
     std::vector<int32_t> shaped;
     std::vector<uint8_t*> sp(pcm ? pcm->nStreams : 0);
     std::vector<const unsigned char*> srcAt(src ? src->nStreams : 0);
@@ -234,6 +242,19 @@ int Engine::renderHostBlocks(const HostCall& c) {
             for (size_t ch = 0; ch < nOut; ++ch)
                 loudness::meter_host(loudPlan, carry.meterState[ch], got + ch * gotStride, nd, loudFrames, [&](double ms) { loudSeries[ch].push_back(ms); });
             loudFrames += nd;
+        }
+        if (c.spectrum && nd) {
+            // the floats are on the host: the header's scalar twin frames and transforms them — the kernel's phases, thread by thread
+            std::lock_guard<std::mutex> lock(mu);
+            const spectrum::Plan& sp = spcPlan;
+            const uint64_t j0 = spcEmitted, j1 = spectrum::frames_complete(spcFrames + nd, sp.size, sp.hop, sp.pad);
+            spcOut.resize((size_t)(j1 - j0) * sp.cols);
+            for (size_t ch = 0; ch < nOut; ++ch) {
+                spectrum::analyse_host(sp, carry.spcTail.data() + ch * (sp.size - 1u), got + ch * gotStride, nd, spcFrames, j0, j1, spcOut.data(),
+                                       carry.spcSums.data() + ch * sp.cols);
+                spcQueue[ch].insert(spcQueue[ch].end(), spcOut.begin(), spcOut.end());
+            }
+            spcFrames += nd; spcEmitted = j1;
         }
         if (c.shape && nd) {
             // the floats are on the host: the header's scalar loop quantises all nd of them — the kernel's functions, the kernel's bits

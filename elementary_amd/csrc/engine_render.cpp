@@ -1251,6 +1251,7 @@ Engine::HostCall Engine::hostCall(const float* const* in, size_t nIn, float* con
     c.shapeBits = flac ? flac->spec.bits : c.pcmFmt == pcm_pack::S16 ? 16u : 24u;
     c.shapeDither = flac ? (flac->spec.dither ? 1u : 0u) : pcm ? (pcm->spec.dither ? 1u : 0u) : 0u;
     c.shapeSeed = flac ? flac->spec.seed : pcm ? pcm->spec.seed : 0u;
+    c.spectrum = spcOn && nOut > 0;         // spectrumSet: the delivered frames of every set go through the analyser, next to the meter
     // option "input_rate": the inputs — planar floats or streams — arrive at another rate and are converted to the engine's in front of
     // the render; a call of numFrames ENGINE frames pulls the input frames [inputs_before(n0), inputs_before(n0 + numFrames)) of the
     // programme. Planar floats count as nIn one-channel float streams: one path for both.
@@ -1270,6 +1271,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
     if (tapSlices) return renderHostBlocks(call);     // (taps under a host block longer than the engine's: engine_host_blocks.cpp)
     // the launch-set loop, under the names it has always read the call by
     const bool flacSrc = call.flacSrc, wantFloat = call.wantFloat, packed = call.packed, meter = call.meter, resamp = call.resamp, limit = call.limit, inres = call.inres, shape = call.shape;
+    const bool spectrum = call.spectrum;
     const uint32_t flacInB = call.flacInB, srcG = call.srcG, srcFmt = call.srcFmt, pcmG = call.pcmG, pcmFmt = call.pcmFmt, inG = call.inG, inFmt = call.inFmt;
     const size_t srcB = call.srcB, pcmB = call.pcmB, inStreams = call.inStreams, inB = call.inB;
     const resample::Plan rp = call.rp, inp = call.inp;
@@ -1289,7 +1291,15 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         // launch sets hold whole HOST blocks: a newer render sequence is adopted at a set boundary (enqueueBlocks), and the reference
         // swaps sequences at host-block boundaries only (Runtime.h:277-285)
         if (hb > bs) setBlocks = std::min(numBlocks, std::max(hb / bs, setBlocks / (hb / bs) * (hb / bs)));
-        outCapFrames = resamp ? (size_t)resample::ceil_div((uint64_t)(setBlocks * bs) * rp.L, rp.M) + 1 : setBlocks * bs;
+        auto deliveredBy = [&](size_t blocks) { return resamp ? (size_t)resample::ceil_div((uint64_t)(blocks * bs) * rp.L, rp.M) + 1 : blocks * bs; };
+        if (spectrum) {
+            // the frames one set completes must fit a pinned half: the largest whole number of host blocks whose frames do
+            const size_t per = std::max<size_t>(hb / bs, 1), frameBytes = nOut * spcPlan.cols * sizeof(float);
+            auto fits = [&](size_t blocks) { return spectrumSetFrames(deliveredBy(blocks)) <= kSpcHalfBytes / frameBytes; };
+            while (setBlocks > per && !fits(setBlocks)) setBlocks = std::max(per, (setBlocks - 1) / per * per);
+            if (!fits(setBlocks)) return kInvalidPropertyValue;
+        }
+        outCapFrames = deliveredBy(setBlocks);
         outCapBlocks = (outCapFrames + bs - 1) / bs;
         int rc = ensureHostStaging(std::max(setBlocks, outCapBlocks) * std::max<size_t>(nOut, 1) * bs, setBlocks * std::max<size_t>(nIn, 1) * bs);
         if (rc != kOk) return rc;
@@ -1335,6 +1345,10 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         }
         if (meter) {
             rc = ensureLoudness(nOut, outCapFrames);
+            if (rc != kOk) return rc;
+        }
+        if (spectrum) {
+            rc = ensureSpectrum(nOut, spectrumSetFrames(outCapFrames));
             if (rc != kOk) return rc;
         }
         if (flac) {
@@ -1402,7 +1416,14 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         for (size_t c = 0; c < nOut; ++c)
             for (uint32_t j = 0; j < loudCountOf[k & 1]; ++j) loudSeries[c].push_back(sums[c * loudOutStride + j] / (double)loudPlan.hop);
     };
+    auto deliverSpectrum = [&](size_t k) {   // the frames set k completed -> the queue spectrumRead drains
+        const size_t count = spcCountOf[k & 1], cols = spcPlan.cols;
+        const float* frames = hSpcOut[k & 1];
+        std::lock_guard<std::mutex> lock(mu);
+        for (size_t c = 0; c < nOut && count; ++c) spcQueue[c].insert(spcQueue[c].end(), frames + c * count * cols, frames + (c + 1) * count * cols);
+    };
     auto deliver = [&](size_t k) { if (wantFloat) { if (resamp) scatterConverted(k); else scatter(k); } if (pcm) deliverPcm(k); if (meter) deliverLoudness(k);
+                                  if (spectrum) deliverSpectrum(k);
                                   if (flac && flacRc == kOk) flacRc = flacDeliver(*flac, (int)(k & 1)); };
     int result = kOk;
     size_t issued = 0, scattered = 0, outOff = 0;
@@ -1619,6 +1640,24 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 HOST_TRY(launch_loudness(stream, a));
                 loudFrames += valid;
             }
+            if (spectrum) {
+                // the analyser's kernels behind the set's last level too, next to the meter: they read the same block. One copy of the
+                // carried frames is read, the carry step writes the other; the sums are added to in place by this stream's kernels
+                // only; the frames this set completes go to this half's region, drained by the D2H of set k - 2 (evOut above).
+                SpectrumArgs a{};
+                a.src = got; a.tailIn = dSpcTail[spcTailCur]; a.tailOut = dSpcTail[spcTailCur ^ 1]; a.out = dSpcOut[half]; a.sums = dSpcSums;
+                a.n0 = spcFrames; a.j0 = spcEmitted;
+                a.numFrames = (uint32_t)(spectrum::frames_complete(spcFrames + valid, spcPlan.size, spcPlan.hop, spcPlan.pad) - spcEmitted);
+                a.validFrames = (uint32_t)valid; a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nOut; a.updateTail = valid ? 1u : 0u;
+                a.plan = spcPlanDev;
+                if (a.numFrames > spcOutCap) { result = kInvariantViolation; break; }       // (sized above for the largest set)
+                spcCountOf[half] = a.numFrames;
+                if (valid) {
+                    HOST_TRY(launch_spectrum(stream, a));
+                    spcTailCur ^= 1;
+                    spcFrames += valid; spcEmitted += a.numFrames;
+                }
+            }
             HOST_TRY(hipEventRecord(evRendered[half], stream));
             HOST_TRY(hipStreamWaitEvent(ioStream, evRendered[half], 0));
             if (flacSrc) HOST_TRY(hipMemcpyAsync(hFlacInErr + half, dFlacInErr + half, sizeof(FlacInError), hipMemcpyDeviceToHost, ioStream));   // the decode's error record
@@ -1630,6 +1669,8 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 HOST_TRY(hipMemcpyAsync(hPcm[half] + flac->statsOff, dPcm[half] + flac->statsOff, nOut * sizeof(pcm_pack::ChannelStats), hipMemcpyDeviceToHost, ioStream));
             }
             if (meter && loudCountOf[half]) HOST_TRY(hipMemcpyAsync(hLoudOut[half], dLoudOut[half], nOut * loudOutStride * sizeof(double), hipMemcpyDeviceToHost, ioStream));
+            if (spectrum && spcCountOf[half])
+                HOST_TRY(hipMemcpyAsync(hSpcOut[half], dSpcOut[half], nOut * spcCountOf[half] * spcPlan.cols * sizeof(float), hipMemcpyDeviceToHost, ioStream));
             HOST_TRY(hipEventRecord(evOut[half], ioStream));
             issued = k + 1;
         }
@@ -1658,6 +1699,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         freeDeferred();
         // a metered call that failed may have advanced the carried state past sets whose sums never arrived: the programme starts anew
         if (meter && result != kOk) (void)loudnessResetLocked(loudChannels);
+        if (spectrum && result != kOk) (void)spectrumResetLocked(spcChannels);      // the same for the analyser's
         if (resamp && result != kOk) (void)resampleResetLocked(0);      // likewise: the clock may be ahead of what was delivered
         if (limit && result != kOk) (void)limiterResetLocked(0);
         if (shape && result != kOk) (void)noiseShapeResetLocked();

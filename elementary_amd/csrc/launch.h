@@ -9,6 +9,7 @@
 #include "flac_decode.h"
 #include "flac_md5.h"
 #include "noise_shape.h"
+#include "spectrum.h"
 
 namespace elemhip {
 
@@ -108,6 +109,19 @@ struct LoudnessArgs {
     loudness::Plan  plan;
 };
 hipError_t launch_loudness(hipStream_t s, const LoudnessArgs& a);
+// ---- spectrum analyser (spectrum.hip): behind a launch set's last level, next to the meter, spectrum.h ----
+struct SpectrumArgs {
+    const float*    src;            // the set's output, [block][numChannels][blockSize] (not read where validFrames = 0: a flush)
+    const float*    tailIn;         // [numChannels][size - 1]: the programme's frames in front of the set, oldest first
+    float*          tailOut;        // the other copy: receives the frames in front of the NEXT set (updateTail)
+    float*          out;            // [numChannels][numFrames][cols]: the frames this set completes
+    double*         sums;           // [numChannels][cols]: the running sums, added into in frame order
+    uint64_t        n0, j0;         // the programme's delivered frames and emitted frames at the set's start
+    uint32_t        numFrames, validFrames, blockSize, numChannels, updateTail;
+    spectrum::Plan  plan;           // (device pointers)
+};
+hipError_t launch_spectrum(hipStream_t s, const SpectrumArgs& a);
+uint64_t spectrum_launches();       // kernels launched by this process so far
 // ---- delivery-rate conversion (resample.hip): behind a launch set's last level, in front of the pack kernel and the meter, resample.h ----
 struct ResampleArgs {
     const float*    src;            // the set's output, [block][numChannels][blockSize]: validIn frames at the engine's rate

@@ -131,6 +131,21 @@ def load_library() -> C.CDLL:
         lib.elemhip_noise_shape_host.argtypes = [_fp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_int64, _fp, C.c_uint32, C.c_size_t,
                                                  C.c_size_t, _u8p, _i32p]
         lib.elemhip_noise_shape_host.restype = C.c_int
+        _spp = C.POINTER(_SpectrumSpec)
+        lib.elemhip_spectrum_set.argtypes = [C.c_void_p, _spp]
+        lib.elemhip_spectrum_set.restype = C.c_int
+        lib.elemhip_spectrum_read.argtypes = [C.c_void_p, C.POINTER(_SpectrumInfo), _fp, C.c_size_t, _dp, C.c_size_t]
+        lib.elemhip_spectrum_read.restype = C.c_int
+        lib.elemhip_spectrum_flush.argtypes = [C.c_void_p]
+        lib.elemhip_spectrum_flush.restype = C.c_int
+        lib.elemhip_spectrum_reset.argtypes = [C.c_void_p]
+        lib.elemhip_spectrum_reset.restype = C.c_int
+        lib.elemhip_spectrum_frames.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_int]
+        lib.elemhip_spectrum_frames.restype = C.c_uint64
+        lib.elemhip_spectrum_host.argtypes = [_spp, _fp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, _fp, _dp, _fp]
+        lib.elemhip_spectrum_host.restype = C.c_int
+        lib.elemhip_spectrum_launches.argtypes = []
+        lib.elemhip_spectrum_launches.restype = C.c_uint64
         lib.elemhip_flac_index.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p, C.c_size_t, _szp]
         lib.elemhip_flac_index.restype = C.c_int
         lib.elemhip_flac_decode.argtypes = [C.POINTER(_FlacIn), C.c_size_t, C.POINTER(C.POINTER(C.c_int32)), _szp, _u32p]
@@ -246,6 +261,101 @@ def noise_shape_host(coeffs, x, bits: int = 16, dither_seed: Optional[int] = Non
         err.code = rc
         raise err
     return codes, st
+
+
+class _SpectrumSpec(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("hop", C.c_uint32), ("center", C.c_uint32), ("bands", C.c_uint32), ("window", C.POINTER(C.c_double)),
+                ("band_first", C.POINTER(C.c_uint32)), ("band_count", C.POINTER(C.c_uint32)), ("weights", C.POINTER(C.c_float))]
+
+
+class _SpectrumInfo(C.Structure):
+    _fields_ = [("channels", C.c_uint32), ("columns", C.c_uint32), ("size", C.c_uint32), ("hop", C.c_uint32), ("center", C.c_uint32),
+                ("bands", C.c_uint32), ("flushed", C.c_uint32), ("reserved", C.c_uint32), ("first_frame", C.c_uint64), ("queued", C.c_uint64),
+                ("frames", C.c_uint64), ("delivered", C.c_uint64)]
+
+
+def _spectrum_spec(size: int, hop: int, window="hann", bands=None, center: bool = False):
+    """``(spec, keep)``: the C struct of an analyser spec and the arrays it points into (keep them alive for the call)."""
+    import numpy as np
+    from . import spectrum as sp
+    if isinstance(window, str):
+        if int(size) not in sp.SIZES:          # (the engine refuses the size; a table of some length lets it say so)
+            win = np.ones(max(int(size), 1), dtype=np.float64)
+        else:
+            win = sp.window(window, int(size))
+    else:
+        win = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+        if win.size != int(size):
+            raise ValueError(f"the window holds {win.size} values, the size is {size}")
+    win = np.ascontiguousarray(win, dtype=np.float64)
+    spec = _SpectrumSpec()
+    spec.size, spec.hop, spec.center = int(size), int(hop), 1 if center else 0
+    spec.window = win.ctypes.data_as(C.POINTER(C.c_double))
+    keep = [win]
+    if bands is not None:
+        first, count, weights = sp.pack_rows(bands)
+        if first.size == 0:
+            raise ValueError("bands: at least one row (None: power mode)")
+        if weights.size == 0:
+            weights = np.zeros(1, dtype=np.float32)
+        spec.bands = int(first.size)
+        spec.band_first = first.ctypes.data_as(C.POINTER(C.c_uint32))
+        spec.band_count = count.ctypes.data_as(C.POINTER(C.c_uint32))
+        spec.weights = weights.ctypes.data_as(C.POINTER(C.c_float))
+        keep += [first, count, weights]
+    return spec, keep
+
+
+def spectrum_frames(size: int, hop: int, center: bool, delivered: int, flushed: bool = False) -> int:
+    """``elemhip_spectrum_frames``: the analyser frames out after ``delivered`` programme frames, or after a flush behind them."""
+    return int(load_library().elemhip_spectrum_frames(int(size), int(hop), 1 if center else 0, int(delivered), 1 if flushed else 0))
+
+
+def spectrum_launches() -> int:
+    """``elemhip_spectrum_launches``: analyser kernels this process has launched so far (an engine whose analyser is off adds none)."""
+    return int(load_library().elemhip_spectrum_launches())
+
+
+def spectrum_host(x, size: int, hop: int, window="hann", bands=None, center: bool = False, flush: bool = True, state=None):
+    """``elemhip_spectrum_host``: the scalar twin of the analyser's kernels, pure host arithmetic — ``x`` float32 ``[channels, frames]``
+    delivered behind the programme ``state`` describes (None: a programme's start) -> ``(frames, sums, state)``: float32
+    ``[channels, n, columns]``, float64 ``[channels, columns]`` and the carried state, a dict of ``tail`` float32
+    ``[channels, size - 1]``, ``sums``, ``delivered`` and ``emitted``. With ``flush`` the frames zero padding completes are included and
+    the returned state is None."""
+    import numpy as np
+    lib = load_library()
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    if a.ndim == 1:
+        a = a[None, :]
+    ch, n = a.shape
+    spec, keep = _spectrum_spec(size, hop, window, bands, center)
+    cols = int(spec.bands) if spec.bands else int(size) // 2 + 1
+    fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+
+    def call(planar, frames, n0, j0, j1, tail, sums):
+        out = np.zeros((ch, max(j1 - j0, 0), cols), dtype=np.float32)
+        rc = lib.elemhip_spectrum_host(C.byref(spec), planar.ctypes.data_as(fp) if frames else None, ch, max(n, 1), frames, n0, j0, j1,
+                                       tail.ctypes.data_as(fp), sums.ctypes.data_as(dp), out.ctypes.data_as(fp))
+        if rc != 0:
+            err = ElemHipError(f"elemhip_spectrum_host failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return out
+
+    if state is None:
+        tail, sums, n0, j0 = np.zeros((ch, int(size) - 1), dtype=np.float32), np.zeros((ch, cols), dtype=np.float64), 0, 0
+    else:
+        tail = np.array(state["tail"], dtype=np.float32).reshape(ch, int(size) - 1)
+        sums = np.array(state["sums"], dtype=np.float64).reshape(ch, cols)
+        n0, j0 = int(state["delivered"]), int(state["emitted"])
+    j1 = spectrum_frames(size, hop, center, n0 + n)
+    parts = [call(a, n, n0, j0, j1, tail, sums)]
+    if flush:
+        j2 = spectrum_frames(size, hop, center, n0 + n, True)
+        parts.append(call(a, 0, n0 + n, j1, j2, tail, sums))
+    frames = np.concatenate(parts, axis=1)
+    del keep
+    return frames, sums, (None if flush else {"tail": tail, "sums": sums, "delivered": n0 + n, "emitted": j1})
 
 
 class FlacMd5:
@@ -982,6 +1092,55 @@ class Runtime(CRuntime):
             err = ElemHipError(f"elemhip_noise_shape_reset failed: {describe(rc)} (code {rc})")
             err.code = rc
             raise err
+
+    def _spectrum_check(self, what: str, rc: int) -> None:
+        if rc != 0:
+            err = ElemHipError(f"{what} failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+
+    def spectrum(self, size: Optional[int], hop: Optional[int] = None, window="hann", bands=None, center: bool = False) -> None:
+        """``elemhip_spectrum_set``: analyse what the host-buffer render calls deliver as STFT frames of ``size`` (256 .. 4096) every
+        ``hop`` (1 .. size; default ``size / 4``) frames — power spectra (``size / 2 + 1`` columns), or with ``bands`` (rows of
+        ``(first_bin, weights)``, at most 512; ``elementary_amd.spectrum.mel_bands``) band sums. ``window``: a name
+        (``elementary_amd.spectrum.window``) or ``size`` float64 values. ``center``: frame j is centred on programme frame ``j * hop``.
+        ``size`` None turns the analyser off (the default). Starts a new programme. A spec the engine refuses raises with ``.code`` 6
+        and changes nothing."""
+        if size is None:
+            return self._spectrum_check("elemhip_spectrum_set", self._lib.elemhip_spectrum_set(self._h, None))
+        spec, keep = _spectrum_spec(size, int(size) // 4 if hop is None else hop, window, bands, center)
+        rc = self._lib.elemhip_spectrum_set(self._h, C.byref(spec))
+        del keep
+        self._spectrum_check("elemhip_spectrum_set", rc)
+
+    def spectrum_read(self, sums: bool = True) -> Dict[str, Any]:
+        """``elemhip_spectrum_read``: drains the frames emitted since the last read — ``frames`` float32 ``[channels, n, columns]``,
+        ``first_frame`` (the programme index of ``frames[:, 0]``), ``sums`` float64 ``[channels, columns]`` (the running sums over every
+        frame emitted so far), ``frames_total``, ``delivered`` (programme frames analysed), ``flushed``, and the spec (``size``, ``hop``,
+        ``center``, ``bands``). The programme is not disturbed. Raises on an engine whose analyser is off."""
+        import numpy as np
+        info = _SpectrumInfo()
+        self._spectrum_check("elemhip_spectrum_read", self._lib.elemhip_spectrum_read(self._h, C.byref(info), None, 0, None, 0))
+        ch, n, cols = int(info.channels), int(info.queued), int(info.columns)
+        frames = np.zeros((ch, n, cols), dtype=np.float32)
+        acc = np.zeros((ch, cols), dtype=np.float64)
+        buf = np.zeros(max(frames.size, 1), dtype=np.float32)
+        rc = self._lib.elemhip_spectrum_read(self._h, C.byref(info), buf.ctypes.data_as(C.POINTER(C.c_float)), buf.size,
+                                             acc.ctypes.data_as(C.POINTER(C.c_double)) if (sums and acc.size) else None, acc.size)
+        self._spectrum_check("elemhip_spectrum_read", rc)
+        frames[...] = buf[:frames.size].reshape(frames.shape)
+        return {"frames": frames, "first_frame": int(info.first_frame), "sums": acc, "frames_total": int(info.frames),
+                "delivered": int(info.delivered), "flushed": bool(info.flushed), "channels": ch, "columns": cols, "size": int(info.size),
+                "hop": int(info.hop), "center": bool(info.center), "bands": int(info.bands)}
+
+    def spectrum_flush(self) -> None:
+        """``elemhip_spectrum_flush``: pads the programme with zeros, emits the frames that completes and ends it; the next analysed call
+        starts a new programme (read first: a new programme drops what was not read)."""
+        self._spectrum_check("elemhip_spectrum_flush", self._lib.elemhip_spectrum_flush(self._h))
+
+    def spectrum_reset(self) -> None:
+        """``elemhip_spectrum_reset``: a new programme; what was pending is dropped."""
+        self._spectrum_check("elemhip_spectrum_reset", self._lib.elemhip_spectrum_reset(self._h))
 
     def event_window_blocks(self) -> int:
         """Blocks a ``process_queued_events(blockwise=True)`` window may span and still equal a relay after every block."""

@@ -263,6 +263,45 @@ size_t elemhip_noise_shape_state_bytes(void);
 int elemhip_noise_shape_host(const float* coeffs, uint32_t count, uint32_t bits, int dither, uint32_t seed, uint32_t channel0, int64_t time0,
                              const float* planar, uint32_t channels, size_t stride, size_t frames, uint8_t* state, int32_t* codes);
 
+/* EXTENSION (no counterpart in the reference): a spectrum analyser on what elemhip_process_blocks_host / _pcm / _pcm_io / _flac deliver,
+ * on the GPU (elementary_amd/csrc/spectrum.hip; the arithmetic: spectrum.h) — behind the delivery-rate converter and the limiter, on the
+ * floats the loudness meter reads, before any quantisation. Per channel, frame j covers the delivered programme frames
+ * [j hop - P, j hop - P + size), zeros outside the programme: size 256, 512, 1024, 2048 or 4096, hop 1 .. size, P = size / 2 with
+ * `center`, else 0. A sample times window[i] (`size` doubles, the caller's) is rounded once, in double; the real FFT runs in double;
+ * the power is re^2 + im^2. bands = 0: size / 2 + 1 power columns per frame, rounded to float once. bands = 1 .. 512: band_first[b],
+ * band_count[b] (0 allowed; first + count <= size / 2 + 1) and the rows' float weights behind one another in `weights`; a column is
+ * the weighted sum of the row's bin powers, in double, in ascending bin order, rounded to float once. No logarithm is taken. The bits
+ * do not depend on how the programme is cut into calls and launch sets. Code 6, and nothing changes, for a spec out of these ranges
+ * (dry handles validate too); a NULL spec, the default, turns the analyser off: no launch, no buffer, not one byte differs.
+ * A frame is emitted once its last sample was delivered: after n frames, elemhip_spectrum_frames(size, hop, center, n, 0) are out.
+ * The programme is the frames those calls delivered since the spec was set, elemhip_spectrum_reset or a flush; a call of another
+ * channel count, and a call that fails, start a new one; a new programme drops the frames nobody read.
+ *   elemhip_spectrum_read    info: channels, columns, the spec, `queued` frames waiting from index first_frame on, the frames emitted
+ *                            and the frames delivered so far. out (NULL: nothing is drained; else `capacity` floats, code 6 when too
+ *                            few): [channel][queued][columns], and the queue is emptied. sums (NULL, or sumCapacity doubles):
+ *                            [channel][columns], the float64 sum of every column over the frames emitted so far, in frame order —
+ *                            the long-term average spectrum times `frames`. The programme is not disturbed.
+ *   elemhip_spectrum_flush   pads with zeros and ends the programme: the total becomes elemhip_spectrum_frames(size, hop, center, n, 1)
+ *                            — centred 1 + n / hop, else the least count that covers every sample; n = 0 emits nothing. The next
+ *                            analysed call starts a new programme.
+ *   elemhip_spectrum_reset   a new programme; what was pending is dropped
+ *   elemhip_spectrum_host    the scalar twin on plain arrays, no handle: `planar` [channels] rows `stride` floats apart, `frames` frames
+ *                            delivered behind programme frame n0; tail: [channels][size - 1] floats in-out (zero at a programme's
+ *                            start); sums: [channels][columns] doubles in-out; frames [j0, j1) go to out [channels][j1 - j0][columns]
+ *   elemhip_spectrum_launches  analyser kernels this process has launched so far */
+typedef struct elemhip_spectrum_spec { uint32_t size, hop, center, bands; const double* window; const uint32_t* band_first; const uint32_t* band_count;
+                                       const float* weights; } elemhip_spectrum_spec;
+typedef struct elemhip_spectrum_info { uint32_t channels, columns, size, hop, center, bands, flushed, reserved;
+                                       uint64_t first_frame, queued, frames, delivered; } elemhip_spectrum_info;
+int elemhip_spectrum_set(elemhip_t*, const elemhip_spectrum_spec* spec);
+int elemhip_spectrum_read(elemhip_t*, elemhip_spectrum_info* info, float* out, size_t capacity, double* sums, size_t sumCapacity);
+int elemhip_spectrum_flush(elemhip_t*);
+int elemhip_spectrum_reset(elemhip_t*);
+uint64_t elemhip_spectrum_frames(uint32_t size, uint32_t hop, int center, uint64_t deliveredFrames, int flushed);
+int elemhip_spectrum_host(const elemhip_spectrum_spec* spec, const float* planar, uint32_t channels, size_t stride, size_t frames, uint64_t n0,
+                          uint64_t j0, uint64_t j1, float* tail, double* sums, float* out);
+uint64_t elemhip_spectrum_launches(void);
+
 /* EXTENSION (no counterpart in the reference): the same render delivered as FLAC, encoded on the GPU in the pack kernel's place
  * (elementary_amd/csrc/flac_encode.hip; the arithmetic and the decision rules: flac_encode.h) — behind the delivery-rate converter and
  * the limiter, next to the meter. RFC 9639 "subset" streams of a fixed block size (option "flac_frame": 256, 512, 1024, 2048 or 4096,

@@ -167,6 +167,13 @@ public:
         return elemhip_noise_shape_read(h, info, cq, saturated, capacity);
     }
     int noiseShapeReset() { return elemhip_noise_shape_reset(h); }
+    // EXTENSION: STFT power or band spectra of what the host-buffer render calls deliver (null spec: off)
+    int spectrumSet(const elemhip_spectrum_spec* spec) { return elemhip_spectrum_set(h, spec); }
+    int spectrumRead(elemhip_spectrum_info* info, float* out, size_t capacity, double* sums, size_t sumCapacity) {
+        return elemhip_spectrum_read(h, info, out, capacity, sums, sumCapacity);
+    }
+    int spectrumFlush() { return elemhip_spectrum_flush(h); }
+    int spectrumReset() { return elemhip_spectrum_reset(h); }
     // EXTENSION: the block loop delivered as FLAC frames encoded on the GPU (elemhip_process_blocks_flac; setOption("flac_frame" /
     // "flac_bits")): inputs as processBlocksPcmIo takes them, per output stream a buffer of at least flacBound(frames delivered,
     // channels_per_stream, bits) bytes; bytesOut[s] = the bytes of the FLAC frames the call completed. flacFlush closes the programme
