@@ -18,8 +18,9 @@
 // predicated steps there, the tail, on three more clamped loads per operand, to arrive at the same bits; kTailSteps and
 // tail_active describe that schedule, and tests/native/chain_skew_host.cpp still emulates it as the reference for this one.)
 //
-// Written as plain index arithmetic for host and device alike: tests/native/chain_skew_host.cpp and chain_carry_host.cpp
-// emulate the loop with these functions and check frames, final states and load offsets without a GPU.
+// Written as plain index arithmetic for host and device alike: tests/native/chain_skew_host.cpp, chain_carry_host.cpp and
+// chain_window_host.cpp emulate the loop with these functions and check frames, final states, load offsets and store windows
+// without a GPU.
 #ifndef ELEMHIP_CHAIN_SKEW_H
 #define ELEMHIP_CHAIN_SKEW_H
 #ifndef __HIPCC_RTC__        // (the run-time compiler has no host headers: jit.cpp declares the fixed-width names)
@@ -76,6 +77,23 @@ CSKEW_FD uint32_t load_offset(uint32_t g, uint32_t q, uint32_t k, uint32_t n) {
 // 48 bytes taken off the instruction's immediate again.
 CSKEW_FD uint32_t load_bias(uint32_t k) { return store_bias(0u) - 16u * k; }
 constexpr int kLoadImmBias = -48;
+
+// Store windows. A store runs with EXEC cut to store_mask, and the switch costs the lone wave four scalar issue slots (save, narrow,
+// restore, one wait state) however many stores stand between: the loop keeps the result pieces of W consecutive groups in registers
+// (4 VGPRs per deferred group) and the group that closes a window issues all W stores under ONE switch, in group order, each at the
+// offset it always had. The groups of a span are d = 0 .. depth - 1; a window never leaves its span (window_fits), so its stores share
+// the span's scalar offset, the last window of a block closes with the block's last group — every store is issued before the state
+// hand-over and before the next block's first loads, which the deferred publish counts on — and a window of 1 is the former schedule.
+constexpr uint32_t kWindowStreamed = 4;   // loops with a streamed operand (depth 8, 4 or 2)
+constexpr uint32_t kWindowPlain = 4;      // loops without one (depth 4)
+CSKEW_FD bool window_fits(uint32_t w, uint32_t depth) { return w >= 1u && w <= depth && depth % w == 0u; }
+CSKEW_FD uint32_t window(bool streamed, uint32_t depth) {
+    return (streamed ? kWindowStreamed : kWindowPlain) < depth ? (streamed ? kWindowStreamed : kWindowPlain) : depth;
+}
+// does group d of a span close a window of w groups? ...
+CSKEW_FD bool window_closes(uint32_t d, uint32_t w) { return (d + 1u) % w == 0u; }
+// ... and the first group of that window: the closing group d stores the pieces of groups window_first(d, w) .. d
+CSKEW_FD uint32_t window_first(uint32_t d, uint32_t w) { return d + 1u - w; }
 
 } // namespace chain_skew
 

@@ -1198,16 +1198,19 @@ __device__ __forceinline__ void sout_put(const SOut& o, uint32_t t, float y) {  
 
 // A recurrence's step together with the registers it carries from frame to frame. The step lambda captures them by reference;
 // `each(g)` calls g(reg) for every one of them, so that a loop can move the state between lanes (chain_loop_q does, behind the
-// last group of a block). The other loops only call the step.
-template <typename F, typename E>
+// last group of a block). The other loops only call the step. SHORT marks a step of a couple of VALU ops and no streamed operand:
+// chain_loop_q writes such a loop out span by span (a few KB of code) and so spares it the counter and back edge, one scalar
+// instruction per 16-frame group of a loop that has 34.
+template <typename F, typename E, bool SHORT = false>
 struct ChainStep {
     F f; E each;
+    static constexpr bool kShort = SHORT;
     template <int N> __device__ __forceinline__ float operator()(const float (&x)[N]) { return f(x); }
 };
-template <typename F, typename E>
-__device__ __forceinline__ ChainStep<F, E> chain_step(F f, E each) { return ChainStep<F, E>{f, each}; }
-template <typename T> struct IsChainStep { static constexpr bool value = false; };
-template <typename F, typename E> struct IsChainStep<ChainStep<F, E>> { static constexpr bool value = true; };
+template <bool SHORT = false, typename F, typename E>
+__device__ __forceinline__ ChainStep<F, E, SHORT> chain_step(F f, E each) { return ChainStep<F, E, SHORT>{f, each}; }
+template <typename T> struct IsChainStep { static constexpr bool value = false, kShort = false; };
+template <typename F, typename E, bool SHORT> struct IsChainStep<ChainStep<F, E, SHORT>> { static constexpr bool value = true, kShort = SHORT; };
 template <typename T> struct IsChainStep<T&> : IsChainStep<T> {};
 template <typename T> struct IsChainStep<const T> : IsChainStep<T> {};
 
@@ -1257,33 +1260,57 @@ __device__ __forceinline__ void chain_store_group(const v4f_& a0, const v4f_& a1
                  : "memory");
 }
 // ---- the quad-skewed form of the loop (chain_skew.h): one 16-byte store per lane and group ---------------------------------
-// chain_store_piece / chain_store_piece_lds: the ONE store of a group — every lane of a quad its own four frames — with EXEC cut to
-// the task's 4 * count member lanes exactly as chain_store_group does it. voff already carries the lane's place inside the group.
-template <int OFF>
-__device__ __forceinline__ void chain_store_piece(const v4f_& a, uint32_t voff, __amdgpu_buffer_rsrc_t rsrc, uint32_t soff, unsigned long long mask) {
-    static_assert(OFF >= 0 && OFF < 4096, "12-bit immediate");
+// chain_store_window / chain_store_window_lds: the stores of a window of W groups (chain_skew.h) — every lane of a quad its own four
+// frames of each — with EXEC cut to the task's 4 * count member lanes exactly as chain_store_group does it, ONE switch for the W of
+// them. EXEC is saved and restored, not assumed to be all ones. voff already carries the lane's place inside a group; OFF is the
+// byte offset of the window's first group inside the span, group i of the window lies 64 * i bytes behind it.
+// Operands of the one asm statement: %0 the saved EXEC, %1 the mask, then the W pieces, their W immediates, and the address operands.
+#define CHAIN_WST_G(D, I, V, R, S) "buffer_store_dwordx4 %" #D ", %" #V ", %" #R ", %" #S " offen offset:%c" #I "\n\t"
+#define CHAIN_WST_L(D, I, V) "ds_write_b128 %" #V ", %" #D " offset:%c" #I "\n\t"
+#define CHAIN_W1(X, ...) X(2, 3, __VA_ARGS__)
+#define CHAIN_W2(X, ...) X(2, 4, __VA_ARGS__) X(3, 5, __VA_ARGS__)
+#define CHAIN_W4(X, ...) X(2, 6, __VA_ARGS__) X(3, 7, __VA_ARGS__) X(4, 8, __VA_ARGS__) X(5, 9, __VA_ARGS__)
+#define CHAIN_W8(X, ...) X(2, 10, __VA_ARGS__) X(3, 11, __VA_ARGS__) X(4, 12, __VA_ARGS__) X(5, 13, __VA_ARGS__) \
+                         X(6, 14, __VA_ARGS__) X(7, 15, __VA_ARGS__) X(8, 16, __VA_ARGS__) X(9, 17, __VA_ARGS__)
+#define CHAIN_A1 "v"(a[0]), "i"(OFF)
+#define CHAIN_A2 "v"(a[0]), "v"(a[1]), "i"(OFF), "i"(OFF + 64)
+#define CHAIN_A4 "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "i"(OFF), "i"(OFF + 64), "i"(OFF + 128), "i"(OFF + 192)
+#define CHAIN_A8 "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]), \
+                 "i"(OFF), "i"(OFF + 64), "i"(OFF + 128), "i"(OFF + 192), "i"(OFF + 256), "i"(OFF + 320), "i"(OFF + 384), "i"(OFF + 448)
+#define CHAIN_WSTORE(STORES, PIECES, ...) \
+    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\t" STORES "s_mov_b64 exec, %0\n\ts_nop 0" \
+                 : "=&s"(saved) : "s"(mask), PIECES, __VA_ARGS__ : "memory")
+template <int OFF, int W>
+__device__ __forceinline__ void chain_store_window(const v4f_ (&a)[W], uint32_t voff, __amdgpu_buffer_rsrc_t rsrc, uint32_t soff, unsigned long long mask) {
+    static_assert(W == 1 || W == 2 || W == 4 || W == 8, "the window sizes that are written out");
+    static_assert(OFF >= 0 && OFF + 64 * (W - 1) < 4096, "12-bit immediate");
     unsigned long long saved;
-    asm volatile("s_mov_b64 %0, exec\n\t"
-                 "s_mov_b64 exec, %5\n\t"
-                 "buffer_store_dwordx4 %1, %2, %3, %4 offen offset:%c6\n\t"
-                 "s_mov_b64 exec, %0\n\t"
-                 "s_nop 0"
-                 : "=&s"(saved)
-                 : "v"(a), "v"(voff), "s"(rsrc), "s"(soff), "s"(mask), "i"(OFF)
-                 : "memory");
+    if constexpr (W == 1) CHAIN_WSTORE(CHAIN_W1(CHAIN_WST_G, 4, 5, 6), CHAIN_A1, "v"(voff), "s"(rsrc), "s"(soff));
+    else if constexpr (W == 2) CHAIN_WSTORE(CHAIN_W2(CHAIN_WST_G, 6, 7, 8), CHAIN_A2, "v"(voff), "s"(rsrc), "s"(soff));
+    else if constexpr (W == 4) CHAIN_WSTORE(CHAIN_W4(CHAIN_WST_G, 10, 11, 12), CHAIN_A4, "v"(voff), "s"(rsrc), "s"(soff));
+    else CHAIN_WSTORE(CHAIN_W8(CHAIN_WST_G, 18, 19, 20), CHAIN_A8, "v"(voff), "s"(rsrc), "s"(soff));
 }
-template <int OFF>
-__device__ __forceinline__ void chain_store_piece_lds(const v4f_& a, uint32_t addr, unsigned long long mask) {
-    static_assert(OFF >= 0 && OFF < 65536, "16-bit immediate");
+template <int OFF, int W>
+__device__ __forceinline__ void chain_store_window_lds(const v4f_ (&a)[W], uint32_t addr, unsigned long long mask) {
+    static_assert(W == 1 || W == 2 || W == 4 || W == 8, "the window sizes that are written out");
+    static_assert(OFF >= 0 && OFF + 64 * (W - 1) < 65536, "16-bit immediate");
     unsigned long long saved;
-    asm volatile("s_mov_b64 %0, exec\n\t"
-                 "s_mov_b64 exec, %3\n\t"
-                 "ds_write_b128 %2, %1 offset:%c4\n\t"
-                 "s_mov_b64 exec, %0"
-                 : "=&s"(saved)
-                 : "v"(a), "v"(addr), "s"(mask), "i"(OFF)
-                 : "memory");
+    if constexpr (W == 1) CHAIN_WSTORE(CHAIN_W1(CHAIN_WST_L, 4), CHAIN_A1, "v"(addr));
+    else if constexpr (W == 2) CHAIN_WSTORE(CHAIN_W2(CHAIN_WST_L, 6), CHAIN_A2, "v"(addr));
+    else if constexpr (W == 4) CHAIN_WSTORE(CHAIN_W4(CHAIN_WST_L, 10), CHAIN_A4, "v"(addr));
+    else CHAIN_WSTORE(CHAIN_W8(CHAIN_WST_L, 18), CHAIN_A8, "v"(addr));
 }
+#undef CHAIN_WSTORE
+#undef CHAIN_A8
+#undef CHAIN_A4
+#undef CHAIN_A2
+#undef CHAIN_A1
+#undef CHAIN_W8
+#undef CHAIN_W4
+#undef CHAIN_W2
+#undef CHAIN_W1
+#undef CHAIN_WST_L
+#undef CHAIN_WST_G
 // every lane takes the register of chain_skew::state_lane(lane), its quad's first lane (one v_mov_b32 with a DPP quad permute; all
 // 64 lanes are enabled)
 __device__ __forceinline__ void quad_first(uint32_t& v) { v = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, chain_skew::kStateQuadPerm, 0xF, 0xF, false); }
@@ -1297,6 +1324,9 @@ __device__ __forceinline__ void quad_first(float& v) { uint32_t u = f2u(v); quad
 // of its quad take that state from it (quad_first) where they used to run up to 12 more predicated steps on three more clamped
 // loads per operand (~50 issue slots and 3 memory instructions per block of the lone wave, for bits the quad already held). The
 // last span issues no loads at all.
+// A steady group is written to the instruction count: the chain's own VALU ops, four loads per streamed operand, ONE wait, ONE
+// store, and the EXEC switch of the stores shared by the W groups of a window (chain_skew.h) — for a one-pole 32 + 4 + 1 + 1 + 4 / W.
+// tools/chain_loop_census.py counts it in the code object; tests/test_chain_loop_census.py holds it there.
 template <int NIN, uint32_t CM, int DEPTH, typename Step>
 __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut out, Step&& step) {
     constexpr int NS0 = NIN - __builtin_popcount(CM & ((1u << NIN) - 1u));
@@ -1304,6 +1334,8 @@ __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut ou
     constexpr uint32_t n = ELEMHIP_SPEC_BLOCK, span = (uint32_t)(DEPTH * CHG);
     static_assert(n % span == 0u && n >= span, "whole spans only");
     static_assert(CHG == (int)chain_skew::kGroup, "chain_skew.h is written for 16-frame groups");
+    constexpr int W = (int)chain_skew::window(NS0 > 0, (uint32_t)DEPTH);   // groups per store window
+    static_assert(chain_skew::window_fits((uint32_t)W, (uint32_t)DEPTH), "a window never leaves its span");
     const uint32_t skew = chain_skew::lane_skew(opaque_lane(), out.cnt);
     gfp arena = out.arena;
 #pragma unroll
@@ -1317,7 +1349,7 @@ __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut ou
     const unsigned long long smask = chain_skew::store_mask(out.cnt);
     typedef const char __attribute__((address_space(1)))* gccp;
     // a steady group: D-th of the span at byte offset soff of the block (never group 0)
-    auto load = [&](uint32_t soff, auto Dc, float (&x)[NS][CHG]) {
+    auto load = [&](uint32_t soff, auto Dc, v4f (&x)[NS][CHG / 4]) {
         constexpr int D = decltype(Dc)::value;
         int s_ = 0;
 #pragma unroll
@@ -1325,15 +1357,14 @@ __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut ou
             if (!((CM >> k) & 1u)) {
 #pragma unroll
                 for (int q = 0; q < CHG / 4; ++q) {
-                    const v4f a = *(gcv4)((gccp)arena + ioff[k] + soff + (D * CHG * 4 + 16 * q + chain_skew::kLoadImmBias));
-                    x[s_][4 * q] = a.x; x[s_][4 * q + 1] = a.y; x[s_][4 * q + 2] = a.z; x[s_][4 * q + 3] = a.w;
+                    x[s_][q] = *(gcv4)((gccp)arena + ioff[k] + soff + (D * CHG * 4 + 16 * q + chain_skew::kLoadImmBias));
                 }
                 ++s_;
             }
         }
     };
     // group G (0: the head's), pieces [0, NQ): every piece at its own clamped offset
-    auto load_edge = [&](uint32_t G, auto NQc, float (&x)[NS][CHG]) {
+    auto load_edge = [&](uint32_t G, auto NQc, v4f (&x)[NS][CHG / 4]) {
         constexpr int NQ = decltype(NQc)::value;
         int s_ = 0;
 #pragma unroll
@@ -1341,34 +1372,39 @@ __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut ou
             if (!((CM >> k) & 1u)) {
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) {
-                    const v4f a = *(gcv4)((gccp)arena + (in[k].goff + chain_skew::load_offset(G, (uint32_t)q, skew, n)));
-                    x[s_][4 * q] = a.x; x[s_][4 * q + 1] = a.y; x[s_][4 * q + 2] = a.z; x[s_][4 * q + 3] = a.w;
+                    x[s_][q] = *(gcv4)((gccp)arena + (in[k].goff + chain_skew::load_offset(G, (uint32_t)q, skew, n)));
                 }
                 ++s_;
             }
         }
     };
-    auto wait_group = [&](float (&x)[NS][CHG], auto Lc) {   // one wait per group, for its LAST load (vector loads return in order)
-        constexpr int L = decltype(Lc)::value;
-        if constexpr (NS0 > 0) {
-#pragma unroll
-            for (int k_ = 0; k_ < NS; ++k_) asm volatile("" : "+v"(x[k_][L - 4]), "+v"(x[k_][L - 3]), "+v"(x[k_][L - 2]), "+v"(x[k_][L - 1]));
-        }
+    // One wait per group, for whichever of its loads was issued last (vector loads return in order; the compiler orders the four
+    // loads of a group as it likes): an empty statement that READS every piece of the group, and a scheduling barrier behind it so
+    // that no step of the group moves above it. (Until r09 the statement made the last piece opaque and nothing more: the chain's
+    // first steps, which read the first piece, were scheduled in front of it and the loop waited piece by piece, three times per
+    // group. The statement has no outputs: the compiler pads an asm output that the next VALU instruction touches with a wait state.)
+    auto wait_group = [&](const v4f (&x)[NS][CHG / 4]) {
+        static_assert(CHG == 16 && NS <= 3, "four pieces per stream, at most three streams in one statement");
+        if constexpr (NS0 == 1) asm volatile("" : : "v"(x[0][0]), "v"(x[0][1]), "v"(x[0][2]), "v"(x[0][3]));
+        else if constexpr (NS0 == 2) asm volatile("" : : "v"(x[0][0]), "v"(x[0][1]), "v"(x[0][2]), "v"(x[0][3]), "v"(x[1][0]), "v"(x[1][1]), "v"(x[1][2]), "v"(x[1][3]));
+        else if constexpr (NS0 == 3) asm volatile("" : : "v"(x[0][0]), "v"(x[0][1]), "v"(x[0][2]), "v"(x[0][3]), "v"(x[1][0]), "v"(x[1][1]), "v"(x[1][2]), "v"(x[1][3]),
+                                                         "v"(x[2][0]), "v"(x[2][1]), "v"(x[2][2]), "v"(x[2][3]));
+        if constexpr (NS0 > 0) __builtin_amdgcn_sched_barrier(0);
     };
-    auto operands = [&](const float (&x)[NS][CHG], int j, float (&xs)[NIN]) {
+    auto operands = [&](const v4f (&x)[NS][CHG / 4], int j, float (&xs)[NIN]) {
         int s_ = 0;
 #pragma unroll
         for (int k = 0; k < NIN; ++k) {
             if ((CM >> k) & 1u) xs[k] = in[k].cval;
-            else xs[k] = x[s_++][j];
+            else xs[k] = x[s_++][j / 4][j % 4];
         }
     };
-    // HEAD: group 0 of the block — a lane of skew k holds for its first 4k steps
-    auto run = [&](float (&x)[NS][CHG], uint32_t soff, auto Dc, auto Hc) {
-        constexpr int D = decltype(Dc)::value;
+    // The 16 steps of a group; returns the lane's piece of it, its last four results. HEAD: group 0 of the block — a lane of skew k
+    // holds for its first 4k steps
+    auto run = [&](v4f (&x)[NS][CHG / 4], auto Hc) {
         constexpr bool HEAD = decltype(Hc)::value != 0;
         float y[CHG];
-        wait_group(x, IntC<CHG>{});
+        wait_group(x);
 #pragma unroll
         for (int j = 0; j < CHG; ++j) {
             float xs[NIN];
@@ -1378,10 +1414,9 @@ __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut ou
         }
         v4f a;
         a.x = y[CHG - 4]; a.y = y[CHG - 3]; a.z = y[CHG - 2]; a.w = y[CHG - 1];
-        if (out.isG) chain_store_piece<D * CHG * 4>(a, ooff, rsrc, soff, smask);
-        else chain_store_piece_lds<D * CHG * 4>(a, ooff + soff, smask);
+        return a;
     };
-    float X[DEPTH][NS][CHG];
+    v4f X[DEPTH][NS][CHG / 4];
     CHAIN_OPAQUE_OFFSETS();
     if constexpr (NS0 > 0) {
         load_edge(0u, IntC<CHG / 4>{}, X[0]);
@@ -1390,24 +1425,36 @@ __device__ __forceinline__ void chain_loop_q(const SIn (&in)[NIN], const SOut ou
     } else take_deferred<0>(out.defer);
     auto span_body = [&](uint32_t soff, auto Hc, auto Lc) {
         constexpr bool HEAD = decltype(Hc)::value != 0, LAST = decltype(Lc)::value != 0;
-        CHAIN_OPAQUE_OFFSETS();
+        // (without loads there is no offset arithmetic to keep in the immediates, and an empty statement that DEFINES ooff right in
+        //  front of the store statement that reads it draws a wait-state pad from the compiler)
+        if constexpr (NS0 > 0) CHAIN_OPAQUE_OFFSETS();
+        v4f A[W];                                            // the pieces of the open window
         static_for<0, DEPTH>([&](auto Dc) {
             constexpr int D = decltype(Dc)::value;
-            run(X[D], soff, Dc, IntC<(HEAD && D == 0) ? 1 : 0>{});
+            A[D % W] = run(X[D], IntC<(HEAD && D == 0) ? 1 : 0>{});
+            if constexpr (chain_skew::window_closes((uint32_t)D, (uint32_t)W)) {
+                constexpr int OFF = (int)chain_skew::window_first((uint32_t)D, (uint32_t)W) * CHG * 4;
+                if (out.isG) chain_store_window<OFF, W>(A, ooff, rsrc, soff, smask);
+                else chain_store_window_lds<OFF, W>(A, ooff + soff, smask);
+            }
             if constexpr (NS0 > 0 && !LAST) load(soff + span * 4u, Dc, X[D]);
         });
     };
     constexpr int NSPAN = (int)(n / span);
-    if constexpr (NS0 > 0) {
+    if constexpr (NS0 > 0 || IsChainStep<Step>::kShort) {
         // Streamed operands: the spans are written out one after the other. As a loop around a peeled head and last span the
         // prefetched registers were carried through phi copies at every span end, each behind a wait for ITS load — the whole
         // next span drained there (vmcnt 24, 20 .. 2 in a row) instead of one group at a time.
+        // A short step without operands (ChainStep::kShort) is written out too: 0.6 KB per span, and no counter or back edge.
         static_for<0, NSPAN>([&](auto Sc) {
             constexpr int S = decltype(Sc)::value;
             span_body((uint32_t)S * span * 4u, IntC<S == 0 ? 1 : 0>{}, IntC<S == NSPAN - 1 ? 1 : 0>{});
         });
     } else if constexpr (n == span) span_body(0u, IntC<1>{}, IntC<1>{});
     else {
+        // No streamed operand, a step of some length: a loop around the inner spans (counter and back edge: ~1 instruction per
+        // group). With EVERY such loop written out the C2 voice kernel grew from 48 to 65 KB of code and its block period went UP,
+        // 7.12 k -> 7.17 k cycles (profiles/r09/spec_island_wave_busy_c2_chain_window.txt): only the short steps are.
         span_body(0u, IntC<1>{}, IntC<0>{});
         for (uint32_t t0 = span; t0 + span < n; t0 += span) span_body(t0 * 4u, IntC<0>{}, IntC<0>{});
         span_body((n - span) * 4u, IntC<0>{}, IntC<1>{});
@@ -1763,7 +1810,7 @@ __device__ __forceinline__ void ser_phasor(const Ctx& c, const Member& m, uint32
     if ((cm & 1u) && in[0].cval * rsr >= 0.0f && phase >= 0.0f) {
         // constant non-negative step: next >= 0, so next - floor(next) is exactly v_fract_f32(next)
         const SIn st[1] = {sin_const(in[0].cval * rsr)};
-        chain_blocks_m<1, 1u>(c, st, sout_of(c, m), chain_step([&](const float (&x)[1]) {
+        chain_blocks_m<1, 1u>(c, st, sout_of(c, m), chain_step<true>([&](const float (&x)[1]) {   // (two VALU ops per frame: written out)
             const float y = phase;
             phase = __builtin_amdgcn_fractf(phase + x[0]);
             return y;
@@ -2330,7 +2377,7 @@ __device__ __forceinline__ void ser_phase(const Ctx& c, const Member& m, bool bl
     if (__all(fast)) {
         // phasor: next >= 0, so next - floor(next) is exactly v_fract_f32(next); oscillator: t = phase + inc lies in [0, 2), where
         // `if (t >= 1) t -= 1` is t - floor(t) exactly as well
-        chain_blocks_m<1, 1u>(c, in, sout_of(c, m), chain_step([&](const float (&x)[1]) {
+        chain_blocks_m<1, 1u>(c, in, sout_of(c, m), chain_step<true>([&](const float (&x)[1]) {   // (two VALU ops per frame: written out)
             const float y = phase;
             phase = __builtin_amdgcn_fractf(phase + x[0]);
             return y;
