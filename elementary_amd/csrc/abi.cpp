@@ -340,6 +340,21 @@ int elemhip_flac_md5_update(uint8_t* record, const int32_t* const* planar, uint3
     return elemhip::kOk;
 }
 
+int elemhip_flac_in_md5_update(uint8_t* record, const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t bits) {
+    namespace fi = flac_in_md5;
+    if (!record || (frames && !planar) || channels == 0u || channels > fi::kMaxChannels || !fi::bits_ok(bits)) return elemhip::kInvalidInstructionFormat;
+    for (uint32_t c = 0; c < channels && frames; ++c) if (!planar[c]) return elemhip::kInvalidInstructionFormat;
+    flac_md5::Record r;
+    std::memcpy(&r, record, sizeof r);           // (the caller's bytes need not be aligned)
+    const int32_t* at[fi::kMaxChannels];
+    for (size_t f0 = 0; f0 < frames; f0 += (size_t)1 << 30) {       // (an update counts its frames in 32 bits)
+        for (uint32_t c = 0; c < channels; ++c) at[c] = planar[c] + f0;
+        fi::update_codes(r, at, channels, 0u, std::min<size_t>((size_t)1 << 30, frames - f0), bits);
+    }
+    std::memcpy(record, &r, sizeof r);
+    return elemhip::kOk;
+}
+
 int elemhip_flac_md5_final(const uint8_t* record, uint8_t digest[16]) {
     if (!record || !digest) return elemhip::kInvalidInstructionFormat;
     flac_md5::Record r;
@@ -405,6 +420,12 @@ int elemhip_flac_in_error(elemhip_t* h, uint32_t* stream, uint64_t* frame, uint3
     return h ? h->engine.flacInError(stream, frame, reason) : elemhip::kInvalidInstructionFormat;
 }
 
+int elemhip_flac_in_md5(elemhip_t* h, uint8_t* digests, uint32_t* states, uint64_t* hashed, size_t capacity, size_t* slots) {
+    return h ? h->engine.flacInMd5Read(digests, states, hashed, capacity, slots) : elemhip::kInvalidInstructionFormat;
+}
+
+int elemhip_flac_in_md5_reset(elemhip_t* h) { return h ? h->engine.flacInMd5Reset() : elemhip::kInvalidInstructionFormat; }
+
 int elemhip_loudness_gate(const double* meanSquares, size_t channels, size_t subBlocks, const double* weights, elemhip_loudness_result* out) {
     if (!out || (channels && subBlocks && !meanSquares)) return elemhip::kInvalidInstructionFormat;
     const loudness::Gated g = loudness::gate(meanSquares, channels, subBlocks, weights);
@@ -435,6 +456,10 @@ int elemhip_shared_resource_info(elemhip_t* h, const char* name, uint32_t* chann
 
 int elemhip_shared_resource_read(elemhip_t* h, const char* name, uint32_t channel, uint64_t first, uint64_t count, float* out) {
     return h && name ? h->engine.sharedResourceRead(name, channel, first, count, out) : elemhip::kInvalidInstructionFormat;
+}
+
+int elemhip_shared_resource_md5(elemhip_t* h, const char* name, uint8_t digest[16], uint32_t* state) {
+    return h && name ? h->engine.sharedResourceMd5(name, digest, state) : elemhip::kInvalidInstructionFormat;
 }
 
 void elemhip_prune_shared_resources(elemhip_t* h) { if (h) h->engine.pruneSharedResources(); }

@@ -559,6 +559,14 @@ int Engine::setOption(const std::string& key, double value) {
         flacMd5Opt = (uint32_t)value;
         return kOk;
     }
+    // flac_in_md5.h: 1 — the samples decoded from FLAC inputs and FLAC resources enter their stream's STREAMINFO MD5 on the device; 0, the
+    // default: not one launch, allocation or byte differs. Another value than the option has resets the input slots.
+    if (key == "flac_in_md5") {
+        if (value != 0.0 && value != 1.0) return kInvalidPropertyValue;
+        if ((uint32_t)value != flacInMd5Opt) { const int rc = flacInMd5ResetLocked(); if (rc != kOk) return rc; }
+        flacInMd5Opt = (uint32_t)value;
+        return kOk;
+    }
     if (key == "flac_frame" || key == "flac_bits") {
         const bool frame = key == "flac_frame";
         const uint32_t v = value >= 0.0 && value <= 65536.0 && value == std::floor(value) ? (uint32_t)value : 0u;

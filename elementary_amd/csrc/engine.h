@@ -31,6 +31,7 @@
 #include "limiter.h"
 #include "flac_decode.h"
 #include "flac_md5.h"
+#include "flac_in_md5.h"
 #include "noise_shape.h"
 #include "spectrum.h"
 
@@ -77,6 +78,10 @@ struct Resource {
     bool onDevice = false;
     uint32_t deviceChannels = 0;
     uint64_t deviceFrames = 0;
+    // a FLAC source loaded under option "flac_in_md5": 0 — not hashed; 1 — the load did not cover the stream from sample 0 to its end;
+    // 2 — `md5` holds the digest of the file's samples
+    uint32_t md5State = 0;
+    uint8_t md5[16] = {};
     size_t numChannels() const { return onDevice ? deviceChannels : channels.size(); }
     size_t frames(size_t ch) const { return onDevice ? (ch < deviceChannels ? (size_t)deviceFrames : 0) : (ch < channels.size() ? channels[ch].size() : 0); }
 };
@@ -254,6 +259,16 @@ public:
     struct FlacIn { const uint8_t* data; uint64_t bytes; const uint64_t* frameOffsets; const uint64_t* frameFirstSamples; uint64_t frames;
                     uint32_t channels, bits; uint64_t totalSamples, position; };
     int flacInError(uint32_t* stream, uint64_t* frame, uint32_t* reason);
+    // Option "flac_in_md5" (flac_in_md5.h; 0, the default: off — no launch, no buffer, not one byte differs; 1): input stream s of a call is
+    // slot s, and the samples the decoder restores enter the slot's running MD5 on the device (flac_in_md5.hip) behind the decode kernels
+    // of every set — each stream sample once, also where two sets decode the same FLAC frame. A slot's state: 0 off or never fed, 1 running,
+    // 2 complete (the digest of the whole stream, finished by the launch that hashed its last sample), 3 broken (a gap, a frame that did not
+    // decode, another stream under a running slot) until the reset. The stage only reads: no rendered sample depends on it.
+    // flacInMd5Read waits for what is in flight; digests [slots][16] (zero unless state 2), states and hashed [slots]; capacity in slots.
+    int flacInMd5Read(uint8_t* digests, uint32_t* states, uint64_t* hashed, size_t capacity, size_t* slots);
+    int flacInMd5Reset();
+    // the digest a FLAC resource's load left (option "flac_in_md5" at the time): state as Resource::md5State
+    int sharedResourceMd5(const std::string& name, uint8_t digest[16], uint32_t* state);
     // Option "loudness_meter" (loudness.h): every launch set of processBlocksHost / processBlocksPcm / processBlocksPcmIo is metered
     // where its output lies in HBM (loudness.hip), float or PCM delivery alike; where those calls render host block by host block the
     // header's scalar loop meters the floats on the host. process() and the device-resident processBlocks() are NOT metered. The
@@ -660,6 +675,8 @@ private:
         std::vector<FlacInFrame> frames; std::vector<FlacInStream> streams;
         std::vector<uint64_t> from, len;        // per stream: its covering bytes in the caller's buffer
         size_t stagedBytes = 0, scratchInts = 0;
+        std::vector<flac_in_md5::Job> jobs;     // option "flac_in_md5": one per stream, staged at jobsOff behind the bytes
+        size_t jobsOff = 0; bool md5Work = false, md5Finish = false;
     };
     FlacInSet flacInSets[2];
     unsigned char* hFlacIn[2] = {nullptr, nullptr}; unsigned char* dFlacIn[2] = {nullptr, nullptr};
@@ -670,13 +687,24 @@ private:
     bool flacInErrSet = false; uint32_t flacInErrStream = 0, flacInErrReason = 0; uint64_t flacInErrFrame = 0;
     int flacInCheck(const PcmSource& src) const;
     uint32_t flacInBits(const PcmSource& src) const;
-    void flacInPlan(const PcmSource& src, uint64_t from, size_t valid, FlacInSet& set) const;
+    void flacInPlan(const PcmSource& src, uint64_t from, size_t valid, FlacInSet& set, bool md5 = false) const;
     int ensureFlacIn(size_t stagedBytes, size_t frames, size_t scratchInts, uint32_t G);      // (`mu` held)
     void flacInStage(const PcmSource& src, const FlacInSet& set, int half);
     int flacInLaunch(const FlacInSet& set, int half, uint32_t G, uint32_t bits, size_t valid, size_t streamStride);      // (`mu` held)
     bool flacInFailed(int half);                // the set's error record has arrived: anything in it -> the last error
-    int flacInHostImage(const PcmSource& src, uint64_t from, size_t n, std::vector<std::vector<unsigned char>>& images);
+    int flacInHostImage(const PcmSource& src, uint64_t from, size_t n, std::vector<std::vector<unsigned char>>& images, flac_md5::Record* md5 = nullptr);
     void flacInFree();
+    // option "flac_in_md5": kMaxHostIn records on the device, as many 16-byte digests behind them and a pinned copy of the digests
+    uint32_t flacInMd5Opt = 0;
+    std::vector<flac_in_md5::Slot> flacInMd5Slots;      // the slots fed since the reset
+    unsigned char* dFlacInMd5 = nullptr; uint8_t* hFlacInMd5 = nullptr;
+    flac_md5::Record* flacInMd5Records() const { return reinterpret_cast<flac_md5::Record*>(dFlacInMd5); }
+    uint8_t* flacInMd5Digests() const { return dFlacInMd5 + (size_t)kMaxHostIn * sizeof(flac_md5::Record); }
+    int ensureFlacInMd5();                                                  // (`mu` held)
+    static flac_in_md5::Job flacInMd5Job(const FlacIn& f, const FlacInSet& set, size_t s, flac_in_md5::Slot& slot);      // one stream's
+    void flacInMd5Jobs(const PcmSource& src, FlacInSet& set, int half);     // (`mu` held) the rule per stream -> the set's staged jobs
+    int flacInMd5Launch(const FlacInSet& set, int half, uint32_t G, uint32_t bits);      // (`mu` held) on `stream`, behind the decode
+    int flacInMd5ResetLocked();
     // The resource loader (engine_resource_load.cpp): everything below is touched under `ctl` only and by the loader's own stream —
     // never by a render. Two staging halves (pinned: the piece as it lies in the file; device: the FLAC bytes, and the PCM image the
     // load kernels read), an event per half, the FLAC decoder's scratch, the last rate pair's tables and the last group's row table.
@@ -688,6 +716,7 @@ private:
     FlacInError* hLoadErr = nullptr; FlacInError* dLoadErr = nullptr;      // one per half
     void* dLoadSubs = nullptr; uint32_t* dLoadState = nullptr; int32_t* dLoadScratch = nullptr;
     size_t loadFrameCap = 0, loadScratchCap = 0;
+    unsigned char* dLoadMd5 = nullptr;              // option "flac_in_md5": the current load's record and, behind it, its digest
     resample::Plan loadPlan{};                      // L == 0: no tables yet
     std::vector<float> loadTable; std::vector<int32_t> loadRowBase;
     float* dLoadTable = nullptr; int32_t* dLoadRowBase = nullptr;
@@ -707,6 +736,7 @@ private:
         PcmJob* pcm; const PcmSource* src; FlacJob* flac;
         size_t bs, hb;                                  // the engine's block, the host's
         bool flacSrc; uint32_t flacInB;                 // a FLAC source, its bits
+        bool inMd5;                                     // ... hashed under option "flac_in_md5"
         uint32_t srcG, srcFmt; size_t srcB;             // the source's group, format (a FLAC source: its image's) and sample bytes
         bool wantFloat;
         uint32_t pcmG, pcmFmt; size_t pcmB;

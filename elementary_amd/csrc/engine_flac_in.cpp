@@ -6,6 +6,7 @@
 namespace elemhip {
 
 namespace fd = flac_decode;
+namespace fi = flac_in_md5;
 
 void Engine::flacInFree() {
     for (int k = 0; k < 2; ++k) { if (hFlacIn[k]) (void)hipHostFree(hFlacIn[k]); if (dFlacIn[k]) (void)hipFree(dFlacIn[k]); hFlacIn[k] = dFlacIn[k] = nullptr; }
@@ -16,6 +17,9 @@ void Engine::flacInFree() {
     if (dFlacInScratch) (void)hipFree(dFlacInScratch);
     hFlacInErr = dFlacInErr = nullptr; dFlacInSubs = nullptr; dFlacInState = nullptr; dFlacInScratch = nullptr;
     flacInBytes = flacInFrameCap = flacInScratchCap = 0;
+    if (dFlacInMd5) (void)hipFree(dFlacInMd5);
+    if (hFlacInMd5) (void)hipHostFree(hFlacInMd5);
+    dFlacInMd5 = nullptr; hFlacInMd5 = nullptr;
 }
 
 uint32_t Engine::flacInBits(const PcmSource& src) const { return src.nStreams ? static_cast<const FlacIn*>(src.streams[0])->bits : 16u; }
@@ -43,7 +47,7 @@ int Engine::flacInCheck(const PcmSource& src) const {
 
 // The records of the set that reads input frames [from, from + valid) of the call: per stream the frames that cover stream samples
 // [position + from, position + from + valid), cut at the stream's end.
-void Engine::flacInPlan(const PcmSource& src, uint64_t from, size_t valid, FlacInSet& set) const {
+void Engine::flacInPlan(const PcmSource& src, uint64_t from, size_t valid, FlacInSet& set, bool md5) const {
     const size_t S = src.nStreams;
     const uint32_t G = src.channelsPerStream;
     set.frames.clear(); set.streams.assign(S, FlacInStream{}); set.from.assign(S, 0); set.len.assign(S, 0);
@@ -75,6 +79,13 @@ void Engine::flacInPlan(const PcmSource& src, uint64_t from, size_t valid, FlacI
     // the staged half: the two tables, 16-byte aligned, in front of the bytes (byteOff counts from the bytes' start)
     const size_t tables = set.frames.size() * sizeof(FlacInFrame) + S * sizeof(FlacInStream);
     set.stagedBytes = tables + (size_t)bytes; set.scratchInts = (size_t)scratch;
+    // option "flac_in_md5": the streams' jobs behind the bytes (flacInMd5Jobs fills them in)
+    set.jobs.clear(); set.md5Work = set.md5Finish = false; set.jobsOff = 0;
+    if (md5) {
+        set.jobs.assign(S, fi::Job{});
+        set.jobsOff = (set.stagedBytes + 15u) & ~(size_t)15u;
+        set.stagedBytes = set.jobsOff + S * sizeof(fi::Job);
+    }
 }
 
 int Engine::ensureFlacIn(size_t stagedBytes, size_t frames, size_t scratchInts, uint32_t G) {
@@ -145,7 +156,97 @@ bool Engine::flacInFailed(int half) {
     const FlacInSet& set = flacInSets[half];
     flacInErrStream = rec < set.frames.size() ? set.frames[rec].stream : 0u;
     flacInErrFrame = rec < set.frames.size() ? set.frames[rec].index : 0u;
+    // (what the failed frame left in the scratch went into the digest: the slot is broken; so is every slot another failed frame of the
+    //  set may belong to — the record names the first one only)
+    if (!set.jobs.empty()) for (size_t s = 0; s < set.jobs.size() && s < flacInMd5Slots.size(); ++s)
+        if (s == flacInErrStream || e.count > 1u) flacInMd5Slots[s].state = fi::kBroken;
     return true;
+}
+
+// ---- option "flac_in_md5" ---------------------------------------------------------------------------------------------------------------------
+int Engine::ensureFlacInMd5() {
+    if (dFlacInMd5) return kOk;
+    const size_t S = kMaxHostIn;
+    HIP_OK(hipMalloc((void**)&dFlacInMd5, S * (sizeof(flac_md5::Record) + 16u)));
+    HIP_OK(hipHostMalloc((void**)&hFlacInMd5, S * 16u, hipHostMallocDefault));
+    std::memset(hFlacInMd5, 0, S * 16u);
+    return flacInMd5ResetLocked();
+}
+
+// every slot off, every record at its initial value (a slot that is fed for the first time finds it so)
+int Engine::flacInMd5ResetLocked() {
+    flacInMd5Slots.clear();
+    if (!dFlacInMd5) return kOk;
+    if (hipSetDevice(device) != hipSuccess) return kHipError;
+    HIP_OK(hipStreamSynchronize(stream));
+    if (ioStream) HIP_OK(hipStreamSynchronize(ioStream));
+    std::vector<flac_md5::Record> fresh(kMaxHostIn);
+    for (flac_md5::Record& r : fresh) flac_md5::init(r);
+    HIP_OK(hipMemcpy(dFlacInMd5, fresh.data(), fresh.size() * sizeof(flac_md5::Record), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(flacInMd5Digests(), 0, (size_t)kMaxHostIn * 16u));
+    std::memset(hFlacInMd5, 0, (size_t)kMaxHostIn * 16u);
+    return kOk;
+}
+
+int Engine::flacInMd5Reset() {
+    RenderGuard lock(*this);
+    return flacInMd5ResetLocked();
+}
+
+int Engine::flacInMd5Read(uint8_t* digests, uint32_t* states, uint64_t* hashed, size_t capacity, size_t* slots) {
+    RenderGuard lock(*this);
+    const size_t S = flacInMd5Slots.size();
+    if (slots) *slots = S;
+    if (!digests && !states && !hashed) return kOk;
+    if (capacity < S) return kInvalidPropertyValue;
+    if (dFlacInMd5) {       // what is in flight: the digests come back on the copy stream behind the set that finished them
+        if (hipSetDevice(device) != hipSuccess) return kHipError;
+        HIP_OK(hipStreamSynchronize(stream));
+        if (ioStream) HIP_OK(hipStreamSynchronize(ioStream));
+    }
+    for (size_t s = 0; s < S; ++s) {
+        const fi::Slot& sl = flacInMd5Slots[s];
+        if (states) states[s] = sl.state;
+        if (hashed) hashed[s] = sl.state == fi::kOff ? 0u : sl.hashedTo;
+        if (digests) { if (sl.state == fi::kComplete && hFlacInMd5) std::memcpy(digests + 16u * s, hFlacInMd5 + 16u * s, 16u); else std::memset(digests + 16u * s, 0, 16u); }
+    }
+    return kOk;
+}
+
+// The rule per stream of a planned set (flac_in_md5::advance): the set decodes its covered frames whole, stream samples [c0, c1); what
+// of them is new enters the digest, and the launch that takes a stream's last sample finishes it. The jobs go into the pinned half.
+fi::Job Engine::flacInMd5Job(const FlacIn& f, const FlacInSet& set, size_t s, fi::Slot& slot) {
+    const FlacInStream& st = set.streams[s];
+    fi::Job j{};
+    if (st.frames == 0u) return j;
+    const uint64_t total = fi::total_of(f.totalSamples, f.frames ? f.frameFirstSamples[f.frames] : 0u);
+    const uint64_t c0 = f.frameFirstSamples[set.frames[st.firstFrame].index], c1 = c0 + st.covered;
+    uint64_t lo = 0; bool finish = false;
+    if (!fi::advance(slot, f.bits, f.channels, total, c0, c1, lo, finish)) return j;
+    j.base = st.scratchBase; j.stride = st.covered; j.first = (uint32_t)(lo - c0); j.count = (uint32_t)(c1 - lo); j.finish = finish ? 1u : 0u;
+    return j;
+}
+
+void Engine::flacInMd5Jobs(const PcmSource& src, FlacInSet& set, int half) {
+    const size_t S = set.streams.size();
+    if (flacInMd5Slots.size() < S) flacInMd5Slots.resize(S, fi::Slot{});
+    set.md5Work = set.md5Finish = false;
+    for (size_t s = 0; s < S && s < set.jobs.size(); ++s) {
+        const fi::Job j = set.jobs[s] = flacInMd5Job(*static_cast<const FlacIn*>(src.streams[s]), set, s, flacInMd5Slots[s]);
+        set.md5Work = set.md5Work || j.count || j.finish; set.md5Finish = set.md5Finish || j.finish;
+    }
+    if (!set.jobs.empty()) std::memcpy(hFlacIn[half] + set.jobsOff, set.jobs.data(), set.jobs.size() * sizeof(fi::Job));
+}
+
+int Engine::flacInMd5Launch(const FlacInSet& set, int half, uint32_t G, uint32_t bits) {
+    if (!set.md5Work) return kOk;
+    if (!dFlacInMd5 || set.jobs.size() > kMaxHostIn || set.jobsOff + set.jobs.size() * sizeof(fi::Job) > flacInBytes) return kInvariantViolation;
+    FlacInMd5Args a{};
+    a.scratch = dFlacInScratch; a.records = flacInMd5Records(); a.digests = flacInMd5Digests();
+    a.jobs = reinterpret_cast<const fi::Job*>(dFlacIn[half] + set.jobsOff);
+    a.numStreams = (uint32_t)set.jobs.size(); a.G = G; a.bits = bits;
+    HIP_OK(launch_flac_in_md5(stream, a, set.jobs.data(), set.scratchInts));
+    return kOk;
 }
 
 int Engine::flacInError(uint32_t* stream, uint64_t* frame, uint32_t* reason) {
@@ -159,7 +260,7 @@ int Engine::flacInError(uint32_t* stream, uint64_t* frame, uint32_t* reason) {
 
 // the block-by-block path: input frames [from, from + n) of the call decoded on the host (decode_host) into the interleaved image
 // unpack_host reads — the kernels' functions, the kernels' bits (`mu` held)
-int Engine::flacInHostImage(const PcmSource& src, uint64_t from, size_t n, std::vector<std::vector<unsigned char>>& images) {
+int Engine::flacInHostImage(const PcmSource& src, uint64_t from, size_t n, std::vector<std::vector<unsigned char>>& images, flac_md5::Record* md5) {
     const uint32_t G = src.channelsPerStream, bits = flacInBits(src), B = bits <= 16u ? 2u : 3u;
     images.resize(src.nStreams);
     std::vector<int32_t> codes((size_t)G * std::max<size_t>(n, 1));
@@ -169,9 +270,20 @@ int Engine::flacInHostImage(const PcmSource& src, uint64_t from, size_t n, std::
         const FlacIn& f = *static_cast<const FlacIn*>(src.streams[s]);
         size_t bad = 0;
         const uint32_t r = fd::decode_host(f.data, f.frameOffsets, f.frameFirstSamples, (size_t)f.frames, G, bits, f.position + from, n, planar, &bad);
+        if (flacInMd5Slots.size() < src.nStreams) flacInMd5Slots.resize(src.nStreams, fi::Slot{});
         if (r != fd::OK) {
             flacInErrSet = true; flacInErrStream = (uint32_t)s; flacInErrFrame = bad; flacInErrReason = r;
+            if (md5) flacInMd5Slots[s].state = fi::kBroken;
             return kFlacInput;
+        }
+        if (md5) {
+            // option "flac_in_md5": the range this block decoded, [c0, c1) of the stream, under the launch sets' rule, through the
+            // kernel's scalar twin on the record brought over for the call
+            const uint64_t closing = f.frames ? f.frameFirstSamples[f.frames] : 0u, total = fi::total_of(f.totalSamples, closing);
+            const uint64_t c0 = f.position + from, c1 = std::min<uint64_t>(c0 + n, closing);
+            uint64_t lo = 0; bool finish = false;
+            if (c0 < closing && c0 >= f.frameFirstSamples[0] && fi::advance(flacInMd5Slots[s], f.bits, f.channels, total, c0, c1, lo, finish))
+                fi::update_codes(md5[s], planar, G, (uint32_t)(lo - c0), c1 - lo, bits, finish ? hFlacInMd5 + 16u * s : nullptr);
         }
         images[s].assign(std::max<size_t>(n * G * B, 1), 0);
         fd::image_host(bits, G, planar, n, images[s].data());

@@ -33,6 +33,7 @@ struct Engine::HostCarry {
     std::vector<unsigned char> limState; std::vector<limiter::GroupStats> limStats;
     std::vector<std::vector<int32_t>> flacCodes;        // FLAC delivery: the open frame's codes per channel
     std::vector<flac_md5::Record> flacMd5;              // ... and, with option "flac_md5", the streams' running digests
+    std::vector<flac_md5::Record> flacInMd5;            // option "flac_in_md5": the input slots' running digests
     std::vector<noise_shape::ChannelState> shapeState;  // noise-shaped requantisation: the channels' errors
     std::vector<float> spcTail; std::vector<double> spcSums;      // the spectrum analyser: the carried frames, the running sums
     std::vector<Carried> stages;
@@ -69,6 +70,9 @@ struct Engine::HostCarry {
                       if (!flacMd5.empty()) s.push_back({flacMd5.data(), e.dFlacMd5, flacMd5.size() * sizeof(flac_md5::Record)});
                       return s; },
              Carried::kNothing, nullptr, [this] { e.flacOpen = (uint32_t)flacCodes[0].size(); }},
+            // option "flac_in_md5": the input slots' records (the slots' states live on the host and stay with what was hashed)
+            {c.inMd5, [this] { flacInMd5.resize(c.src->nStreams); return e.ensureFlacInMd5(); },
+             [this] { return std::vector<Span>{{flacInMd5.data(), e.dFlacInMd5, flacInMd5.size() * sizeof(flac_md5::Record)}}; }, Carried::kWriteBack, nullptr, nullptr},
             // the spectrum analyser: the carried frames and the running sums; a failed call starts a new programme
             {c.spectrum, [this] { const int rc = e.ensureSpectrum(c.nOut, 0);
                                   if (rc == kOk) { spcTail.resize(c.nOut * (size_t)(e.spcPlan.size - 1u)); spcSums.resize(c.nOut * (size_t)e.spcPlan.cols); }
@@ -189,7 +193,7 @@ int Engine::renderHostBlocks(const HostCall& c) {
             std::lock_guard<std::mutex> lock(mu);
             const size_t ni = (size_t)(resample::inputs_before(c.inp, inFramesOut + nf) - inFramesIn), stride = std::max<size_t>(ni, 1);
             tailIn.assign(nIn * hb, 0.0f);
-            if (c.flacSrc) flacInRc = flacInHostImage(*src, inOff, ni, flacImg);
+            if (c.flacSrc) flacInRc = flacInHostImage(*src, inOff, ni, flacImg, c.inMd5 ? carry.flacInMd5.data() : nullptr);
             if (src && flacInRc == kOk) {
                 inX.resize(nIn * stride);
                 for (size_t s = 0; s < src->nStreams; ++s) srcAt[s] = c.flacSrc ? flacImg[s].data() : c.inStream(s) + inOff * c.srcG * c.srcB;
@@ -204,7 +208,7 @@ int Engine::renderHostBlocks(const HostCall& c) {
         } else if (src) {
             // the inputs are needed on the host: the header's scalar loop unpacks them — the kernel's functions, the kernel's floats
             tailIn.resize(nIn * hb);
-            if (c.flacSrc) { std::lock_guard<std::mutex> lock(mu); flacInRc = flacInHostImage(*src, f0, nf, flacImg); }
+            if (c.flacSrc) { std::lock_guard<std::mutex> lock(mu); flacInRc = flacInHostImage(*src, f0, nf, flacImg, c.inMd5 ? carry.flacInMd5.data() : nullptr); }
             for (size_t s = 0; s < src->nStreams && flacInRc == kOk; ++s)
                 srcAt[s] = c.flacSrc ? flacImg[s].data() : static_cast<const unsigned char*>(src->streams[s]) + f0 * c.srcG * c.srcB;
             if (flacInRc == kOk) pcm_unpack::unpack_host(c.srcFmt, c.srcG, (uint32_t)src->nStreams, srcAt.data(), nf, tailIn.data(), hb, hb);

@@ -1230,6 +1230,7 @@ Engine::HostCall Engine::hostCall(const float* const* in, size_t nIn, float* con
     // on it IS that PCM source
     c.flacSrc = src && src->format == flac_decode::kFormat;
     c.flacInB = c.flacSrc ? flacInBits(*src) : 0u;
+    c.inMd5 = c.flacSrc && flacInMd5Opt != 0u;      // option "flac_in_md5": what the decoder restores enters the input slots' digests
     c.srcG = src ? src->channelsPerStream : 1u; c.srcFmt = c.flacSrc ? flac_decode::image_format(c.flacInB) : src ? src->format : 0u;
     c.srcB = src ? pcm_pack::sample_bytes(c.srcFmt) : 0;
     c.wantFloat = nOut > 0 && out != nullptr;
@@ -1333,11 +1334,13 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 const uint64_t e0 = std::min<uint64_t>(k * setBlocks * bs, numFrames), e1 = std::min<uint64_t>((k + 1) * setBlocks * bs, numFrames);
                 const uint64_t base = inres ? resample::inputs_before(inp, inN) : 0;
                 const uint64_t i0 = inres ? resample::inputs_before(inp, inN + e0) - base : e0, i1 = inres ? resample::inputs_before(inp, inN + e1) - base : e1;
-                flacInPlan(*src, i0, (size_t)(i1 - i0), probe);
+                flacInPlan(*src, i0, (size_t)(i1 - i0), probe, call.inMd5);
                 staged = std::max(staged, probe.stagedBytes); frames = std::max(frames, probe.frames.size()); scratch = std::max(scratch, probe.scratchInts);
             }
             rc = ensureFlacIn(staged, std::max<size_t>(frames, 1), std::max<size_t>(scratch, 1), srcG);
             if (rc != kOk) return rc;
+            if (flacInMd5Slots.size() < src->nStreams) flacInMd5Slots.resize(src->nStreams, flac_in_md5::Slot{});      // (slot s is input stream s, hashed or not)
+            if (call.inMd5) { rc = ensureFlacInMd5(); if (rc != kOk) return rc; }
         }
         if (pcm) {
             rc = ensurePcmStaging(pcm->nStreams * (size_t)pcm_pack::stream_stride(outCapFrames, pcmG, pcmFmt) + nOut * sizeof(pcm_pack::ChannelStats), pcmG);
@@ -1446,7 +1449,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             if (flacSrc) {
                 // the FLAC frames that cover the set's input frames, found by binary search in the streams' tables, as they lie in the
                 // caller's buffers: the compressed bytes and nothing more
-                flacInPlan(*src, inres ? inOff : b0 * bs, inres ? inValid : srcValid, flacInSets[half]);
+                flacInPlan(*src, inres ? inOff : b0 * bs, inres ? inValid : srcValid, flacInSets[half], call.inMd5);
                 if (flacInSets[half].stagedBytes > flacInBytes) { result = kInvariantViolation; break; }      // (sized above from the same table)
                 flacInStage(*src, flacInSets[half], half);
             } else if (inres) {
@@ -1484,6 +1487,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             if (nIn) {
                 // (the copy stream is in order: this H2D runs behind the D2H of set k - 2, which waited for that set's render,
                 //  the last reader of this device half)
+                if (call.inMd5) flacInMd5Jobs(*src, flacInSets[half], half);      // (the jobs ride in the staged half, behind the bytes)
                 if (flacSrc) { if (flacInSets[half].stagedBytes) HOST_TRY(hipMemcpyAsync(dFlacIn[half], hFlacIn[half], flacInSets[half].stagedBytes, hipMemcpyHostToDevice, ioStream)); }
                 else if (inres) { if (inStreams * inStride) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], inStreams * inStride, hipMemcpyHostToDevice, ioStream)); }
                 else if (src) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], src->nStreams * srcStride, hipMemcpyHostToDevice, ioStream))
@@ -1496,6 +1500,9 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                     // ran behind the D2H of set k - 2 like every other; the scratch is touched by this stream's kernels only.
                     const int rf = flacInLaunch(flacInSets[half], half, srcG, flacInB, inres ? inValid : srcValid, inres ? inStride : srcStride);
                     if (rf != kOk) { result = rf; break; }
+                    // option "flac_in_md5": directly behind the decode kernels, which left the samples in the scratch; the next set's
+                    // parse, the scratch's next writer, runs behind it on this stream. Nothing waits for it.
+                    if (call.inMd5) { const int rm = flacInMd5Launch(flacInSets[half], half, srcG, flacInB); if (rm != kOk) { result = rm; break; } }
                 }
                 if (inres) {
                     // the input converter in the unpack kernel's place, and the argument below holds for it word for word: dStageIn[half]
@@ -1661,6 +1668,12 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             HOST_TRY(hipEventRecord(evRendered[half], stream));
             HOST_TRY(hipStreamWaitEvent(ioStream, evRendered[half], 0));
             if (flacSrc) HOST_TRY(hipMemcpyAsync(hFlacInErr + half, dFlacInErr + half, sizeof(FlacInError), hipMemcpyDeviceToHost, ioStream));   // the decode's error record
+            if (call.inMd5 && flacInSets[half].md5Finish) {     // the digests this set finished come back with it
+                bool ok = true;
+                for (size_t s = 0; s < flacInSets[half].jobs.size() && ok; ++s)
+                    if (flacInSets[half].jobs[s].finish) ok = hipMemcpyAsync(hFlacInMd5 + 16u * s, flacInMd5Digests() + 16u * s, 16u, hipMemcpyDeviceToHost, ioStream) == hipSuccess;
+                if (!ok) { result = kHipError; break; }
+            }
             if (wantFloat || !packed) { if (nOut && gotBlocks) HOST_TRY(hipMemcpyAsync(hStageOut[half], got, gotBlocks * nOut * bs * sizeof(float), hipMemcpyDeviceToHost, ioStream)); }
             if (pcm) HOST_TRY(hipMemcpyAsync(hPcm[half], dPcm[half], pcmCopy, hipMemcpyDeviceToHost, ioStream));
             if (flac) {     // the length table and the statistics; the frames follow once the table says how many bytes they are (flacDeliver)
@@ -1704,6 +1717,8 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         if (limit && result != kOk) (void)limiterResetLocked(0);
         if (shape && result != kOk) (void)noiseShapeResetLocked();
         if (inres && result != kOk) (void)inputResampleResetLocked(0);   // and the input programme: its clock may be ahead of what was rendered
+        // a call that failed for another reason than a frame that did not decode may have left records and slots apart: the slots break
+        if (call.inMd5 && result != kOk && result != kFlacInput) for (flac_in_md5::Slot& sl : flacInMd5Slots) if (sl.state != flac_in_md5::kOff) sl.state = flac_in_md5::kBroken;
     }
     return result;
 }

@@ -9,6 +9,7 @@ namespace elemhip {
 namespace rl = resource_load;
 namespace fd = flac_decode;
 namespace pp = pcm_pack;
+namespace fi = flac_in_md5;
 
 void Engine::resourceLoadFree() {
     if (loadStream) (void)hipStreamSynchronize(loadStream);
@@ -27,6 +28,8 @@ void Engine::resourceLoadFree() {
     if (dLoadTable) (void)hipFree(dLoadTable);
     if (dLoadRowBase) (void)hipFree(dLoadRowBase);
     if (dLoadRowTable) (void)hipFree(dLoadRowTable);
+    if (dLoadMd5) (void)hipFree(dLoadMd5);
+    dLoadMd5 = nullptr;
     if (loadStream) (void)hipStreamDestroy(loadStream);
     hLoadErr = dLoadErr = nullptr; dLoadSubs = nullptr; dLoadState = nullptr; dLoadScratch = nullptr;
     dLoadTable = nullptr; dLoadRowBase = nullptr; dLoadRowTable = nullptr; loadStream = nullptr;
@@ -108,6 +111,13 @@ int Engine::resourceLoadHost(const ResourceSrc& src, uint32_t fmt, uint64_t N, c
             flacInErrSet = true; flacInErrStream = 0u; flacInErrFrame = bad; flacInErrReason = why;
             return kFlacInput;
         }
+        if (flacInMd5Opt) {         // option "flac_in_md5": the scalar twin over what was decoded, under the device path's rule
+            const uint64_t total = fi::total_of(f.totalSamples, f.frames ? f.frameFirstSamples[f.frames] : 0u);
+            fi::Slot slot{}; flac_md5::Record rec; flac_md5::init(rec);
+            uint64_t lo = 0; bool finish = false;
+            if (fi::advance(slot, f.bits, G, total, f.position, f.position + N, lo, finish)) fi::update_codes(rec, planar, G, 0u, N, f.bits, finish ? r.md5 : nullptr);
+            r.md5State = slot.state == fi::kComplete ? 2u : 1u;
+        }
         image.assign(std::max<size_t>((size_t)N * G * pp::sample_bytes(fmt), 1), 0);
         fd::image_host(f.bits, G, planar, (size_t)N, image.data());
         data = image.data();
@@ -124,7 +134,7 @@ int Engine::resourceLoadHost(const ResourceSrc& src, uint32_t fmt, uint64_t N, c
 // other half's H2D and kernels run; an event per half says when it may be written again.
 int Engine::resourceLoadDevice(const ResourceSrc& src, uint32_t fmt, uint64_t N, const resample::Plan* plan, Resource& r) {
     const uint32_t G = src.channels, P = resourceLoadFramesOpt, B = pp::sample_bytes(fmt);
-    const bool flac = src.format == fd::kFormat;
+    const bool flac = src.format == fd::kFormat, md5 = flac && flacInMd5Opt != 0u;
     const uint64_t outN = rl::out_frames(plan, N), pieces = rl::piece_count(N, P);
     const size_t rowFloats = std::max<size_t>((size_t)outN, (size_t)blockSize);      // (ensureResourceOnDevice's rule: a block at least, zero behind the frames)
 
@@ -136,7 +146,7 @@ int Engine::resourceLoadDevice(const ResourceSrc& src, uint32_t fmt, uint64_t N,
     for (uint64_t j = 0; j < pieces; ++j) {
         const rl::Piece pc = rl::piece_of(plan, N, P, j);
         if (!flac) { pinned = std::max<size_t>(pinned, (size_t)rl::piece_bytes(rl::piece_head(pc.in0, G, fmt), pc.in1 - pc.in0, G, fmt)); continue; }
-        flacInPlan(one, pc.in0, (size_t)(pc.in1 - pc.in0), sets[0]);
+        flacInPlan(one, pc.in0, (size_t)(pc.in1 - pc.in0), sets[0], md5);
         if (sets[0].stagedBytes > 0xFFFFFFFFull || sets[0].scratchInts > 0xFFFFFFFFull) return kInvalidPropertyValue;      // (the records count in 32 bits)
         pinned = std::max(pinned, sets[0].stagedBytes); maxFrames = std::max(maxFrames, sets[0].frames.size()); maxScratch = std::max(maxScratch, sets[0].scratchInts);
     }
@@ -150,6 +160,15 @@ int Engine::resourceLoadDevice(const ResourceSrc& src, uint32_t fmt, uint64_t N,
         if (!dLoadRowTable) HIP_OK(hipMalloc((void**)&dLoadRowTable, rl::kMaxChannels * sizeof(uint16_t)));
         HIP_OK(hipMemcpy(dLoadRowTable, table.data(), G * sizeof(uint16_t), hipMemcpyHostToDevice));
         loadRowGroup = G;
+    }
+
+    // option "flac_in_md5": a record of this load's own at its initial value; the slot is the load's too
+    fi::Slot md5Slot{};
+    if (md5) {
+        if (!dLoadMd5) HIP_OK(hipMalloc((void**)&dLoadMd5, sizeof(flac_md5::Record) + 16u));
+        flac_md5::Record fresh; flac_md5::init(fresh);
+        HIP_OK(hipStreamSynchronize(loadStream));
+        HIP_OK(hipMemcpy(dLoadMd5, &fresh, sizeof fresh, hipMemcpyHostToDevice));
     }
 
     // the rows: the resource's own device buffers, zeroed on the loader's stream in front of the first piece
@@ -207,12 +226,13 @@ int Engine::resourceLoadDevice(const ResourceSrc& src, uint32_t fmt, uint64_t N,
             LOAD_OK(hipMemcpyAsync(dLoadImage[half], hLoad[half], (size_t)a.srcBytes, hipMemcpyHostToDevice, loadStream));
         } else {
             FlacInSet& set = sets[half];
-            flacInPlan(one, pc.in0, (size_t)validIn, set);
+            flacInPlan(one, pc.in0, (size_t)validIn, set, md5);
             const size_t nF = set.frames.size(), tables = nF * sizeof(FlacInFrame) + sizeof(FlacInStream);
             unsigned char* dst = hLoad[half];
             if (nF) std::memcpy(dst, set.frames.data(), nF * sizeof(FlacInFrame));
             std::memcpy(dst + nF * sizeof(FlacInFrame), set.streams.data(), sizeof(FlacInStream));
             if (set.len[0]) std::memcpy(dst + tables, src.flac->data + set.from[0], (size_t)set.len[0]);
+            if (md5) { set.jobs[0] = flacInMd5Job(*src.flac, set, 0, md5Slot); std::memcpy(dst + set.jobsOff, set.jobs.data(), sizeof(fi::Job)); }
             LOAD_OK(hipMemcpyAsync(dLoadFlac[half], dst, set.stagedBytes, hipMemcpyHostToDevice, loadStream));
             LOAD_OK(hipMemsetAsync(dLoadErr + half, 0, sizeof(FlacInError), loadStream));
             a.head = 0u; a.srcBytes = pp::stream_stride(validIn, G, fmt);
@@ -226,6 +246,12 @@ int Engine::resourceLoadDevice(const ResourceSrc& src, uint32_t fmt, uint64_t N,
             if (nF * G > loadFrameCap || set.scratchInts > loadScratchCap || set.stagedBytes > dLoadFlacBytes || a.srcBytes > dLoadImageBytes) return drop(kInvariantViolation);
             LOAD_OK(launch_flac_decode(loadStream, d, set.frames.data(), set.streams.data(), set.stagedBytes - tables, set.scratchInts));
             LOAD_OK(hipMemcpyAsync(hLoadErr + half, dLoadErr + half, sizeof(FlacInError), hipMemcpyDeviceToHost, loadStream));
+            if (md5) {      // the piece's new samples enter the load's digest behind its decode, in front of the next piece's, which reuses the scratch
+                FlacInMd5Args m{};
+                m.scratch = dLoadScratch; m.records = reinterpret_cast<flac_md5::Record*>(dLoadMd5); m.digests = dLoadMd5 + sizeof(flac_md5::Record);
+                m.jobs = reinterpret_cast<const fi::Job*>(dLoadFlac[half] + set.jobsOff); m.numStreams = 1u; m.G = G; m.bits = src.flac->bits;
+                LOAD_OK(launch_flac_in_md5(loadStream, m, set.jobs.data(), set.scratchInts));
+            }
         }
         if (a.srcBytes > dLoadImageBytes) return drop(kInvariantViolation);
         LOAD_OK(plan ? launch_resource_convert(loadStream, a, fmt) : launch_resource_copy(loadStream, a, fmt));
@@ -234,6 +260,10 @@ int Engine::resourceLoadDevice(const ResourceSrc& src, uint32_t fmt, uint64_t N,
     LOAD_OK(hipStreamSynchronize(loadStream));
 #undef LOAD_OK
     if (failed(0) || failed(1)) return drop(kFlacInput);
+    if (md5) {      // a load that covered the stream from sample 0 to its end leaves its digest with the resource
+        r.md5State = md5Slot.state == fi::kComplete ? 2u : 1u;
+        if (r.md5State == 2u && hipMemcpy(r.md5, dLoadMd5 + sizeof(flac_md5::Record), 16u, hipMemcpyDeviceToHost) != hipSuccess) return drop(kHipError);
+    }
     r.devCh[0] = DevBuf{};                          // (channel 0 is `dev`)
     r.onDevice = true; r.deviceChannels = G; r.deviceFrames = outN;
     return kOk;
@@ -302,6 +332,16 @@ int Engine::sharedResourceInfo(const std::string& name, uint32_t* channels, uint
     if (it == resources.end()) return kInvalidPropertyValue;
     if (channels) *channels = (uint32_t)it->second->numChannels();
     if (frames) *frames = it->second->frames(0);
+    return kOk;
+}
+
+int Engine::sharedResourceMd5(const std::string& name, uint8_t digest[16], uint32_t* state) {
+    std::lock_guard<std::mutex> control(ctl);
+    RenderGuard lock(*this);
+    auto it = resources.find(name);
+    if (it == resources.end()) return kInvalidPropertyValue;
+    if (state) *state = it->second->md5State;
+    if (digest) std::memcpy(digest, it->second->md5, 16u);
     return kOk;
 }
 

@@ -1,6 +1,6 @@
 // flac_md5.h — the STREAMINFO MD5 of FLAC delivery (option "flac_md5"; flac_md5.hip, engine_flac.cpp): RFC 1321 over the bytes
-// process_blocks_pcm would deliver for the stream in s16 / s24 — for frame f, then channel g, the low bits / 8 bytes of the
-// two's-complement code, little-endian. One Record per stream carries the digest from launch set to launch set: the chaining value,
+// process_blocks_pcm would deliver for the stream in s16 / s24 — for frame f, then channel g, the low B = (bits + 7) / 8 bytes of the
+// two's-complement code, little-endian (delivery: 16 / 24 bits; the input side, flac_in_md5.h, walks the same schedule at 8 .. 24). One Record per stream carries the digest from launch set to launch set: the chaining value,
 // the byte count and the bytes behind the last whole 64-byte block.
 //
 // MD5 is a serial chain of 64-byte blocks inside one stream; what is parallel is the gather of the message words and, per block, the
@@ -86,7 +86,7 @@ struct Job {
 };
 PCM_FD Job make_job(uint64_t bytesSoFar, uint32_t G, uint32_t first, uint64_t count, uint32_t bits, bool finish) {
     Job j;
-    j.G = G; j.B = bits / 8u; j.FB = G * j.B; j.first = first; j.finish = finish ? 1u : 0u;
+    j.G = G; j.B = (bits + 7u) / 8u; j.FB = G * j.B; j.first = first; j.finish = finish ? 1u : 0u;
     j.fill = (uint32_t)(bytesSoFar & 63u);
     j.total = j.fill + count * j.FB;
     j.bitLen = (bytesSoFar + count * j.FB) * 8u;
@@ -130,7 +130,7 @@ PCM_FD void next_chunk(const Job& j, Chunk& c) {
 
 // byte r of a frame's G * B bytes; codes(g, f): the code of channel g at frame f
 template <class Codes> PCM_FD uint32_t frame_byte(const Job& j, const Codes& codes, uint32_t f, uint32_t r) {
-    const uint32_t g = j.B == 2u ? r >> 1 : r / 3u, k = r - g * j.B;
+    const uint32_t g = j.B == 2u ? r >> 1 : j.B == 1u ? r : r / 3u, k = r - g * j.B;
     return ((uint32_t)codes(g, f) >> (8u * k)) & 0xFFu;
 }
 template <class Codes> PCM_FD uint32_t chunk_byte(const Job& j, const Chunk& c, const uint8_t* tail, const Codes& codes, uint32_t v) {

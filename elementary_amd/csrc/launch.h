@@ -8,6 +8,7 @@
 #include "limiter.h"
 #include "flac_decode.h"
 #include "flac_md5.h"
+#include "flac_in_md5.h"
 #include "noise_shape.h"
 #include "spectrum.h"
 
@@ -228,6 +229,15 @@ struct FlacDecodeArgs {
 // (the host's copies of the two tables are checked against the buffers' sizes before anything is launched)
 hipError_t launch_flac_decode(hipStream_t s, const FlacDecodeArgs& a, const FlacInFrame* hostFrames, const FlacInStream* hostStreams,
                               size_t stagedBytes, size_t scratchInts);
+// ---- the STREAMINFO MD5 of FLAC inputs and resources (flac_in_md5.hip): behind the decode kernels, flac_in_md5.h ----
+struct FlacInMd5Args {
+    const int32_t*  scratch;        // the decoder's: the restored samples of the set's covered frames
+    flac_md5::Record* records;      // [numStreams], carried from launch to launch
+    uint8_t*        digests;        // [numStreams][16], 4-byte aligned: a stream's written with its job's `finish`
+    const flac_in_md5::Job* jobs;   // [numStreams], 16-byte aligned, staged with the set
+    uint32_t        numStreams, G, bits, pad;
+};
+hipError_t launch_flac_in_md5(hipStream_t s, const FlacInMd5Args& a, const flac_in_md5::Job* hostJobs, size_t scratchInts);
 // ---- resource loader (resource_load.hip): a staged piece of a source file into the resource's planar rows, resource_load.h ----
 struct ResourceLoadArgs {
     const unsigned char* src;       // the staged piece, 16-byte aligned, `srcBytes` (whole 16-byte lines): sample (f, g) of its frame f lies at

@@ -33,8 +33,10 @@ class FlacReader:
     ``n`` samples, their slice of the table and the position — the compressed bytes are what crosses the host link, the samples are
     decoded on the GPU (``flac_decode.hip``). Fixed-block-size streams of 8 / 12 / 16 / 20 / 24 bits with blocks of up to 16384 samples.
 
-    The STREAMINFO MD5 is NOT verified: the decoded samples never reach the host; ``md5`` holds the 16 bytes the file announces (all
-    zero: none). Every frame's CRC-16 is. Unlike ``WavReader``,
+    ``md5`` holds the 16 bytes STREAMINFO announces (all zero: none) and every chunk carries them. They are verified where the caller
+    asks for it — ``verify_input=True`` of ``process_wav`` / ``process_pcm_io`` / ``process_flac`` / ``master_wav``, ``verify=True`` of
+    ``update_virtual_file_system_files`` — against a digest the GPU computes over the decoded samples (option ``flac_in_md5``), which
+    never reach the host. Every frame's CRC-16 is checked always. Unlike ``WavReader``,
     which streams, the whole (compressed) file is read into memory at construction: the index needs every frame header."""
 
     def __init__(self, path):
@@ -82,12 +84,16 @@ class FlacReader:
         self._pos += n
         p1 = min(p0 + n, self.frames)
         if p0 >= p1:
-            return FlacChunk(self._data[:0], [0], [p0], self.channels, self.bits, self.frames, p0, n)
+            return self._announce(FlacChunk(self._data[:0], [0], [p0], self.channels, self.bits, self.frames, p0, n))
         j0 = int(np.searchsorted(self._first, p0, side="right")) - 1
         j1 = int(np.searchsorted(self._first, p1 - 1, side="right")) - 1
         base = int(self._off[j0])
-        return FlacChunk(self._data[base:int(self._off[j1 + 1])], self._off[j0:j1 + 2] - np.uint64(base), self._first[j0:j1 + 2],
-                         self.channels, self.bits, self.frames, p0, n)
+        return self._announce(FlacChunk(self._data[base:int(self._off[j1 + 1])], self._off[j0:j1 + 2] - np.uint64(base), self._first[j0:j1 + 2],
+                                        self.channels, self.bits, self.frames, p0, n))
+
+    def _announce(self, chunk):
+        chunk.md5 = self.md5            # what the file says its samples hash to (``verify_input``)
+        return chunk
 
     def close(self) -> None:
         self._data = None

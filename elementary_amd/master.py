@@ -21,7 +21,7 @@ def _reader(path):
 
 
 def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, target_lufs: float = -14.0, ceiling_dbtp: float = -1.0,
-               fmt: str = "s24", block_size: int = 512, oversample: int = 1, noise_shape=None, **limiter) -> Dict[str, Any]:
+               fmt: str = "s24", block_size: int = 512, oversample: int = 1, noise_shape=None, verify_input: bool = False, **limiter) -> Dict[str, Any]:
     """``in_path`` -> ``out_path`` (format ``fmt`` — 's16', 's24', 'f32', or 'flac16' / 'flac24' for a FLAC file encoded on the GPU —
     the input's rate and channel count) at ``target_lufs`` integrated loudness under a
     true-peak ceiling of ``ceiling_dbtp``. ``limiter``: further limiter parameters (``lookahead_ms``, ``release_ms``, ``link``).
@@ -29,6 +29,10 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
     'limited_frames', 'over', 'nonfinite'}``. Where the limiter worked the output is quieter than the target by what it took away; the
     output's metered true peak may exceed the ceiling slightly (``OfflineRenderer.initialize``). An input that passes no loudness
     gate (silence) raises ``ValueError``: there is no gain that brings it to a target.
+
+    ``verify_input`` (a FLAC input): the metering pass also hashes the decoded samples on the GPU (option ``flac_in_md5``) and compares
+    the digest with what the file's STREAMINFO announces; the result carries ``input_md5`` (['ok'], ['absent'], ...), and a mismatch
+    raises ``FlacMd5Mismatch`` BEFORE the second pass opens the output: a damaged source does not become a deliverable.
 
     Both passes meter on the same grid: the limiter delays its output by ``latency_frames``, so the first pass puts as many frames of
     silence in front of the input — the second pass's figures then differ from the first's by the gain and the limiter alone.
@@ -76,12 +80,18 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
     del probe
     first = renderer()
     first.process_pcm_io([silence(latency)], sil_fmt, latency * k)      # (every call renders a multiple of k engine frames: it consumes its frames / k)
+    verify = bool(verify_input) and in_fmt == "flac"
+    verdicts = {}
     with _reader(str(in_path)) as r:
+        if verify:
+            first.verify_begin()
         done = 0
         while done < frames:
             m = min(1 << 20, frames - done)
             first.process_pcm_io([r.read(m)], in_fmt, m * k)
             done += m
+        if verify:
+            verdicts = {"input_md5": first.verify_end([r.md5])}
     if k > 1:
         # what the second pass renders behind the file to take the converters' latencies out (OfflineRenderer._file_span)
         tail = first.resample()["latency_frames"] + (2 * first.input_resample()["latency_frames"] + k) // (2 * k)
@@ -94,7 +104,7 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
     stats = second.process_wav(str(in_path), str(out_path), fmt)
     lim = second.limiter()
     shaped = {"saturated": int(np.sum(second.noise_shape()["saturated"]))} if shape else {}
-    return {**shaped, "input_lufs": float(measured["integrated_lufs"]), "input_true_peak_dbtp": float(measured["true_peak_dbtp"]),
+    return {**shaped, **verdicts, "input_lufs": float(measured["integrated_lufs"]), "input_true_peak_dbtp": float(measured["true_peak_dbtp"]),
             "output_lufs": float(stats["integrated_lufs"]), "output_true_peak_dbtp": float(stats["true_peak_dbtp"]), "gain_db": gain_db,
             "max_reduction_db": float(lim["max_reduction_db"]), "max_reduction": float(np.max(lim["max_reduction"], initial=0.0)),
             "limited_frames": int(np.sum(lim["limited_frames"])), "over": int(np.sum(stats["over"])), "nonfinite": int(np.sum(stats["nonfinite"]))}

@@ -299,14 +299,48 @@ class OfflineRenderer:
         planar = np.concatenate([p[2] for p in parts], axis=1) if want_float else None
         return streams, stats, planar
 
+    # -- option flac_in_md5: the STREAMINFO MD5 of FLAC inputs, computed on the GPU and compared here ------------------------------
+    def verify_begin(self) -> None:
+        """A programme of FLAC inputs that is to be verified starts: option ``flac_in_md5`` on, every input slot reset."""
+        self._rt.set_option("flac_in_md5", 1)
+        self._rt.flac_in_md5_reset()
+
+    def verify_end(self, expected: Sequence[Optional[bytes]], output=None) -> List[str]:
+        """The programme's verdicts, one per input stream: ``expected[s]`` is the MD5 input ``s`` announces (``FlacReader.md5``;
+        None or sixteen zeros: none). 'ok', 'absent' (nothing announced: not a mismatch), 'incomplete' (the render ended before the
+        stream did, started behind its first sample or skipped a part) or 'mismatch' — which raises ``FlacMd5Mismatch`` for the
+        first such input, with ``output`` (what was written, left in place) named in it. Also kept as ``self.input_md5``."""
+        from .runtime import FlacMd5Mismatch, flac_md5_verdict
+        got = self._rt.flac_in_md5()
+        verdicts = []
+        for s, exp in enumerate(expected):
+            exp = bytes(16) if exp is None else bytes(exp)
+            have = s < len(got["state"])
+            verdicts.append(flac_md5_verdict(got["state"][s] if have else 0, got["md5"][s] if have else bytes(16), exp))
+        self.input_md5 = verdicts
+        for s, v in enumerate(verdicts):
+            if v == "mismatch":
+                err = FlacMd5Mismatch(s, expected[s], got["md5"][s], output)
+                err.input_md5 = verdicts
+                raise err
+        return verdicts
+
     def process_flac(self, inputs: Sequence[np.ndarray], num_streams: int, channels_per_stream: int, num_frames: int, bits: int = 16,
-                     dither_seed: Optional[int] = None, sample_time: Optional[int] = None, drop: int = 0, take: Optional[int] = None, in_fmt=None):
+                     dither_seed: Optional[int] = None, sample_time: Optional[int] = None, drop: int = 0, take: Optional[int] = None, in_fmt=None,
+                     verify_input: bool = False):
         """``process_pcm`` delivered as FLAC frames encoded on the GPU (``Runtime.process_blocks_flac``): returns ``(streams, stats)``,
         one ``bytes`` per stream with the whole FLAC frames this call completed in the engine's FLAC programme — the open frame stays on
         the device until the next call or ``flac_flush()``. Decoded, the samples are ``process_pcm``'s s16 / s24 codes for the same
         render. With listeners attached the render walks ``event_window_blocks()`` windows with the blockwise relay between them; the
         bytes are those of one call. ``drop`` / ``take``: of the frames delivered, the first ``drop`` stay out of the programme and at
-        most ``take`` enter it. ``in_fmt``: the inputs are PCM stream arrays in that format (``process_pcm_io``'s), not planar floats."""
+        most ``take`` enter it. ``in_fmt``: the inputs are PCM stream arrays in that format (``process_pcm_io``'s), not planar floats.
+        ``verify_input`` (``in_fmt`` 'flac'): this call is a programme of its own for option ``flac_in_md5`` — the chunks' decoded samples
+        are hashed on the GPU and compared with the MD5 each chunk carries (``FlacChunk.md5``, set by ``FlacReader.read``); the
+        statistics carry ``input_md5``, one verdict per input (``verify_end``), and a mismatch raises ``FlacMd5Mismatch`` after the
+        render (the frames this call emitted stay in the FLAC programme)."""
+        verify = bool(verify_input) and _is_flac(in_fmt)
+        if verify:
+            self.verify_begin()
         flac = getattr(self._rt, "process_blocks_flac", None)
         if flac is None:
             raise RuntimeError("this engine has no FLAC delivery (process_blocks_flac)")
@@ -354,10 +388,13 @@ class OfflineRenderer:
                 for cb in self._listeners.get(kind, []):
                     cb(payload)
         if len(parts) == 1:
-            return parts[0]
-        streams = [b"".join(p[0][s] for p in parts) for s in range(int(num_streams))]
-        stats = {"peak": np.max([p[1]["peak"] for p in parts], axis=0), "over": np.sum([p[1]["over"] for p in parts], axis=0, dtype=np.uint64),
-                 "nonfinite": np.sum([p[1]["nonfinite"] for p in parts], axis=0, dtype=np.uint64)}
+            streams, stats = parts[0]
+        else:
+            streams = [b"".join(p[0][s] for p in parts) for s in range(int(num_streams))]
+            stats = {"peak": np.max([p[1]["peak"] for p in parts], axis=0), "over": np.sum([p[1]["over"] for p in parts], axis=0, dtype=np.uint64),
+                     "nonfinite": np.sum([p[1]["nonfinite"] for p in parts], axis=0, dtype=np.uint64)}
+        if verify:
+            stats = dict(stats, input_md5=self.verify_end([getattr(a, "md5", None) for a in ins]))
         return streams, stats
 
     def flac_flush(self):
@@ -633,7 +670,7 @@ class OfflineRenderer:
 
     def process_pcm_io(self, in_streams: Sequence[np.ndarray], in_fmt, num_frames: Optional[int] = None, out_fmt=None,
                        num_streams: Optional[int] = None, channels_per_stream: Optional[int] = None, dither_seed: Optional[int] = None,
-                       want_float: bool = False, sample_time: Optional[int] = None):
+                       want_float: bool = False, sample_time: Optional[int] = None, verify_input: bool = False):
         """``process`` / ``process_pcm`` fed with interleaved PCM that is unpacked on the GPU (``Runtime.process_blocks_pcm_io``):
         ``in_streams`` are arrays in stream layout (``WavReader.read``, or what ``process_pcm`` returns) that together hold the
         ``num_input_channels`` input channels; a stream shorter than ``num_frames`` is padded with silence. ``in_fmt`` 'flac': the
@@ -641,7 +678,13 @@ class OfflineRenderer:
         float32 ``[num_output_channels, num_frames]``; else ``(streams, stats, planar)`` as ``process_pcm`` does. With listeners attached
         the render walks ``event_window_blocks()`` windows with the blockwise relay between them, as ``process`` does. With
         ``initialize(limiter=...)`` what comes back is limited and carries the limiter's latency: frame n is the limited render at
-        n - latency_frames."""
+        n - latency_frames. ``verify_input`` (``in_fmt`` 'flac'): this call is a programme of its own for option ``flac_in_md5`` — the
+        chunks' decoded samples are hashed on the GPU and compared with the MD5 each chunk carries (``FlacChunk.md5``, set by
+        ``FlacReader.read``); the verdicts (``verify_end``) are ``self.input_md5`` and, where statistics come back, their
+        ``input_md5``; a mismatch raises ``FlacMd5Mismatch`` after the render."""
+        verify = bool(verify_input) and _is_flac(in_fmt)
+        if verify:
+            self.verify_begin()
         pcm_io = getattr(self._rt, "process_blocks_pcm_io", None)
         if pcm_io is None:
             raise RuntimeError("this engine takes no PCM input (process_blocks_pcm_io)")
@@ -683,22 +726,30 @@ class OfflineRenderer:
             for kind, payload in events:
                 for cb in self._listeners.get(kind, []):
                     cb(payload)
-        if len(parts) == 1:
-            return parts[0]
+        verdicts = self.verify_end([getattr(a, "md5", None) for a in ins]) if verify else None
         if out_fmt is None:
-            return np.concatenate(parts, axis=1)
-        streams = [np.concatenate([p[0][s] for p in parts]) for s in range(int(num_streams))]
-        stats = {"peak": np.max([p[1]["peak"] for p in parts], axis=0), "over": np.sum([p[1]["over"] for p in parts], axis=0, dtype=np.uint64),
-                 "nonfinite": np.sum([p[1]["nonfinite"] for p in parts], axis=0, dtype=np.uint64)}
-        planar = np.concatenate([p[2] for p in parts], axis=1) if want_float else None
+            return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=1)
+        if len(parts) == 1:
+            streams, stats, planar = parts[0]
+        else:
+            streams = [np.concatenate([p[0][s] for p in parts]) for s in range(int(num_streams))]
+            stats = {"peak": np.max([p[1]["peak"] for p in parts], axis=0), "over": np.sum([p[1]["over"] for p in parts], axis=0, dtype=np.uint64),
+                     "nonfinite": np.sum([p[1]["nonfinite"] for p in parts], axis=0, dtype=np.uint64)}
+            planar = np.concatenate([p[2] for p in parts], axis=1) if want_float else None
+        if verify:
+            stats = dict(stats, input_md5=verdicts)
         return streams, stats, planar
 
     def process_wav(self, in_paths, out_paths, out_fmt="s16", channels_per_stream: Optional[int] = None, num_frames: Optional[int] = None,
-                    dither_seed: Optional[int] = None, chunk_frames: int = 1 << 20):
+                    dither_seed: Optional[int] = None, chunk_frames: int = 1 << 20, verify_input: bool = False):
         """RIFF/WAVE files through the graph into RIFF/WAVE files, ``chunk_frames`` (rounded to whole blocks) per engine call; the samples
         cross the host as they lie in the files and are converted on the GPU in both directions (``out_fmt`` 'flac16' / 'flac24': FLAC
         files instead, encoded on the GPU — ``write_flac``'s). An input that starts with ``fLaC`` is read by ``FlacReader``: its frames
-        cross the host compressed and are decoded on the GPU (the STREAMINFO MD5 is not verified). ``in_paths``: one name or a list —
+        cross the host compressed and are decoded on the GPU; with ``verify_input`` the decoded samples' MD5 is computed there too (option
+        ``flac_in_md5``: no sample reaches the host for it) and compared with what each file's STREAMINFO announces — the statistics
+        then carry ``input_md5``, one of 'ok' / 'absent' / 'incomplete' / 'mismatch' per input file (``verify_end``), and a mismatch
+        raises ``FlacMd5Mismatch`` AFTER the output files have been closed: they are left in place and named in the exception,
+        deleting them is the caller's decision. ``in_paths``: one name or a list —
         the files' channels become the input channels in file order (files of one format, one channel count and the renderer's
         sample rate — or, with ``initialize(input_sample_rate=...)``, that rate: a file of F frames then renders ceil(F L / M) engine
         frames, L / M = engine rate / input rate, and the input converter's latency is taken out with the others, to under half a
@@ -744,11 +795,16 @@ class OfflineRenderer:
                 total, skip, keep = self._file_span(max(r.frames for r in readers), input_frames=True)
             chunk = max(bs, (int(chunk_frames) // bs) * bs)
             in_fmt = readers[0].fmt if readers else "s16"
+            verify = bool(verify_input) and bool(readers) and _is_flac(in_fmt)
+            if verify:
+                self.verify_begin()
             if flac_bits is not None:         # FLAC files: encoded on the GPU, the latencies left out in front of the encoder
                 def pull(m):
                     return [r.read(self._rt.input_resample_frames(m) if inres else m) for r in readers]
-                return self._flac_files(outs, pull, total, skip, keep, flac_bits, S, G, dither_seed, chunk, in_fmt=in_fmt if readers else None)
-            writers = [WavWriter(p, fmt, G, self.output_sample_rate) for p in outs]
+                stats = self._flac_files(outs, pull, total, skip, keep, flac_bits, S, G, dither_seed, chunk, in_fmt=in_fmt if readers else None)
+                total = 0                     # (rendered)
+            else:
+                writers = [WavWriter(p, fmt, G, self.output_sample_rate) for p in outs]
             for k in range(0, total, chunk):
                 m = min(chunk, total - k)
                 ni = self._rt.input_resample_frames(m) if inres else m
@@ -764,23 +820,36 @@ class OfflineRenderer:
                 else:
                     stats = {"peak": np.maximum(stats["peak"], st["peak"]), "over": stats["over"] + st["over"], "nonfinite": stats["nonfinite"] + st["nonfinite"]}
         finally:
+            expected = [getattr(r, "md5", None) for r in readers]
             for x in readers + writers:
                 x.close()
-        return self._with_loudness(stats)
+        if flac_bits is None:
+            stats = self._with_loudness(stats)
+        if verify:          # (the outputs are closed: a mismatch leaves them in place and names them)
+            stats = dict(stats or {}, input_md5=self.verify_end(expected, output=outs))
+        return stats
 
     def update_virtual_file_system(self, vfs: Dict[str, np.ndarray]) -> None:
         for k, v in vfs.items():
             self._rt.add_shared_resource(k, v)
 
-    def update_virtual_file_system_files(self, files: Dict[str, str], resample: bool = True) -> Dict[str, bool]:
+    def update_virtual_file_system_files(self, files: Dict[str, str], resample: bool = True, verify: bool = False) -> Dict[str, bool]:
         """Shared resources straight from audio files, decoded on the GPU (``Runtime.add_shared_resource_pcm``): ``{name: path}``. A
         file that starts with ``fLaC`` is read by ``FlacReader`` (its compressed frames cross the host link), anything else by
         ``WavReader`` (s16 / s24 / f32). A file whose rate is not the engine's is converted with the centred filter, so it plays at its
         own pitch and length; ``resample=False`` takes its samples as they are, as ``update_virtual_file_system`` does with floats.
-        Returns ``{name: inserted}`` (False: the name was taken)."""
+        Returns ``{name: inserted}`` (False: the name was taken). ``verify``: the samples decoded from a FLAC file are hashed on the GPU
+        during the load (option ``flac_in_md5``) and the digest — of the FILE's samples, also where the resource is converted — is
+        compared with what its STREAMINFO announces; ``self.resource_md5[name]`` is 'ok' / 'absent' / 'incomplete' / 'mismatch', and a
+        mismatch raises ``FlacMd5Mismatch`` (``.stream``: the name) once that file is loaded. The resource STAYS under its name
+        (resources are insert-only): pruning it, or never using it, is the caller's decision."""
         from .flac import FlacReader
+        from .runtime import FlacMd5Mismatch, flac_md5_verdict
         from .wav import WavReader
         done = {}
+        if verify:
+            self._rt.set_option("flac_in_md5", 1)
+            self.resource_md5 = getattr(self, "resource_md5", {})
         for name, path in files.items():
             with open(path, "rb") as f:
                 is_flac = f.read(4) == b"fLaC"
@@ -789,6 +858,11 @@ class OfflineRenderer:
                 rate = reader.sample_rate if resample else None
                 data = reader.read(reader.frames)
                 done[name] = self._rt.add_shared_resource_pcm(name, data, None if is_flac else reader.fmt, reader.channels, rate)
+                if verify and is_flac and done[name]:
+                    got = self._rt.shared_resource_md5(name)
+                    self.resource_md5[name] = flac_md5_verdict(got["state"], got["md5"], reader.md5)
+                    if self.resource_md5[name] == "mismatch":
+                        raise FlacMd5Mismatch(name, reader.md5, got["md5"])
             finally:
                 reader.close()
         return done

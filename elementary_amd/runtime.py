@@ -152,6 +152,14 @@ def load_library() -> C.CDLL:
         lib.elemhip_flac_decode.restype = C.c_int
         lib.elemhip_flac_in_error.argtypes = [C.c_void_p, _u32p, _u64p, _u32p]
         lib.elemhip_flac_in_error.restype = C.c_int
+        lib.elemhip_flac_in_md5.argtypes = [C.c_void_p, _u8p, _u32p, _u64p, C.c_size_t, _szp]
+        lib.elemhip_flac_in_md5.restype = C.c_int
+        lib.elemhip_flac_in_md5_reset.argtypes = [C.c_void_p]
+        lib.elemhip_flac_in_md5_reset.restype = C.c_int
+        lib.elemhip_flac_in_md5_update.argtypes = [_u8p, C.POINTER(C.POINTER(C.c_int32)), C.c_uint32, C.c_size_t, C.c_uint32]
+        lib.elemhip_flac_in_md5_update.restype = C.c_int
+        lib.elemhip_shared_resource_md5.argtypes = [C.c_void_p, C.c_char_p, _u8p, _u32p]
+        lib.elemhip_shared_resource_md5.restype = C.c_int
         lib.elemhip_add_shared_resource_pcm.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(_ResourceSrc), C.POINTER(C.c_int)]
         lib.elemhip_add_shared_resource_pcm.restype = C.c_int
         lib.elemhip_shared_resource_info.argtypes = [C.c_void_p, C.c_char_p, _u32p, _u64p]
@@ -396,6 +404,46 @@ class FlacMd5:
         return out.tobytes()
 
 
+class FlacInMd5(FlacMd5):
+    """The host twin of the MD5 the GPU computes over FLAC inputs and resources (option ``flac_in_md5``;
+    ``elemhip_flac_in_md5_update``): the digest STREAMINFO announces — for every stream sample, then channel, the low
+    ``(bits + 7) // 8`` bytes of the code, little-endian. ``update(codes[G, n], bits)`` takes 8 / 12 / 16 / 20 / 24 bits and 1 .. 8
+    channels, piece by piece; ``digest()`` leaves the record as it is."""
+
+    def update(self, codes, bits: int = 16) -> "FlacInMd5":
+        import numpy as np
+        a = np.ascontiguousarray(codes, dtype=np.int32)
+        if a.ndim == 1:
+            a = a[None, :]
+        ch, n = int(a.shape[0]), int(a.shape[1])
+        rows = (C.POINTER(C.c_int32) * max(1, ch))(*[a[c].ctypes.data_as(C.POINTER(C.c_int32)) for c in range(ch)])
+        self._check(self._lib.elemhip_flac_in_md5_update(self._p(), rows, ch, n, int(bits)), "update")
+        return self
+
+
+class FlacMd5Mismatch(ElemHipError):
+    """A FLAC input or resource whose decoded samples do not have the MD5 its STREAMINFO announces (``verify_input=True`` /
+    ``verify=True``): ``.stream`` (the input's index, or the resource's name), ``.expected`` (the file's 16 bytes), ``.computed`` (the
+    GPU's) and ``.output`` (the files the render wrote before the mismatch was known — closed and left in place; None where nothing was
+    written)."""
+
+    def __init__(self, stream, expected: bytes, computed: bytes, output=None):
+        self.stream, self.expected, self.computed, self.output = stream, bytes(expected), bytes(computed), output
+        where = f"; the output was written and is left in place: {output}" if output else ""
+        super().__init__(f"FLAC input {stream!r}: the decoded samples' MD5 {self.computed.hex()} is not the {self.expected.hex()} STREAMINFO announces{where}")
+
+
+def flac_md5_verdict(state: int, computed: bytes, expected: bytes) -> str:
+    """What a slot (``Runtime.flac_in_md5``) or a resource (``Runtime.shared_resource_md5``) says about a file that announces
+    ``expected``: 'absent' (sixteen zeros: "not computed"), 'incomplete' (the stream was not hashed from sample 0 to its end), 'ok' or
+    'mismatch'."""
+    if bytes(expected) == bytes(16):
+        return "absent"
+    if int(state) != 2:
+        return "incomplete"
+    return "ok" if bytes(computed) == bytes(expected) else "mismatch"
+
+
 class _FlacIn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("bytes", C.c_uint64), ("frame_offsets", C.c_void_p), ("frame_first_samples", C.c_void_p),
                 ("frames", C.c_uint64), ("channels", C.c_uint32), ("bits", C.c_uint32), ("total_samples", C.c_uint64), ("position", C.c_uint64)]
@@ -422,6 +470,7 @@ class FlacChunk:
         if len(self.offsets) != len(self.first_samples) or len(self.offsets) < 1:
             raise ValueError("a FLAC table holds frames + 1 entries of offset and first sample")
         self.channels, self.bits, self.total_samples, self.position, self.count = int(channels), int(bits), int(total_samples), int(position), int(count)
+        self.md5 = None         # the MD5 the stream's STREAMINFO announces, where the chunk comes from a file (FlacReader.read)
 
     @property
     def frames(self) -> int:
@@ -429,7 +478,9 @@ class FlacChunk:
 
     def at(self, offset: int, count: int) -> "FlacChunk":
         """The same frames read from ``position + offset`` on for ``count`` samples (the engine looks the covering frames up itself)."""
-        return FlacChunk(self.data, self.offsets, self.first_samples, self.channels, self.bits, self.total_samples, self.position + int(offset), count)
+        c = FlacChunk(self.data, self.offsets, self.first_samples, self.channels, self.bits, self.total_samples, self.position + int(offset), count)
+        c.md5 = self.md5
+        return c
 
     def struct(self) -> "_FlacIn":
         return _FlacIn(self.data.ctypes.data, self.data.size, self.offsets.ctypes.data, self.first_samples.ctypes.data, self.frames,
@@ -580,6 +631,19 @@ class Runtime(CRuntime):
             err.code = rc
             raise err
         return {"channels": int(ch.value), "frames": int(fr.value)}
+
+    def shared_resource_md5(self, name: str) -> Dict[str, Any]:
+        """``elemhip_shared_resource_md5``: ``{'state', 'md5'}`` — what the load of a FLAC resource left under option ``flac_in_md5``:
+        state 0 not hashed (the option was off, or the source was no FLAC), 1 incomplete (the load did not cover the stream from
+        sample 0 to its end), 2 ``md5`` is the digest of the FILE's samples (also where the resource was rate-converted)."""
+        import numpy as np
+        st, out = C.c_uint32(0), np.zeros(16, dtype=np.uint8)
+        rc = self._lib.elemhip_shared_resource_md5(self._h, name.encode(), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st))
+        if rc != 0:
+            err = ElemHipError(f"elemhip_shared_resource_md5 failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return {"state": int(st.value), "md5": out.tobytes()}
 
     def shared_resource_read(self, name: str, channel: Optional[int] = None, first: int = 0, count: Optional[int] = None):
         """``elemhip_shared_resource_read``: the floats the nodes see — one channel's frames ``[first, first + count)``, or with
@@ -848,6 +912,33 @@ class Runtime(CRuntime):
             err.code = rc
             raise err
         return {"stream": s.value, "frame": f.value, "reason": r.value, "text": FLAC_IN_REASONS.get(r.value, str(r.value))}
+
+    def flac_in_md5(self) -> Dict[str, Any]:
+        """``elemhip_flac_in_md5`` (option ``flac_in_md5``): ``{'state': [...], 'md5': [bytes, ...], 'hashed': [...]}``, one entry per
+        slot — input stream ``s`` of a call is slot ``s``. state 0 off or never fed, 1 running, 2 complete (``md5`` holds the 16 bytes
+        STREAMINFO should announce), 3 broken until ``flac_in_md5_reset`` (a gap, a frame that did not decode, another stream under a
+        running slot); ``md5`` is all zero unless the state is 2; ``hashed``: stream samples in the digest. Waits for what is in flight."""
+        import numpy as np
+        n = C.c_size_t(0)
+        rc = self._lib.elemhip_flac_in_md5(self._h, None, None, None, 0, C.byref(n))
+        S = int(n.value)
+        dig, st, hs = np.zeros((max(S, 1), 16), dtype=np.uint8), np.zeros(max(S, 1), dtype=np.uint32), np.zeros(max(S, 1), dtype=np.uint64)
+        if rc == 0 and S:
+            rc = self._lib.elemhip_flac_in_md5(self._h, dig.ctypes.data_as(C.POINTER(C.c_uint8)), st.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               hs.ctypes.data_as(C.POINTER(C.c_uint64)), S, C.byref(n))
+        if rc != 0:
+            err = ElemHipError(f"elemhip_flac_in_md5 failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
+        return {"state": [int(v) for v in st[:S]], "md5": [dig[s].tobytes() for s in range(S)], "hashed": [int(v) for v in hs[:S]]}
+
+    def flac_in_md5_reset(self) -> None:
+        """``elemhip_flac_in_md5_reset``: every input slot back to state 0 (a new programme of inputs starts)."""
+        rc = self._lib.elemhip_flac_in_md5_reset(self._h)
+        if rc != 0:
+            err = ElemHipError(f"elemhip_flac_in_md5_reset failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
 
     def flac_read(self) -> Dict[str, Any]:
         """``elemhip_flac_read``: the FLAC programme so far — ``{'flac_frame', 'bits', 'channels_per_stream', 'streams', 'sample_rate',

@@ -386,11 +386,27 @@ int elemhip_flac_md5_final(const uint8_t* record, uint8_t digest[16]);
  * the s24 sample code << (24 - bits): the floats a graph sees are bit for bit those of the PCM input of the same samples, however the
  * render is cut into calls (a frame that straddles two launch sets or calls is decoded in both). Input frames past the table's
  * closing entry are silence; total_samples (the whole stream's length, where the table is a slice of it) is carried for the caller's
- * book-keeping and not read by the engine. With "input_rate" on a call pulls elemhip_input_resample_frames(numFrames) input frames from `position`.
+ * book-keeping and read by the engine for one thing only: with option "flac_in_md5" it is where the stream's digest ends (0: at the table's closing entry). With "input_rate" on a call pulls elemhip_input_resample_frames(numFrames) input frames from `position`.
  * What is read: fixed-block-size streams of 8 / 12 / 16 / 20 / 24 bits, 1 .. 8 channels, blocks of 16 .. 16384 samples (a shorter last
  * one), CONSTANT / VERBATIM / FIXED / LPC subframes, wasted bits, both residual coding methods with escapes, all channel assignments;
- * every frame's CRC-16 is verified on the GPU. Not read: variable block size, 32-bit samples, blocks above 16384; STREAMINFO's MD5 is
- * not verified (the decoded samples never reach the host).
+ * every frame's CRC-16 is verified on the GPU. Not read: variable block size, 32-bit samples, blocks above 16384.
+ * STREAMINFO's MD5 — what catches a stream cut at a frame boundary, spliced, or re-encoded by a broken tool, which no CRC-16 does — is
+ * computed on the GPU with option "flac_in_md5" = 1 (integral, 0 or 1; 0, the default: no launch, no buffer, not one byte differs; with
+ * it on every rendered sample is still bit for bit what it is without: the stage only reads). Input stream s of a call is slot s. Behind
+ * the decode kernels of every launch set one wave per stream (elementary_amd/csrc/flac_in_md5.hip; the arithmetic: flac_in_md5.h) takes
+ * the samples the decoder restored — for stream sample t, then channel, the low (bits + 7) / 8 bytes of the code, little-endian, as
+ * libFLAC hashes them — into the slot's running digest, every stream sample once: a set that decodes samples [c0, c1) hashes those from
+ * the slot's `hashed` on, so the frame two sets decode enters once and feeding a completed stream again changes nothing. The launch that
+ * hashes the stream's last sample (total_samples, or the table's closing entry where that is 0) finishes the digest; silence past the end is never hashed. A slot's state:
+ * 0 off or never fed, 1 running, 2 complete, 3 broken until the reset — a gap (a render that starts behind sample 0, a seek forward), a
+ * frame that answered 106, another total, sample size or channel count under a running slot. No decoded sample reaches the host, and the
+ * set loop gains no synchronisation. Comparing the 16 bytes with what the file announces is the caller's (sixteen zeros there: "not computed").
+ *   elemhip_flac_in_md5        waits for what is in flight; *slots: the slots fed since the reset; digests [slots][16] (zero unless
+ *                              state 2), states and hashed (stream samples in the digest) [slots], each NULL or with room for `capacity`
+ *                              slots (code 6 when that is too small)
+ *   elemhip_flac_in_md5_reset  every slot back to state 0; so does another value of the option
+ *   elemhip_flac_in_md5_update the handle-less twin, pure host arithmetic: planar int32 codes of 8 / 12 / 16 / 20 / 24 bits, 1 .. 8
+ *                              channels into a record of elemhip_flac_md5_init / _final / _record_bytes (code 8 otherwise)
  * Codes: 8 for a NULL field, a sample size or channel count outside the above, or channels_per_stream unequal to a stream's channels;
  * 106 where a frame does not decode — elemhip_flac_in_error then names the first such (stream, frame index in the stream's table) and
  * the reason: 1 bad CRC, 2 reserved value, 3 bits missing, 4 non-zero padding, 5 sample out of range, 6 unsupported. A call that
@@ -406,6 +422,9 @@ int elemhip_flac_index(const uint8_t* data, size_t bytes, uint32_t channels, uin
                        uint64_t* frameFirstSamples, size_t capacity, size_t* entries);
 int elemhip_flac_decode(const elemhip_flac_in* in, size_t count, int32_t* const* planar, size_t* badFrame, uint32_t* reason);
 int elemhip_flac_in_error(elemhip_t*, uint32_t* stream, uint64_t* frame, uint32_t* reason);   /* of the last call that answered 106 (code 6: none) */
+int elemhip_flac_in_md5(elemhip_t*, uint8_t* digests /*[slots][16]*/, uint32_t* states, uint64_t* hashed, size_t capacity, size_t* slots);
+int elemhip_flac_in_md5_reset(elemhip_t*);
+int elemhip_flac_in_md5_update(uint8_t* record, const int32_t* const* planar, uint32_t channels, size_t frames, uint32_t bits /* 8, 12, 16, 20, 24 */);
 
 /* bool addSharedResource(name, unique_ptr<SharedResource>)       Runtime.h:83,461-465 (insert-only) */
 int    elemhip_add_shared_resource(elemhip_t*, const char* name, const float* const* channels, size_t nCh, size_t nSamples);
@@ -427,7 +446,12 @@ int    elemhip_add_shared_resource(elemhip_t*, const char* name, const float* co
  *   6   a rate pair without a plan (L <= 1024, 2 * ceil(32 * max(1, M / L)) <= 1024 taps, L <= 8 M, both rates integral) or a
  *       resource of more than 2^31 - 1 frames
  *   106 a FLAC frame that does not decode (elemhip_flac_in_error names it, stream 0); nothing is inserted
- * Not done: STREAMINFO's MD5 is not verified, and resources added as floats are never converted.
+ * With option "flac_in_md5" = 1 (see FLAC input above) a FLAC source is hashed by the same kernel under the same rule, on the loader's
+ * stream behind the decode of every piece, with a record of the load's own: a load that decodes the stream from sample 0 to its end
+ * leaves the digest of the FILE's samples with the resource (also where the resource is rate-converted), anything less leaves
+ * "incomplete". The resource's floats do not depend on the option. Not done: resources added as floats are never converted.
+ *   elemhip_shared_resource_md5    *state 0: not hashed (the option was off, or no FLAC source); 1: incomplete; 2: digest[16] is the
+ *                                  STREAMINFO MD5 of the source's samples. Comparing it is the caller's; 6: no such name
  *   elemhip_shared_resource_info   channels and frames (of channel 0) of any resource; 6: no such name
  *   elemhip_shared_resource_read   frames [first, first + count) of `channel` as the nodes see them; a resource shorter than the engine's
  *                                  block can be read up to the block size (the device row's zero padding); 6: no such name, channel or range */
@@ -436,6 +460,7 @@ typedef struct elemhip_resource_src { uint32_t format, channels; double sample_r
 int    elemhip_add_shared_resource_pcm(elemhip_t*, const char* name, const elemhip_resource_src* src, int* inserted);
 int    elemhip_shared_resource_info(elemhip_t*, const char* name, uint32_t* channels, uint64_t* frames);
 int    elemhip_shared_resource_read(elemhip_t*, const char* name, uint32_t channel, uint64_t first, uint64_t count, float* out);
+int    elemhip_shared_resource_md5(elemhip_t*, const char* name, uint8_t digest[16], uint32_t* state);
 /* void pruneSharedResources()                                    Runtime.h:89,467-471 */
 void   elemhip_prune_shared_resources(elemhip_t*);
 /* std::set<NodeId> gc()                                          Runtime.h:76,220-272

@@ -7,13 +7,18 @@ host clock around calls that end in a device synchronise. Reported per leg: medi
 s16 leg, and the bytes that cross the host link. What is timed is a whole call of four launch sets of 256 blocks, not one set: the
 sets of a call overlap (copy, decode and render of neighbouring sets run side by side), so a per-set figure is the call's divided by
 four. The three kernels' own times are NOT printed here: they come from a kernel trace of `--decode-only`, which renders a few
-FLAC-fed calls and nothing else. `--out FILE` also writes the report there."""
+FLAC-fed calls and nothing else. `--out FILE` also writes the report there.
+`--md5`: the FLAC-fed call alone, with engine option flac_in_md5 = 1 (the decoded samples' STREAMINFO MD5 on the GPU,
+elementary_amd/csrc/flac_in_md5.hip) against the same without — two engines, the slots reset in front of every call so that every call
+hashes the whole programme, the legs alternating, medians; the digests are checked against hashlib once. The chain is serial inside a
+stream: the delivery kernel's 0.85 us per 64-byte block (profiles/r07/flac_md5.txt) is the prediction to compare with."""
 import sys, time; sys.path.insert(0, '.')
 import numpy as np
 from elementary_amd import el
 from elementary_amd.runtime import FlacChunk, Runtime, flac_encode, flac_index
 
 decode_only = "--decode-only" in sys.argv
+md5_legs = "--md5" in sys.argv
 out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
 WARM, ROUNDS, BS, FF = 5, 20, 512, 4096
 lines = []
@@ -43,8 +48,10 @@ def workload(name, streams, G, batch, sets):
         off, first = flac_index(data, G, 16, FF)
         chunks.append(FlacChunk(np.frombuffer(data, dtype=np.uint8), off, first, G, 16, frames, 0, frames))
 
-    def engine():
+    def engine(md5=0):
         rt = Runtime(48000.0, BS, device=0); rt.set_option("specialize", 2); rt.set_option("batch_blocks", batch)
+        if md5:
+            rt.set_option("flac_in_md5", 1)
         assert rt.render(*[el.mul(0.5 + 0.01 * c, el.in_({"channel": c})) for c in range(n_in)])["result"] == 0
         rt.process_blocks_host(None, n_in, 64 * BS)             # root fades settle: launch sets from here on
         return rt
@@ -53,6 +60,33 @@ def workload(name, streams, G, batch, sets):
         rt = engine()
         for _ in range(3):
             rt.process_blocks_pcm_io(chunks, "flac", n_in, frames)
+        return
+    if md5_legs:
+        import hashlib
+        rts = {"flac_in_md5 0": engine(), "flac_in_md5 1": engine(1)}
+
+        def call(k):
+            rts[k].flac_in_md5_reset()
+            return rts[k].process_blocks_pcm_io(chunks, "flac", n_in, frames)
+        a, b = call("flac_in_md5 0"), call("flac_in_md5 1")
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), "the option changed a rendered sample"
+        got = rts["flac_in_md5 1"].flac_in_md5()
+        assert got["state"] == [2] * streams and got["md5"] == [hashlib.md5(p.tobytes()).digest() for p in pcm], "a digest is not hashlib's"
+        for _ in range(WARM - 1):
+            for k in rts:
+                call(k)
+        ts = {k: [] for k in rts}
+        for _ in range(ROUNDS):
+            for k in rts:
+                t0 = time.perf_counter(); call(k); ts[k].append(time.perf_counter() - t0)
+        base = float(np.median(ts["flac_in_md5 0"]))
+        blocks = frames * G * 2 // 64
+        say(f"{name}: {streams} streams x {G} channels, {frames} frames per call ({sets} sets of {batch} blocks), FLAC frames of {FF}, {WARM} warm-up calls, "
+            f"{ROUNDS} timed rounds, legs alternating; {blocks} MD5 blocks per stream and call")
+        for k, v in ts.items():
+            med = float(np.median(v))
+            say(f"  {k:14s} median {1e3 * med:8.3f} ms   min {1e3 * min(v):8.3f}   max {1e3 * max(v):8.3f}   median / off {med / base:5.3f}"
+                + (f"   (+{1e3 * (med - base):.3f} ms = {1e6 * (med - base) / blocks:.3f} us per 64-byte block of one stream)" if k.endswith("1") else ""))
         return
     rts = {"s16": engine(), "flac16": engine()}
     calls = {"s16": lambda: rts["s16"].process_blocks_pcm_io(pcm, "s16", n_in, frames),
