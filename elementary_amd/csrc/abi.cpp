@@ -276,6 +276,38 @@ int elemhip_spectrum_host(const elemhip_spectrum_spec* spec, const float* planar
 
 uint64_t elemhip_spectrum_launches(void) { return elemhip::spectrum_launches(); }
 
+static_assert(sizeof(elemhip_automation_point) == sizeof(automation::Point) && offsetof(elemhip_automation_point, value) == offsetof(automation::Point, value) &&
+              offsetof(elemhip_automation_point, curve) == offsetof(automation::Point, curve), "same layout");
+
+int elemhip_automation_set(elemhip_t* h, uint32_t channel, const elemhip_automation_point* points, size_t count) {
+    if (!h || (count && !points)) return elemhip::kInvalidInstructionFormat;
+    return h->engine.automationSet(channel, reinterpret_cast<const automation::Point*>(points), count);
+}
+
+int elemhip_automation_read(elemhip_t* h, uint32_t channel, elemhip_automation_info* info, elemhip_automation_point* points, size_t capacity) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    Engine::AutomationInfo ai{};
+    const int rc = h->engine.automationRead(channel, &ai, reinterpret_cast<automation::Point*>(points), capacity);
+    if (info) { info->lanes = ai.lanes; info->inputs = ai.inputs; info->count = ai.count; }
+    return rc;
+}
+
+int elemhip_automation_reset(elemhip_t* h) { return h ? h->engine.automationReset() : elemhip::kInvalidInstructionFormat; }
+
+int elemhip_automation_host(const elemhip_automation_point* points, size_t count, int64_t t0, size_t n, float* out) {
+    const automation::Point* p = reinterpret_cast<const automation::Point*>(points);
+    if (!automation::lane_ok(p, count)) return elemhip::kInvalidPropertyValue;
+    if (n && !out) return elemhip::kInvalidInstructionFormat;
+    automation::value_host(p, count, t0, n, out);
+    return elemhip::kOk;
+}
+
+int64_t elemhip_automation_segment_at(const elemhip_automation_point* points, size_t count, int64_t t) {
+    return automation::segment_at(reinterpret_cast<const automation::Point*>(points), points ? count : 0, t);
+}
+
+uint64_t elemhip_automation_launches(void) { return elemhip::automation_launches(); }
+
 int elemhip_process_blocks_flac(elemhip_t* h, const void* const* inStreams, size_t nInStreams, const elemhip_pcm_in_spec* inSpec,
                                 void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams, const elemhip_flac_spec* spec,
                                 size_t numFrames, int64_t st, elemhip_pcm_channel_stats* stats) {

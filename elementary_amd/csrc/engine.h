@@ -34,6 +34,7 @@
 #include "flac_in_md5.h"
 #include "noise_shape.h"
 #include "spectrum.h"
+#include "automation.h"
 
 namespace elemhip {
 
@@ -341,6 +342,22 @@ public:
     int spectrumRead(SpectrumInfo* info, float* out, size_t capacity, double* sums, size_t sumCapacity);
     int spectrumFlush();
     int spectrumReset();
+    // Breakpoint automation (automation.h; no lane set: no launch, no buffer, not one byte differs): a lane — a sorted list of
+    // {frame, value, hold | linear} points — bound to engine input channel `channel` (0 .. 31) feeds that channel of processBlocksHost /
+    // Pcm / PcmIo / Flac with the lane's value at the ABSOLUTE engine frame sampleTime + f for frame f of the call, zeros behind the call's
+    // last frame like every input. The points cross the host link once, when the lane is set; a kernel in front of every launch set's
+    // first level (automation.hip, next to the unpack kernel) writes the channel's rows of the set's input, and where those calls
+    // render host block by host block the header's scalar twin fills them: the same floats. Lane channels lie at or above the channels
+    // a call supplies — a call that supplies a bound channel is refused (kInvalidPropertyValue, nothing rendered); the engine's input
+    // count for a call is max(supplied, highest lane + 1), and a channel in between that has no lane reads zeros. With option
+    // "input_rate" on, lanes are not inputs at that rate: they bypass the converter and frame f of a call of numFrames ENGINE frames is
+    // still evaluated at sampleTime + f, sampleTime counting engine frames. A lane that is refused (automation::lane_ok: unsorted, a
+    // non-finite value, an unknown curve, more than 2^20 points, a linear segment longer than 2^52 frames) changes nothing. process()
+    // and the device-resident processBlocks() do not know lanes. Works on a dry handle too (the tables stay on the host).
+    struct AutomationInfo { uint32_t lanes, inputs; uint64_t count; };      // mask of bound channels, highest bound channel + 1, this lane's points
+    int automationSet(uint32_t channel, const automation::Point* points, size_t count);      // count 0 clears the lane
+    int automationRead(uint32_t channel, AutomationInfo* info, automation::Point* points, size_t capacity);
+    int automationReset();
     // FLAC delivery (flac_encode.h; options "flac_frame" 256 .. 4096, default 4096, "flac_bits" 16 / 24, "flac_lpc_order" 0 .. 12 and "flac_md5" 0 / 1): the host-buffer render
     // delivered as RFC 9639 frames of a fixed block size, encoded on the GPU in the pack kernel's place (flac_encode.hip) — behind the
     // converter and the limiter, next to the meter. The sample values are processBlocksPcm's codes for the same render. The programme is
@@ -552,6 +569,16 @@ private:
     int ensureSpectrum(size_t channels, size_t setFrames);      // (`mu` held) a programme of `channels`; halves for sets of `setFrames` (0: none)
     int spectrumResetLocked(size_t channels);
     void spectrumFree(bool tables);
+    // breakpoint automation (automationSet): every lane's points behind one another, on the host and — uploaded when a lane is set —
+    // on the device. The set is immutable and shared: a render call works on the one it found at its start, whatever is set meanwhile.
+    struct AutoLanes {
+        std::vector<automation::Point> points;
+        uint32_t offset[automation::kMaxChannels] = {}, count[automation::kMaxChannels] = {};
+        uint32_t lowest = 0, inputs = 0;       // the lowest bound channel; the highest + 1
+        automation::Point* dev = nullptr;
+        ~AutoLanes();
+    };
+    std::shared_ptr<const AutoLanes> autoLanes;      // null: no lane
     int ensureLoudness(size_t channels, size_t setFrames);      // (`mu` held, both streams idle)
     int loudnessResetLocked(size_t channels);
     void loudnessFree();
@@ -746,6 +773,8 @@ private:
         bool shape; uint32_t shapeBits, shapeDither, shapeSeed;      // noiseShapeSet applies to this call: s16 / s24 / FLAC delivery
         bool spectrum;                                  // spectrumSet applies to this call
         uint32_t inG, inFmt; size_t inStreams, inB;     // the inputs as streams: planar floats count as nIn one-channel float streams
+        std::shared_ptr<const AutoLanes> lanes;         // automationSet applies to this call (null: no lane)
+        size_t nEng;                                    // the engine's input channels: nIn, or with lanes max(nIn, highest lane + 1)
         const unsigned char* inStream(size_t s) const { return src ? static_cast<const unsigned char*>(src->streams[s]) : reinterpret_cast<const unsigned char*>(in[s]); }
     };
     HostCall hostCall(const float* const* in, size_t nIn, float* const* out, size_t nOut, size_t numFrames, int64_t sampleTime, PcmJob* pcm,

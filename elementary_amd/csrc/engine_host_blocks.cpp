@@ -166,9 +166,10 @@ int Engine::renderHostBlocks(const HostCall& c) {
     const size_t nIn = c.nIn, nOut = c.nOut, hb = c.hb, numFrames = c.numFrames;
     const PcmSource* src = c.src; PcmJob* pcm = c.pcm;
     const bool staged = c.packed || c.meter || c.resamp || c.limit || c.spectrum;      // every host block renders into tailOut: a stage reads it there
-    std::vector<const float*> ip(nIn);
+    const AutoLanes* lanes = c.lanes.get();
+    std::vector<const float*> ip(c.nEng);       // the supplied channels, then the lanes' (automationSet)
     std::vector<float*> op(nOut);
-    std::vector<float> tailIn, tailOut, inX, resOut, limOut, spcOut;
+    std::vector<float> tailIn, tailOut, inX, resOut, limOut, spcOut, laneIn;
     std::vector<int32_t> shaped;
     std::vector<uint8_t*> sp(pcm ? pcm->nStreams : 0);
     std::vector<const unsigned char*> srcAt(src ? src->nStreams : 0);
@@ -217,7 +218,17 @@ int Engine::renderHostBlocks(const HostCall& c) {
             tailIn.assign(nIn * hb, 0.0f);
             for (size_t ch = 0; ch < nIn; ++ch) { std::memcpy(tailIn.data() + ch * hb, in[ch] + f0, nf * sizeof(float)); ip[ch] = tailIn.data() + ch * hb; }
         }
-        const int rc = flacInRc != kOk ? flacInRc : process(ip.data(), nIn, op.data(), nOut, hb, c.sampleTime + (int64_t)f0);
+        if (lanes) {
+            // the lane channels' rows of this host block from the header's scalar twin — the kernel's functions, the kernel's floats:
+            // the lanes' values at the block's nf frames, zeros behind them and in a channel without a lane
+            laneIn.assign((c.nEng - nIn) * hb, 0.0f);
+            for (size_t ch = nIn; ch < c.nEng; ++ch) {
+                float* row = laneIn.data() + (ch - nIn) * hb;
+                if (lanes->count[ch]) automation::value_host(lanes->points.data() + lanes->offset[ch], lanes->count[ch], c.sampleTime + (int64_t)f0, nf, row);
+                ip[ch] = row;
+            }
+        }
+        const int rc = flacInRc != kOk ? flacInRc : process(ip.data(), c.nEng, op.data(), nOut, hb, c.sampleTime + (int64_t)f0);
         if (rc != kOk) { carry.abandon(); return rc; }
         // what is delivered of this host block: its nf frames, or their conversion
         const float* got = tailOut.data();

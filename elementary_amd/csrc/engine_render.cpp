@@ -1260,6 +1260,9 @@ Engine::HostCall Engine::hostCall(const float* const* in, size_t nIn, float* con
     c.inp = inPlan;
     c.inG = src ? c.srcG : 1u; c.inFmt = src ? c.srcFmt : pcm_pack::F32;
     c.inStreams = src ? src->nStreams : nIn; c.inB = pcm_pack::sample_bytes(c.inFmt);
+    // automationSet: the lanes as this call found them; their channels are the engine's inputs behind the supplied ones
+    c.lanes = std::atomic_load(&autoLanes);
+    c.nEng = c.lanes ? std::max<size_t>(nIn, c.lanes->inputs) : nIn;
     return c;
 }
 
@@ -1267,6 +1270,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                            const PcmSource* src, FlacJob* flac) {
     const HostCall call = hostCall(in, nIn, out, nOut, numFrames, sampleTime, pcm, src, flac);
     const size_t bs = call.bs, hb = call.hb;
+    if (call.lanes && nIn > call.lanes->lowest) return kInvalidPropertyValue;      // a supplied channel is bound to a lane: nothing is rendered
     bool tapSlices = hb % bs != 0;          // ragged slices (a host block that no k divides evenly): launch sets hold whole engine blocks
     if (hb != bs && !tapSlices) { std::lock_guard<std::mutex> lock(mu); tapSlices = !tapNodeIds.empty(); }
     if (tapSlices) return renderHostBlocks(call);     // (taps under a host block longer than the engine's: engine_host_blocks.cpp)
@@ -1277,6 +1281,8 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
     const size_t srcB = call.srcB, pcmB = call.pcmB, inStreams = call.inStreams, inB = call.inB;
     const resample::Plan rp = call.rp, inp = call.inp;
     const limiter::Plan lmp = call.lmp;
+    const AutoLanes* lanes = call.lanes.get();
+    const size_t nEng = call.nEng;          // the rows of a block of the set's input: the supplied channels, then the lanes' (nIn without lanes)
     auto inStream = [&](size_t s) { return call.inStream(s); };
     const size_t numBlocks = ((numFrames + hb - 1) / hb) * (hb / bs);
     if (numBlocks == 0) return kOk;
@@ -1302,7 +1308,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         }
         outCapFrames = deliveredBy(setBlocks);
         outCapBlocks = (outCapFrames + bs - 1) / bs;
-        int rc = ensureHostStaging(std::max(setBlocks, outCapBlocks) * std::max<size_t>(nOut, 1) * bs, setBlocks * std::max<size_t>(nIn, 1) * bs);
+        int rc = ensureHostStaging(std::max(setBlocks, outCapBlocks) * std::max<size_t>(nOut, 1) * bs, setBlocks * std::max<size_t>(nEng, 1) * bs);
         if (rc != kOk) return rc;
         if (resamp) {
             rc = ensureResample(nOut, outCapBlocks);
@@ -1491,6 +1497,9 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                 if (flacSrc) { if (flacInSets[half].stagedBytes) HOST_TRY(hipMemcpyAsync(dFlacIn[half], hFlacIn[half], flacInSets[half].stagedBytes, hipMemcpyHostToDevice, ioStream)); }
                 else if (inres) { if (inStreams * inStride) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], inStreams * inStride, hipMemcpyHostToDevice, ioStream)); }
                 else if (src) HOST_TRY(hipMemcpyAsync(dPcmIn[half], hPcmIn[half], src->nStreams * srcStride, hipMemcpyHostToDevice, ioStream))
+                else if (lanes)      // (the supplied rows of every block: the lanes' rows behind them are the kernel's, below)
+                    HOST_TRY(hipMemcpy2DAsync(dStageIn[half], nEng * bs * sizeof(float), hStageIn[half], nIn * bs * sizeof(float), nIn * bs * sizeof(float), nb,
+                                              hipMemcpyHostToDevice, ioStream))
                 else HOST_TRY(hipMemcpyAsync(dStageIn[half], hStageIn[half], nb * nIn * bs * sizeof(float), hipMemcpyHostToDevice, ioStream));
                 HOST_TRY(hipEventRecord(evIn[half], ioStream));
                 HOST_TRY(hipStreamWaitEvent(stream, evIn[half], 0));
@@ -1512,7 +1521,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                     ResampleInArgs a{};
                     a.src = dPcmIn[half]; a.dst = dStageIn[half]; a.histIn = dInHist[inHistCur]; a.histOut = dInHist[inHistCur ^ 1];
                     a.table = dInTable; a.rowBase = dInRowBase; a.t0 = inT0; a.n0 = inN; a.streamStride = inStride;
-                    a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nIn; a.G = inG; a.numStreams = (uint32_t)inStreams;
+                    a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nEng; a.G = inG; a.numStreams = (uint32_t)inStreams;
                     a.validIn = (uint32_t)inValid; a.validOut = (uint32_t)inOut; a.numBlocks = (uint32_t)nb; a.plan = inp;
                     HOST_TRY(launch_resample_in(stream, a, inFmt));
                     inHistCur ^= 1;
@@ -1526,14 +1535,27 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                     // row of all nb blocks, zeros behind srcValid: nothing of set k - 2 is left in the half.
                     PcmUnpackArgs a{};
                     a.src = dPcmIn[half]; a.dst = dStageIn[half]; a.rowBase = dPcmInRowBase; a.streamStride = srcStride;
-                    a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nIn; a.G = srcG; a.numStreams = (uint32_t)src->nStreams;
+                    a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nEng; a.G = srcG; a.numStreams = (uint32_t)src->nStreams;
                     a.validFrames = (uint32_t)srcValid; a.numBlocks = (uint32_t)nb; a.tilesPerBlock = pcm_pack::tiles_per_block((uint32_t)bs, srcG);
                     a.rowDwords = pcmInRowDwords;
                     HOST_TRY(launch_pcm_unpack(stream, a, srcFmt));
                 }
             }
+            if (lanes) {
+                // the lanes' kernel in front of the set's first level, on the render's stream, next to the unpack kernel: it writes the
+                // rows of channels [nIn, nEng) of all nb blocks — the lanes' values, zeros for a channel without a lane and behind the
+                // call's last frame — and nothing else, the H2D and the kernels above write the rows in front of them and nothing else.
+                // dStageIn[half] was last read by the render of set k - 2, earlier on this stream. It reads the tables only, which the
+                // call holds.
+                AutomationArgs a{};
+                a.dst = dStageIn[half]; a.points = lanes->dev; a.numPoints = lanes->points.size(); a.time0 = sampleTime + (int64_t)(b0 * bs);
+                a.validFrames = std::min(nb * bs, numFrames - b0 * bs);
+                a.blockSize = (uint32_t)bs; a.numChannels = (uint32_t)nEng; a.firstChannel = (uint32_t)nIn; a.numBlocks = (uint32_t)nb;
+                std::memcpy(a.offset, lanes->offset, sizeof a.offset); std::memcpy(a.count, lanes->count, sizeof a.count);
+                HOST_TRY(launch_automation(stream, a));
+            }
             if (k >= 2) HOST_TRY(hipStreamWaitEvent(stream, evOut[half], 0));   // the D2H of set k - 2 has drained this device half
-            int rc = enqueueBlocks(nIn ? dStageIn[half] : nullptr, nIn, nOut ? dStageOut[half] : nullptr, nOut, nb,
+            int rc = enqueueBlocks(nEng ? dStageIn[half] : nullptr, nEng, nOut ? dStageOut[half] : nullptr, nOut, nb,
                                    sampleTime + (int64_t)(b0 * bs));
             if (rc != kOk) { result = rc; break; }
             if (hb > bs) {                                      // (whole host blocks of hb / bs slices each: where each one ended, for the event relay)

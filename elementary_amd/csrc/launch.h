@@ -11,6 +11,7 @@
 #include "flac_in_md5.h"
 #include "noise_shape.h"
 #include "spectrum.h"
+#include "automation.h"
 
 namespace elemhip {
 
@@ -98,6 +99,18 @@ struct PcmUnpackArgs {
     uint32_t        blockSize, numChannels, G, numStreams, validFrames, numBlocks, tilesPerBlock, rowDwords;   // frames behind validFrames: zero
 };
 hipError_t launch_pcm_unpack(hipStream_t s, const PcmUnpackArgs& a, uint32_t format);
+// ---- breakpoint automation (automation.hip): in front of a launch set's first level, next to the unpack kernel, automation.h ----
+struct AutomationArgs {
+    float*          dst;            // the set's input, [block][numChannels][blockSize]: rows of channels [firstChannel, numChannels) are written
+    const automation::Point* points;        // every lane's points behind one another (device)
+    uint64_t        numPoints;
+    int64_t         time0;          // the absolute engine frame of the set's first frame
+    uint64_t        validFrames;    // frames of the set inside the call: zeros behind them
+    uint32_t        blockSize, numChannels, firstChannel, numBlocks;
+    uint32_t        offset[automation::kMaxChannels], count[automation::kMaxChannels];      // per channel: its lane's points (count 0: no lane, zeros)
+};
+hipError_t launch_automation(hipStream_t s, const AutomationArgs& a);
+uint64_t automation_launches();     // kernels launched by this process so far
 // ---- loudness meter (loudness.hip): behind a launch set's last level, loudness.h ----
 struct LoudnessArgs {
     const float*    src;            // the set's output, [block][numChannels][blockSize]

@@ -144,8 +144,37 @@ class OfflineRenderer:
                 raise ValueError(f"this engine refuses the spectrum spec (size {params['size']}, hop {params.get('hop')})") from e
         self._spectrum_parts = []
         self._time = 0
+        self._lanes: Dict[int, list] = {}
         for k, v in (virtual_file_system or {}).items():
             self._rt.add_shared_resource(k, v)
+
+    def automate(self, lanes: Dict[int, Sequence], unit: str = "frames") -> None:
+        """Breakpoint automation (no counterpart in the reference): ``{channel: [(frame_or_seconds, value, "hold" | "linear"), ...]}``
+        binds each list — sorted by time; ``elementary_amd.automation`` has ``ramp``, ``steps`` and the value rule — as a lane to engine
+        input channel ``channel`` (``Runtime.automation``), which ``el.in({"channel": channel})`` reads like any input. The lanes'
+        channels count into the engine's inputs behind the ``num_input_channels`` the caller supplies, so ``channel`` lies in
+        ``num_input_channels .. 31``; an empty list clears a lane. ``unit`` "seconds": times convert with
+        ``round(seconds * sample_rate)`` (the engine's rate, also with ``input_sample_rate`` set: lanes are not converted). The lanes are
+        expanded on the GPU at the renderer's running sample time, so ``process``, ``process_pcm``, ``process_pcm_io``, ``write_wav``,
+        ``write_flac`` and ``process_wav`` need nothing more. A lane the engine refuses raises ``ValueError`` and changes nothing."""
+        from . import automation as _au
+        if unit not in ("frames", "seconds"):
+            raise ValueError(f"unit is 'frames' or 'seconds', got {unit!r}")
+        if not hasattr(self._rt, "automation"):
+            raise RuntimeError("this engine has no automation lanes (Runtime.automation)")
+        for channel, points in lanes.items():
+            ch = int(channel)
+            if not self.num_in <= ch < _au.MAX_CHANNELS:
+                raise ValueError(f"lane channel {ch}: lanes bind to channels {self.num_in} .. {_au.MAX_CHANNELS - 1}, behind the {self.num_in} supplied inputs")
+            pts = _au.normalise(_au.to_frames(points, self.sample_rate) if unit == "seconds" else points)
+            try:
+                self._rt.automation(ch, pts)
+            except RuntimeError as e:
+                raise ValueError(f"this engine refuses the lane of channel {ch}") from e
+            if pts:
+                self._lanes[ch] = pts
+            else:
+                self._lanes.pop(ch, None)
 
     @property
     def runtime(self) -> Any:
@@ -187,7 +216,8 @@ class OfflineRenderer:
                 total = -((-total * iinfo["up"]) // iinfo["down"])
         inres = getattr(self, "_inres", False) and self.num_in > 0
         icur = 0                                     # input frames consumed so far (option input_rate: not the engine's count)
-        if host_batch is not None and window is not None and any(self._listeners.values()) and (total > bs or self._resample or self._limiter or inres):
+        lanes = bool(getattr(self, "_lanes", None))     # automate(): lanes live in the host-buffer calls only
+        if host_batch is not None and window is not None and any(self._listeners.values()) and (total > bs or self._resample or self._limiter or inres or lanes):
             # listeners to serve: the reference relays events after EVERY block (index.ts:112-122). The engine keeps per-block readout
             # logs, so the block loop still runs as launch sets — `event_window_blocks()` blocks per engine call (1024 with meters and
             # snapshots only, fewer with a scope ring, one with a capture node made without history) — and the BLOCKWISE relay after each call hands the
@@ -210,7 +240,7 @@ class OfflineRenderer:
                         buf[at:at + mm] = y[i, :mm]
                 at += y.shape[1]
             return
-        if host_batch is not None and not any(self._listeners.values()) and (total > bs or self._resample or self._limiter or inres):
+        if host_batch is not None and not any(self._listeners.values()) and (total > bs or self._resample or self._limiter or inres or lanes):
             # no event listeners to serve between blocks: the whole block loop in one engine call
             # (elemhip_process_blocks_host: launch sets staged through pinned double buffers); the event queues are drained
             # once afterwards, as the per-block loop's relay (index.ts:118-122) would have kept them drained — a listener
@@ -231,6 +261,8 @@ class OfflineRenderer:
             raise RuntimeError("this engine cannot limit (no process_blocks_host)")
         if inres:
             raise RuntimeError("this engine cannot take inputs at another sample rate (no process_blocks_host)")
+        if lanes:
+            raise RuntimeError("automation lanes need process_blocks_host, without event listeners or with event_window_blocks")
         for k in range(0, total, bs):
             block_in = None
             if self.num_in:

@@ -146,6 +146,19 @@ def load_library() -> C.CDLL:
         lib.elemhip_spectrum_host.restype = C.c_int
         lib.elemhip_spectrum_launches.argtypes = []
         lib.elemhip_spectrum_launches.restype = C.c_uint64
+        _app = C.POINTER(_AutomationPoint)
+        lib.elemhip_automation_set.argtypes = [C.c_void_p, C.c_uint32, _app, C.c_size_t]
+        lib.elemhip_automation_set.restype = C.c_int
+        lib.elemhip_automation_read.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_AutomationInfo), _app, C.c_size_t]
+        lib.elemhip_automation_read.restype = C.c_int
+        lib.elemhip_automation_reset.argtypes = [C.c_void_p]
+        lib.elemhip_automation_reset.restype = C.c_int
+        lib.elemhip_automation_host.argtypes = [_app, C.c_size_t, C.c_int64, C.c_size_t, _fp]
+        lib.elemhip_automation_host.restype = C.c_int
+        lib.elemhip_automation_segment_at.argtypes = [_app, C.c_size_t, C.c_int64]
+        lib.elemhip_automation_segment_at.restype = C.c_int64
+        lib.elemhip_automation_launches.argtypes = []
+        lib.elemhip_automation_launches.restype = C.c_uint64
         lib.elemhip_flac_index.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _u64p, _u64p, C.c_size_t, _szp]
         lib.elemhip_flac_index.restype = C.c_int
         lib.elemhip_flac_decode.argtypes = [C.POINTER(_FlacIn), C.c_size_t, C.POINTER(C.POINTER(C.c_int32)), _szp, _u32p]
@@ -168,6 +181,53 @@ def load_library() -> C.CDLL:
         lib.elemhip_shared_resource_read.restype = C.c_int
         _lib = lib
     return _lib
+
+
+class _AutomationPoint(C.Structure):
+    _fields_ = [("frame", C.c_int64), ("value", C.c_float), ("curve", C.c_uint32)]
+
+
+class _AutomationInfo(C.Structure):
+    _fields_ = [("lanes", C.c_uint32), ("inputs", C.c_uint32), ("count", C.c_uint64)]
+
+
+def _automation_points(points):
+    """``(frame, value[, curve])`` rows as a ctypes array of ``_AutomationPoint`` and their count."""
+    from . import automation as au
+    pts = au.normalise(points)
+    arr = (_AutomationPoint * max(1, len(pts)))()
+    for i, (f, v, c) in enumerate(pts):
+        if not -(1 << 63) <= f < (1 << 63):
+            raise ValueError(f"frame {f} does not fit 64 bits")
+        arr[i].frame, arr[i].curve = f, c
+        # (a value float32 cannot hold goes in as the infinity it rounds to: the engine refuses it)
+        arr[i].value = v if v != v or abs(v) <= 3.4028235677973366e38 else (float("inf") if v > 0 else float("-inf"))
+    return arr, len(pts)
+
+
+def automation_host(points, t0: int, n: int):
+    """``elemhip_automation_host``: the scalar twin of the automation kernel, pure host arithmetic — float32 ``[n]``, the lane's value
+    at frames ``t0 .. t0 + n - 1``. Raises with ``.code`` 6 for a lane the engine refuses."""
+    import numpy as np
+    arr, count = _automation_points(points)
+    out = np.zeros(max(int(n), 0), dtype=np.float32)
+    rc = load_library().elemhip_automation_host(arr, count, int(t0), out.size, out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        err = ElemHipError(f"elemhip_automation_host failed: {describe(rc)} (code {rc})")
+        err.code = rc
+        raise err
+    return out
+
+
+def automation_segment_at(points, t: int) -> int:
+    """``elemhip_automation_segment_at``: the index of the last point whose frame is ``<= t`` (-1 before the first)."""
+    arr, count = _automation_points(points)
+    return int(load_library().elemhip_automation_segment_at(arr, count, int(t)))
+
+
+def automation_launches() -> int:
+    """``elemhip_automation_launches``: automation kernels this process has launched so far (an engine without lanes adds none)."""
+    return int(load_library().elemhip_automation_launches())
 
 
 class _PcmSpec(C.Structure):
@@ -707,7 +767,9 @@ class Runtime(CRuntime):
         rc = self._lib.elemhip_process_blocks_host(self._h, _ptr_array(rows), len(rows),
                                                    _ptr_array([out[i] for i in range(num_outputs)]), num_outputs, int(num_frames), st)
         if rc != 0:
-            raise ElemHipError(f"elemhip_process_blocks_host failed: {describe(rc)} (code {rc})")
+            err = ElemHipError(f"elemhip_process_blocks_host failed: {describe(rc)} (code {rc})")
+            err.code = rc
+            raise err
         if sample_time is None:
             nb = (int(num_frames) + self.block_size - 1) // self.block_size
             self.sample_time += nb * self.block_size
@@ -1232,6 +1294,29 @@ class Runtime(CRuntime):
     def spectrum_reset(self) -> None:
         """``elemhip_spectrum_reset``: a new programme; what was pending is dropped."""
         self._spectrum_check("elemhip_spectrum_reset", self._lib.elemhip_spectrum_reset(self._h))
+
+    def automation(self, channel: int, points) -> None:
+        """``elemhip_automation_set``: binds a lane — ``(frame, value[, "hold" | "linear"])`` rows sorted by frame
+        (``elementary_amd.automation``: ``ramp``, ``steps`` and the value rule) — to engine input channel ``channel`` (0 .. 31) of the
+        host-buffer render calls; frame ``f`` of a call reads the lane's value at ``sample_time + f``, expanded on the GPU. The channel
+        must lie at or above the inputs a call supplies. ``points`` empty or None clears the lane. A lane the engine refuses raises with
+        ``.code`` 6 and changes nothing."""
+        arr, count = _automation_points(points or [])
+        self._spectrum_check("elemhip_automation_set", self._lib.elemhip_automation_set(self._h, int(channel), arr if count else None, count))
+
+    def automation_read(self, channel: int) -> Dict[str, Any]:
+        """``elemhip_automation_read``: ``{'points': [(frame, value, curve code), ...] of the channel's lane, 'channels': the bound
+        channels, 'inputs': highest bound channel + 1}``."""
+        info = _AutomationInfo()
+        self._spectrum_check("elemhip_automation_read", self._lib.elemhip_automation_read(self._h, int(channel), C.byref(info), None, 0))
+        arr = (_AutomationPoint * max(1, int(info.count)))()
+        self._spectrum_check("elemhip_automation_read", self._lib.elemhip_automation_read(self._h, int(channel), C.byref(info), arr, len(arr)))
+        return {"points": [(int(arr[i].frame), float(arr[i].value), int(arr[i].curve)) for i in range(int(info.count))],
+                "channels": [c for c in range(32) if info.lanes >> c & 1], "inputs": int(info.inputs)}
+
+    def automation_reset(self) -> None:
+        """``elemhip_automation_reset``: clears every lane."""
+        self._spectrum_check("elemhip_automation_reset", self._lib.elemhip_automation_reset(self._h))
 
     def event_window_blocks(self) -> int:
         """Blocks a ``process_queued_events(blockwise=True)`` window may span and still equal a relay after every block."""

@@ -302,6 +302,44 @@ int elemhip_spectrum_host(const elemhip_spectrum_spec* spec, const float* planar
                           uint64_t j0, uint64_t j1, float* tail, double* sums, float* out);
 uint64_t elemhip_spectrum_launches(void);
 
+/* EXTENSION (no counterpart in the reference): breakpoint automation for elemhip_process_blocks_host / _pcm / _pcm_io / _flac, expanded
+ * on the GPU (elementary_amd/csrc/automation.hip; the arithmetic: automation.h). A lane is a list of points {frame, value, curve}
+ * sorted by frame and bound to one engine input channel (0 .. 31); `el.in({channel})` reads it like any input. Only the points cross
+ * the host link, once, when the lane is set: a kernel in front of every launch set's first level writes the channel's float32 rows
+ * where the copy of a dense control signal would have put them, and no byte of a lane channel is staged or copied per call.
+ * The value at ABSOLUTE engine frame t, with i the last point whose frame is <= t:
+ *   t before the first point: the first value; i the last point: its value; curve 0 (hold), or t == frame_i: value_i bit for bit;
+ *   curve 1 (linear): in double u = (double)(t - f_i) / (double)(f_{i+1} - f_i), y = a + (b - a) * u with the two values widened,
+ *   these operations in this order, never fused, rounded once to float32.
+ * Several points on one frame make a jump: the last of them is the value from that frame on, the first of them is what a ramp into
+ * that frame aims at, any between the two have no effect.
+ * Frame f of a call is evaluated at sampleTime + f, so a render does not depend on how it is cut into calls and launch sets and
+ * nothing is carried; behind a call's last frame a lane channel is zero, as every input is. With option "input_rate" on, lanes are
+ * not inputs at that rate: they are generated at the engine's rate and bypass the converter, and sampleTime keeps counting ENGINE
+ * frames — frame f of a call of numFrames engine frames is evaluated at sampleTime + f, whatever the input frames it pulls.
+ * Lane channels lie at or above the channels a call supplies (nIn, or nInStreams * channels_per_stream): a call that supplies a bound
+ * channel answers 6 and renders nothing. The engine's input count for a call is max(supplied, highest lane + 1); a channel in between
+ * that has no lane reads zeros, as a missing input does. Code 6, and nothing changes, for a lane that is unsorted, holds a non-finite
+ * value or a curve other than 0 or 1, has more than 2^20 points or a linear segment longer than 2^52 frames, and for a channel
+ * above 31 (dry handles validate and keep lanes too). With no lane set: no launch, no buffer, not one byte differs.
+ * elemhip_process and the device-resident elemhip_process_blocks are not covered: they read the inputs they are given.
+ *   elemhip_automation_set     binds a lane to `channel`, replacing the one it had; count 0 clears it
+ *   elemhip_automation_read    info: lanes = bit mask of the bound channels, inputs = highest bound channel + 1 (0: none), count = the
+ *                              points of `channel`'s lane; points (NULL, or `capacity` points, code 6 when too few) receives them
+ *   elemhip_automation_reset   clears every lane
+ *   elemhip_automation_host    the scalar twin, no handle: out[k] = the lane's value at t0 + k, k < n (code 6 for a lane that is refused)
+ *   elemhip_automation_segment_at  the search a thread of the kernel does for its first frame: the index of the last point whose
+ *                              frame is <= t, -1 before the first
+ *   elemhip_automation_launches  automation kernels this process has launched so far */
+typedef struct elemhip_automation_point { int64_t frame; float value; uint32_t curve; } elemhip_automation_point;
+typedef struct elemhip_automation_info { uint32_t lanes, inputs; uint64_t count; } elemhip_automation_info;
+int elemhip_automation_set(elemhip_t*, uint32_t channel, const elemhip_automation_point* points, size_t count);
+int elemhip_automation_read(elemhip_t*, uint32_t channel, elemhip_automation_info* info, elemhip_automation_point* points, size_t capacity);
+int elemhip_automation_reset(elemhip_t*);
+int elemhip_automation_host(const elemhip_automation_point* points, size_t count, int64_t t0, size_t n, float* out);
+int64_t elemhip_automation_segment_at(const elemhip_automation_point* points, size_t count, int64_t t);
+uint64_t elemhip_automation_launches(void);
+
 /* EXTENSION (no counterpart in the reference): the same render delivered as FLAC, encoded on the GPU in the pack kernel's place
  * (elementary_amd/csrc/flac_encode.hip; the arithmetic and the decision rules: flac_encode.h) — behind the delivery-rate converter and
  * the limiter, next to the meter. RFC 9639 "subset" streams of a fixed block size (option "flac_frame": 256, 512, 1024, 2048 or 4096,

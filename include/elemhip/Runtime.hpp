@@ -174,6 +174,12 @@ public:
     }
     int spectrumFlush() { return elemhip_spectrum_flush(h); }
     int spectrumReset() { return elemhip_spectrum_reset(h); }
+    // EXTENSION: breakpoint automation lanes on engine input channels of the host-buffer render calls, expanded on the GPU (count 0: cleared)
+    int automationSet(uint32_t channel, const elemhip_automation_point* points, size_t count) { return elemhip_automation_set(h, channel, points, count); }
+    int automationRead(uint32_t channel, elemhip_automation_info* info, elemhip_automation_point* points, size_t capacity) {
+        return elemhip_automation_read(h, channel, info, points, capacity);
+    }
+    int automationReset() { return elemhip_automation_reset(h); }
     // EXTENSION: the block loop delivered as FLAC frames encoded on the GPU (elemhip_process_blocks_flac; setOption("flac_frame" /
     // "flac_bits")): inputs as processBlocksPcmIo takes them, per output stream a buffer of at least flacBound(frames delivered,
     // channels_per_stream, bits) bytes; bytesOut[s] = the bytes of the FLAC frames the call completed. flacFlush closes the programme
