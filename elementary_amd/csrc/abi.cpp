@@ -308,6 +308,56 @@ int64_t elemhip_automation_segment_at(const elemhip_automation_point* points, si
 
 uint64_t elemhip_automation_launches(void) { return elemhip::automation_launches(); }
 
+int elemhip_qc_set(elemhip_t* h, const elemhip_qc_spec* spec) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    if (!spec) return h->engine.qcSet(nullptr);
+    const Engine::QcSpec sp{spec->silence_level, spec->clip_level, spec->clip_run, spec->dropout_frames, spec->bucket, spec->num_pairs, spec->pairs, spec->skip, spec->limit};
+    return h->engine.qcSet(&sp);
+}
+
+int elemhip_qc_read(elemhip_t* h, elemhip_qc_info* info, elemhip_qc_channel* channels, size_t channelCapacity, double* pairSums, size_t pairCapacity) {
+    if (!h) return elemhip::kInvalidInstructionFormat;
+    static_assert(sizeof(elemhip_qc_info) == sizeof(Engine::QcInfo) && sizeof(elemhip_qc_channel) == sizeof(qc::ChannelReport), "same layout");
+    Engine::QcInfo qi{};
+    const int rc = h->engine.qcRead(&qi, reinterpret_cast<qc::ChannelReport*>(channels), channelCapacity, pairSums, pairCapacity);
+    if (info) std::memcpy(info, &qi, sizeof qi);
+    return rc;
+}
+
+int elemhip_qc_overview(elemhip_t* h, float* out, size_t capacity) { return h ? h->engine.qcOverview(out, capacity) : elemhip::kInvalidInstructionFormat; }
+
+int elemhip_qc_reset(elemhip_t* h) { return h ? h->engine.qcReset() : elemhip::kInvalidInstructionFormat; }
+
+size_t elemhip_qc_state_bytes(uint32_t channels, uint32_t numPairs) { return (size_t)channels * sizeof(qc::ChannelState) + (size_t)numPairs * sizeof(qc::PairState); }
+
+int elemhip_qc_host(const elemhip_qc_spec* spec, const float* planar, uint32_t channels, size_t stride, size_t frames, uint64_t p0, uint8_t* state,
+                    elemhip_qc_channel* reports, double* pairSums, float* overview) {
+    if (!spec || !qc::spec_ok(spec->silence_level, spec->clip_level, spec->clip_run, spec->dropout_frames, spec->bucket, spec->num_pairs) || (spec->num_pairs && !spec->pairs))
+        return elemhip::kInvalidPropertyValue;
+    for (uint32_t k = 0; k < spec->num_pairs; ++k)
+        if (spec->pairs[2u * k] == spec->pairs[2u * k + 1u] || spec->pairs[2u * k] >= channels || spec->pairs[2u * k + 1u] >= channels) return elemhip::kInvalidPropertyValue;
+    if (!state || (frames && !planar) || (frames > stride && channels > 1u) || frames > 0xFFFFFFFFull) return elemhip::kInvalidInstructionFormat;
+    const qc::Spec sp{spec->silence_level, spec->clip_level, spec->clip_run, spec->dropout_frames, spec->bucket, spec->num_pairs};
+    const uint32_t buckets = qc::buckets_complete(p0, (uint32_t)frames, sp.bucket);
+    if (buckets && !overview) return elemhip::kInvalidInstructionFormat;
+    // (the state is bytes to the caller: worked on in aligned copies)
+    std::vector<qc::ChannelState> st(channels);
+    std::vector<qc::PairState> ps(spec->num_pairs);
+    if (channels) std::memcpy(st.data(), state, channels * sizeof(qc::ChannelState));
+    if (spec->num_pairs) std::memcpy(ps.data(), state + channels * sizeof(qc::ChannelState), spec->num_pairs * sizeof(qc::PairState));
+    if (p0 == 0u) { for (auto& s : st) s = qc::state_empty(); for (auto& p : ps) p = qc::PairState{0.0, 0.0}; }
+    for (uint32_t c = 0; c < channels; ++c) qc::channel_host(sp, st[c], planar + (size_t)c * stride, frames, p0, overview ? overview + (size_t)c * buckets * 2u : nullptr);
+    for (uint32_t k = 0; k < spec->num_pairs; ++k)
+        qc::pair_host(ps[k], planar + (size_t)spec->pairs[2u * k] * stride, planar + (size_t)spec->pairs[2u * k + 1u] * stride, frames, p0, sp);
+    if (channels) std::memcpy(state, st.data(), channels * sizeof(qc::ChannelState));
+    if (spec->num_pairs) std::memcpy(state + channels * sizeof(qc::ChannelState), ps.data(), spec->num_pairs * sizeof(qc::PairState));
+    for (uint32_t c = 0; c < channels && reports; ++c) { const qc::ChannelReport r = qc::report(sp, st[c]); std::memcpy(reports + c, &r, sizeof r); }
+    for (uint32_t k = 0; k < spec->num_pairs && pairSums; ++k) pairSums[k] = qc::sums_value(ps[k]);
+    return elemhip::kOk;
+}
+
+uint64_t elemhip_qc_launches(void) { return elemhip::qc_launches(); }
+
 int elemhip_process_blocks_flac(elemhip_t* h, const void* const* inStreams, size_t nInStreams, const elemhip_pcm_in_spec* inSpec,
                                 void* const* outStreams, const size_t* capacities, size_t* bytesOut, size_t nOutStreams, const elemhip_flac_spec* spec,
                                 size_t numFrames, int64_t st, elemhip_pcm_channel_stats* stats) {

@@ -195,6 +195,7 @@ Engine::~Engine() {
     limiterFree();
     noiseShapeFree();
     spectrumFree(true);
+    qcFree();
     flacFree();
     flacInFree();
     if (ioStream) (void)hipStreamDestroy(ioStream);

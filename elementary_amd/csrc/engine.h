@@ -34,6 +34,7 @@
 #include "flac_in_md5.h"
 #include "noise_shape.h"
 #include "spectrum.h"
+#include "qc.h"
 #include "automation.h"
 
 namespace elemhip {
@@ -342,6 +343,23 @@ public:
     int spectrumRead(SpectrumInfo* info, float* out, size_t capacity, double* sums, size_t sumCapacity);
     int spectrumFlush();
     int spectrumReset();
+    // Inspector (qc.h; off by default: no launch, no buffer, not one byte differs): with a spec set, what processBlocksHost / Pcm / PcmIo /
+    // Flac deliver — behind the converter and the limiter, the floats the meter reads, before any quantisation — is inspected per
+    // channel behind every launch set's last level (qc.hip; the header's scalar twin where those calls render host block by host
+    // block): quiet and clipped frames and their runs (head and tail silence, dropouts, clip events), non-finite samples, min, max and
+    // the first peak, the float64 sums of x and x^2 and of x_a x_b for up to 128 channel pairs, and with `bucket` a min / max overview.
+    // The programme is the delivered frames since the spec was set or qcReset, less the first `skip`, cut after `limit` (0: unbounded);
+    // a call of another channel count, and a call that fails, start a new one. It only reads. A null spec turns it off. A spec that is
+    // refused (qc::spec_ok; a pair of one channel twice) changes nothing; a call that delivers fewer channels than a pair names is
+    // refused with kInvalidPropertyValue.
+    struct QcSpec { float silenceLevel, clipLevel; uint32_t clipRun, dropoutFrames, bucket, numPairs; const uint32_t* pairs; uint64_t skip, limit; };
+    struct QcInfo { uint32_t channels, pairs, bucket, reserved; uint64_t frames, delivered, firstBucket, queued; };
+    int qcSet(const QcSpec* spec);
+    // `channels` (null, or room for channelCap reports) and `pairSums` (null, or pairCap doubles): the cumulative results; the open
+    // bucket's partial comes with the channel. The programme is not disturbed. info.queued complete buckets from info.firstBucket on wait.
+    int qcRead(QcInfo* info, qc::ChannelReport* channels, size_t channelCap, double* pairSums, size_t pairCap);
+    int qcOverview(float* out, size_t capacity);      // drains the queue: [channel][queued][2] (min, max); too small: kInvalidPropertyValue
+    int qcReset();
     // Breakpoint automation (automation.h; no lane set: no launch, no buffer, not one byte differs): a lane — a sorted list of
     // {frame, value, hold | linear} points — bound to engine input channel `channel` (0 .. 31) feeds that channel of processBlocksHost /
     // Pcm / PcmIo / Flac with the lane's value at the ABSOLUTE engine frame sampleTime + f for frame f of the call, zeros behind the call's
@@ -566,6 +584,20 @@ private:
     std::vector<std::vector<float>> spcQueue; uint64_t spcQueueFirst = 0;      // [channel]: frames x columns; the index of the first one
     static constexpr size_t kSpcHalfBytes = 256u << 20;                       // the most a pinned half may hold
     size_t spectrumSetFrames(size_t deliveredFrames) const { return deliveredFrames / spcPlan.hop + 2; }     // frames a set of that many completes at most
+    // inspector (qcSet): per channel and per pair the programme's summary on the device; per set the tiles' summaries, the leaves' sums
+    // and the overview's edge pieces (scratch); per half the buckets a set completes (device, pinned); the buckets nobody has read yet
+    bool qcOn = false;
+    qc::Spec qcSpec{}; std::vector<uint32_t> qcPairs; uint64_t qcSkip = 0, qcLimit = 0;
+    uint32_t qcChannels = 0;               // channels of the programme (0: none yet)
+    uint64_t qcFrames = 0, qcDelivered = 0;         // programme frames inspected / frames delivered by inspected calls (the window's clock)
+    qc::ChannelState* dQcState = nullptr; qc::PairState* dQcPairState = nullptr; uint32_t* dQcPairs = nullptr; size_t qcStateCap = 0;
+    qc::Stretch<uint32_t>* dQcTiles = nullptr; double* dQcLeaves = nullptr; float* dQcEdges = nullptr; size_t qcSetCap = 0, qcScratchChannels = 0;
+    float* dQcOut[2] = {nullptr, nullptr}; float* hQcOut[2] = {nullptr, nullptr}; size_t qcOutCap = 0, qcOutChannels = 0;      // (cap: buckets per channel)
+    uint32_t qcCountOf[2] = {0, 0};        // buckets the set in each half completed
+    std::vector<std::vector<float>> qcQueue; uint64_t qcQueueFirst = 0;        // [channel]: buckets x 2; the index of the first one
+    int ensureQc(size_t channels, size_t setFrames);            // (`mu` held) a programme of `channels`; scratch for sets of `setFrames` (0: none)
+    int qcResetLocked(size_t channels);
+    void qcFree();
     int ensureSpectrum(size_t channels, size_t setFrames);      // (`mu` held) a programme of `channels`; halves for sets of `setFrames` (0: none)
     int spectrumResetLocked(size_t channels);
     void spectrumFree(bool tables);
@@ -772,6 +804,7 @@ private:
         resample::Plan rp, inp; limiter::Plan lmp;
         bool shape; uint32_t shapeBits, shapeDither, shapeSeed;      // noiseShapeSet applies to this call: s16 / s24 / FLAC delivery
         bool spectrum;                                  // spectrumSet applies to this call
+        bool qc;                                        // qcSet applies to this call
         uint32_t inG, inFmt; size_t inStreams, inB;     // the inputs as streams: planar floats count as nIn one-channel float streams
         std::shared_ptr<const AutoLanes> lanes;         // automationSet applies to this call (null: no lane)
         size_t nEng;                                    // the engine's input channels: nIn, or with lanes max(nIn, highest lane + 1)

@@ -36,6 +36,7 @@ struct Engine::HostCarry {
     std::vector<flac_md5::Record> flacInMd5;            // option "flac_in_md5": the input slots' running digests
     std::vector<noise_shape::ChannelState> shapeState;  // noise-shaped requantisation: the channels' errors
     std::vector<float> spcTail; std::vector<double> spcSums;      // the spectrum analyser: the carried frames, the running sums
+    std::vector<qc::ChannelState> qcState; std::vector<qc::PairState> qcPairState;      // the inspector: the programme's summaries
     std::vector<Carried> stages;
     size_t opened = 0;                                  // stages [0, opened) are open
 
@@ -80,6 +81,13 @@ struct Engine::HostCarry {
              [this] { return std::vector<Span>{{spcTail.data(), e.dSpcTail[e.spcTailCur], spcTail.size() * sizeof(float)},
                                                {spcSums.data(), e.dSpcSums, spcSums.size() * sizeof(double)}}; },
              Carried::kReset, [this] { return e.spectrumResetLocked(e.spcChannels); }, nullptr},
+            // the inspector: the channels' and the pairs' summaries; a failed call starts a new programme
+            {c.qc, [this] { const int rc = e.ensureQc(c.nOut, 0);
+                            if (rc == kOk) { qcState.resize(c.nOut); qcPairState.resize(e.qcPairs.size() / 2u); }
+                            return rc; },
+             [this] { return std::vector<Span>{{qcState.data(), e.dQcState, qcState.size() * sizeof(qc::ChannelState)},
+                                               {qcPairState.data(), e.dQcPairState, qcPairState.size() * sizeof(qc::PairState)}}; },
+             Carried::kReset, [this] { return e.qcResetLocked(e.qcChannels); }, nullptr},
         };
     }
 
@@ -165,11 +173,11 @@ int Engine::renderHostBlocks(const HostCall& c) {
     const float* const* in = c.in; float* const* out = c.out;
     const size_t nIn = c.nIn, nOut = c.nOut, hb = c.hb, numFrames = c.numFrames;
     const PcmSource* src = c.src; PcmJob* pcm = c.pcm;
-    const bool staged = c.packed || c.meter || c.resamp || c.limit || c.spectrum;      // every host block renders into tailOut: a stage reads it there
+    const bool staged = c.packed || c.meter || c.resamp || c.limit || c.spectrum || c.qc;      // every host block renders into tailOut: a stage reads it there
     const AutoLanes* lanes = c.lanes.get();
     std::vector<const float*> ip(c.nEng);       // the supplied channels, then the lanes' (automationSet)
     std::vector<float*> op(nOut);
-    std::vector<float> tailIn, tailOut, inX, resOut, limOut, spcOut, laneIn;
+    std::vector<float> tailIn, tailOut, inX, resOut, limOut, spcOut, laneIn, qcOut;
     std::vector<int32_t> shaped;
     std::vector<uint8_t*> sp(pcm ? pcm->nStreams : 0);
     std::vector<const unsigned char*> srcAt(src ? src->nStreams : 0);
@@ -270,6 +278,20 @@ int Engine::renderHostBlocks(const HostCall& c) {
                 spcQueue[ch].insert(spcQueue[ch].end(), spcOut.begin(), spcOut.end());
             }
             spcFrames += nd; spcEmitted = j1;
+        }
+        if (c.qc && nd) {
+            // the floats are on the host: the header's scalar twin inspects the frames the window lets in — the kernel's functions
+            std::lock_guard<std::mutex> lock(mu);
+            const qc::Window w = qc::window(qcDelivered, qcFrames, qcSkip, qcLimit, nd);
+            const uint32_t buckets = qc::buckets_complete(qcFrames, w.count, qcSpec.bucket);
+            qcOut.resize((size_t)buckets * 2u);
+            for (size_t ch = 0; ch < nOut; ++ch) {
+                qc::channel_host(qcSpec, carry.qcState[ch], got + ch * gotStride + w.q0, w.count, qcFrames, qcOut.data());
+                qcQueue[ch].insert(qcQueue[ch].end(), qcOut.begin(), qcOut.end());
+            }
+            for (size_t k = 0; k < carry.qcPairState.size(); ++k)
+                qc::pair_host(carry.qcPairState[k], got + qcPairs[2u * k] * gotStride + w.q0, got + qcPairs[2u * k + 1u] * gotStride + w.q0, w.count, qcFrames, qcSpec);
+            qcDelivered += nd; qcFrames += w.count;
         }
         if (c.shape && nd) {
             // the floats are on the host: the header's scalar loop quantises all nd of them — the kernel's functions, the kernel's bits

@@ -1253,6 +1253,7 @@ Engine::HostCall Engine::hostCall(const float* const* in, size_t nIn, float* con
     c.shapeDither = flac ? (flac->spec.dither ? 1u : 0u) : pcm ? (pcm->spec.dither ? 1u : 0u) : 0u;
     c.shapeSeed = flac ? flac->spec.seed : pcm ? pcm->spec.seed : 0u;
     c.spectrum = spcOn && nOut > 0;         // spectrumSet: the delivered frames of every set go through the analyser, next to the meter
+    c.qc = qcOn && nOut > 0;                // qcSet: and through the inspector
     // option "input_rate": the inputs — planar floats or streams — arrive at another rate and are converted to the engine's in front of
     // the render; a call of numFrames ENGINE frames pulls the input frames [inputs_before(n0), inputs_before(n0 + numFrames)) of the
     // programme. Planar floats count as nIn one-channel float streams: one path for both.
@@ -1276,7 +1277,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
     if (tapSlices) return renderHostBlocks(call);     // (taps under a host block longer than the engine's: engine_host_blocks.cpp)
     // the launch-set loop, under the names it has always read the call by
     const bool flacSrc = call.flacSrc, wantFloat = call.wantFloat, packed = call.packed, meter = call.meter, resamp = call.resamp, limit = call.limit, inres = call.inres, shape = call.shape;
-    const bool spectrum = call.spectrum;
+    const bool spectrum = call.spectrum, inspect = call.qc;
     const uint32_t flacInB = call.flacInB, srcG = call.srcG, srcFmt = call.srcFmt, pcmG = call.pcmG, pcmFmt = call.pcmFmt, inG = call.inG, inFmt = call.inFmt;
     const size_t srcB = call.srcB, pcmB = call.pcmB, inStreams = call.inStreams, inB = call.inB;
     const resample::Plan rp = call.rp, inp = call.inp;
@@ -1360,6 +1361,10 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             rc = ensureSpectrum(nOut, spectrumSetFrames(outCapFrames));
             if (rc != kOk) return rc;
         }
+        if (inspect) {
+            rc = ensureQc(nOut, outCapFrames);
+            if (rc != kOk) return rc;
+        }
         if (flac) {
             rc = ensureFlac(*flac, outCapFrames);
             if (rc != kOk) return rc;
@@ -1431,8 +1436,15 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         std::lock_guard<std::mutex> lock(mu);
         for (size_t c = 0; c < nOut && count; ++c) spcQueue[c].insert(spcQueue[c].end(), frames + c * count * cols, frames + (c + 1) * count * cols);
     };
+    auto deliverQc = [&](size_t k) {         // the buckets set k completed -> the queue qcOverview drains
+        const size_t count = qcCountOf[k & 1];
+        const float* buckets = hQcOut[k & 1];
+        std::lock_guard<std::mutex> lock(mu);
+        for (size_t c = 0; c < nOut && count; ++c) qcQueue[c].insert(qcQueue[c].end(), buckets + c * count * 2u, buckets + (c + 1) * count * 2u);
+    };
     auto deliver = [&](size_t k) { if (wantFloat) { if (resamp) scatterConverted(k); else scatter(k); } if (pcm) deliverPcm(k); if (meter) deliverLoudness(k);
                                   if (spectrum) deliverSpectrum(k);
+                                  if (inspect) deliverQc(k);
                                   if (flac && flacRc == kOk) flacRc = flacDeliver(*flac, (int)(k & 1)); };
     int result = kOk;
     size_t issued = 0, scattered = 0, outOff = 0;
@@ -1687,6 +1699,22 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
                     spcFrames += valid; spcEmitted += a.numFrames;
                 }
             }
+            if (inspect) {
+                // the inspector's kernels behind the set's last level too: they read the same block. The programme's summaries live on
+                // the device and are folded in place by this stream's kernels only; the overview buckets this set completes go to this
+                // half's region, drained by the D2H of set k - 2 (evOut above).
+                const qc::Window w = qc::window(qcDelivered, qcFrames, qcSkip, qcLimit, valid);
+                QcArgs a{};
+                a.src = got; a.state = dQcState; a.pairState = dQcPairState; a.pairs = dQcPairs; a.tileStretch = dQcTiles; a.leafSums = dQcLeaves;
+                a.tileEdge = dQcEdges; a.out = dQcOut[half]; a.p0 = qcFrames; a.q0 = w.q0; a.count = w.count; a.blockSize = (uint32_t)bs;
+                a.numChannels = (uint32_t)nOut; a.numPairs = (uint32_t)(qcPairs.size() / 2u); a.numTiles = qc::tile_count(a.p0, a.count);
+                a.tileCap = (uint32_t)(qcSetCap / qc::kTileFrames + 2u); a.leafCap = (uint32_t)(qcSetCap / qc::kLeaf + 2u);
+                a.outCount = qc::buckets_complete(a.p0, a.count, qcSpec.bucket); a.spec = qcSpec;
+                if (a.outCount > qcOutCap || valid > qcSetCap) { result = kInvariantViolation; break; }       // (sized above for the largest set)
+                qcCountOf[half] = a.outCount;
+                HOST_TRY(launch_qc(stream, a));
+                qcDelivered += valid; qcFrames += w.count;
+            }
             HOST_TRY(hipEventRecord(evRendered[half], stream));
             HOST_TRY(hipStreamWaitEvent(ioStream, evRendered[half], 0));
             if (flacSrc) HOST_TRY(hipMemcpyAsync(hFlacInErr + half, dFlacInErr + half, sizeof(FlacInError), hipMemcpyDeviceToHost, ioStream));   // the decode's error record
@@ -1706,6 +1734,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
             if (meter && loudCountOf[half]) HOST_TRY(hipMemcpyAsync(hLoudOut[half], dLoudOut[half], nOut * loudOutStride * sizeof(double), hipMemcpyDeviceToHost, ioStream));
             if (spectrum && spcCountOf[half])
                 HOST_TRY(hipMemcpyAsync(hSpcOut[half], dSpcOut[half], nOut * spcCountOf[half] * spcPlan.cols * sizeof(float), hipMemcpyDeviceToHost, ioStream));
+            if (inspect && qcCountOf[half]) HOST_TRY(hipMemcpyAsync(hQcOut[half], dQcOut[half], nOut * qcCountOf[half] * 2u * sizeof(float), hipMemcpyDeviceToHost, ioStream));
             HOST_TRY(hipEventRecord(evOut[half], ioStream));
             issued = k + 1;
         }
@@ -1735,6 +1764,7 @@ int Engine::renderHostSets(const float* const* in, size_t nIn, float* const* out
         // a metered call that failed may have advanced the carried state past sets whose sums never arrived: the programme starts anew
         if (meter && result != kOk) (void)loudnessResetLocked(loudChannels);
         if (spectrum && result != kOk) (void)spectrumResetLocked(spcChannels);      // the same for the analyser's
+        if (inspect && result != kOk) (void)qcResetLocked(qcChannels);             // and the inspector's
         if (resamp && result != kOk) (void)resampleResetLocked(0);      // likewise: the clock may be ahead of what was delivered
         if (limit && result != kOk) (void)limiterResetLocked(0);
         if (shape && result != kOk) (void)noiseShapeResetLocked();

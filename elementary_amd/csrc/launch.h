@@ -11,6 +11,7 @@
 #include "flac_in_md5.h"
 #include "noise_shape.h"
 #include "spectrum.h"
+#include "qc.h"
 #include "automation.h"
 
 namespace elemhip {
@@ -136,6 +137,22 @@ struct SpectrumArgs {
 };
 hipError_t launch_spectrum(hipStream_t s, const SpectrumArgs& a);
 uint64_t spectrum_launches();       // kernels launched by this process so far
+// ---- inspector (qc.hip): behind a launch set's last level, next to the meter and the analyser, qc.h ----
+struct QcArgs {
+    const float*    src;            // the set's output, [block][numChannels][blockSize]; frames [q0, q0 + count) enter the programme
+    qc::ChannelState* state;        // [numChannels]: the programme so far, carried on the device
+    qc::PairState*  pairState;      // [numPairs]
+    const uint32_t* pairs;          // [numPairs][2]: the channels of every pair
+    qc::Stretch<uint32_t>* tileStretch;     // scratch [numChannels][tileCap]: the tiles' summaries
+    double*         leafSums;       // scratch [2 numChannels + numPairs][leafCap]: the leaves' sums of x and x^2 per channel, x_a x_b per pair
+    float*          tileEdge;       // scratch [numChannels][tileCap][4]: min, max of a tile's lead and trail piece of the overview
+    float*          out;            // [numChannels][outCount][2]: the buckets this set completes
+    uint64_t        p0;             // programme frames in front of the set
+    uint32_t        q0, count, blockSize, numChannels, numPairs, numTiles, tileCap, leafCap, outCount;
+    qc::Spec        spec;
+};
+hipError_t launch_qc(hipStream_t s, const QcArgs& a);
+uint64_t qc_launches();             // kernels launched by this process so far
 // ---- delivery-rate conversion (resample.hip): behind a launch set's last level, in front of the pack kernel and the meter, resample.h ----
 struct ResampleArgs {
     const float*    src;            // the set's output, [block][numChannels][blockSize]: validIn frames at the engine's rate

@@ -21,10 +21,12 @@ def _reader(path):
 
 
 def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, target_lufs: float = -14.0, ceiling_dbtp: float = -1.0,
-               fmt: str = "s24", block_size: int = 512, oversample: int = 1, noise_shape=None, verify_input: bool = False, **limiter) -> Dict[str, Any]:
+               fmt: str = "s24", block_size: int = 512, oversample: int = 1, noise_shape=None, verify_input: bool = False, qc=None, **limiter) -> Dict[str, Any]:
     """``in_path`` -> ``out_path`` (format ``fmt`` — 's16', 's24', 'f32', or 'flac16' / 'flac24' for a FLAC file encoded on the GPU —
     the input's rate and channel count) at ``target_lufs`` integrated loudness under a
     true-peak ceiling of ``ceiling_dbtp``. ``limiter``: further limiter parameters (``lookahead_ms``, ``release_ms``, ``link``).
+    ``qc``: an inspector spec (``Runtime.qc``; None: off) — the second pass is inspected on the GPU and the read-out of the file it wrote
+    comes back under ``'qc'`` (``elementary_amd.qc.report`` / ``findings`` derive the figures and the verdicts).
     Returns ``{'input_lufs', 'input_true_peak_dbtp', 'output_lufs', 'output_true_peak_dbtp', 'gain_db', 'max_reduction_db',
     'limited_frames', 'over', 'nonfinite'}``. Where the limiter worked the output is quieter than the target by what it took away; the
     output's metered true peak may exceed the ceiling slightly (``OfflineRenderer.initialize``). An input that passes no loudness
@@ -100,10 +102,12 @@ def master_wav(engine_factory: Callable[[float, int], Any], in_path, out_path, t
     if not np.isfinite(measured["integrated_lufs"]):
         raise ValueError("the input passes no loudness gate: no gain brings it to a target")
     gain_db = float(target_lufs) - float(measured["integrated_lufs"])
-    second = renderer(limiter=dict(params, gain_db=gain_db), noise_shape=shape)
+    second = renderer(limiter=dict(params, gain_db=gain_db), noise_shape=shape, **({} if qc is None else {"qc": dict(qc)}))
     stats = second.process_wav(str(in_path), str(out_path), fmt)
     lim = second.limiter()
     shaped = {"saturated": int(np.sum(second.noise_shape()["saturated"]))} if shape else {}
+    if qc is not None:        # the inspector's report of the file the second pass wrote (elementary_amd.qc.report derives the figures)
+        verdicts = dict(verdicts, qc=stats["qc"])
     return {**shaped, **verdicts, "input_lufs": float(measured["integrated_lufs"]), "input_true_peak_dbtp": float(measured["true_peak_dbtp"]),
             "output_lufs": float(stats["integrated_lufs"]), "output_true_peak_dbtp": float(stats["true_peak_dbtp"]), "gain_db": gain_db,
             "max_reduction_db": float(lim["max_reduction_db"]), "max_reduction": float(np.max(lim["max_reduction"], initial=0.0)),

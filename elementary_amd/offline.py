@@ -28,7 +28,7 @@ class OfflineRenderer:
                    block_size: int = 512, virtual_file_system: Optional[Dict[str, np.ndarray]] = None,
                    event_history_blocks: int = 0, capture_history_blocks: int = 0, loudness_meter: bool = False,
                    output_sample_rate: Optional[float] = None, limiter=None, input_sample_rate: Optional[float] = None, noise_shape=None,
-                   spectrum: Optional[Dict[str, Any]] = None) -> None:
+                   spectrum: Optional[Dict[str, Any]] = None, qc: Optional[Dict[str, Any]] = None) -> None:
         """``event_history_blocks`` (no counterpart in the reference; 0 = off): engine option of the same name — `scope` and `fft`
         nodes keep a device ring long enough for a relay window of that many blocks, so ``process`` still renders launch sets of
         that size with such a listener attached (engines without ``set_option`` relay after every block anyway).
@@ -143,6 +143,19 @@ class OfflineRenderer:
             except RuntimeError as e:
                 raise ValueError(f"this engine refuses the spectrum spec (size {params['size']}, hop {params.get('hop')})") from e
         self._spectrum_parts = []
+        # ``qc`` (likewise; None: off): the inspector's spec (``Runtime.qc``: silence_level, clip_level, clip_run, dropout_frames, bucket,
+        # pairs, skip, limit) — everything ``process`` (in engine calls of many blocks), ``process_pcm``, ``process_pcm_io``,
+        # ``process_flac`` and the file wrappers deliver is inspected on the GPU; read with ``qc()``. Not covered: the device-resident
+        # ``process_blocks``, and ``process`` block by block outside the host-block path.
+        self._qc = None if qc is None else dict(qc)
+        self._qc_overview = []
+        if self._qc is not None:
+            if not hasattr(self._rt, "qc") or not hasattr(self._rt, "qc_read"):
+                raise RuntimeError("this engine has no inspector (Runtime.qc)")
+            try:
+                self._rt.qc(self._qc)
+            except RuntimeError as e:
+                raise ValueError(f"this engine refuses the qc spec {self._qc}") from e
         self._time = 0
         self._lanes: Dict[int, list] = {}
         for k, v in (virtual_file_system or {}).items():
@@ -499,6 +512,7 @@ class OfflineRenderer:
         paths = self._stream_paths(path, S)
         bs = self.block_size
         total, skip, keep = self._file_span(num_frames)
+        self._qc_window(skip, keep)
         chunk = max(bs, (int(chunk_frames) // bs) * bs)
         cursor = [0]
 
@@ -645,12 +659,43 @@ class OfflineRenderer:
         """A new programme for the loudness meter: time 0, zero filter state, no peaks."""
         self._rt.loudness_reset()
 
+    def qc(self) -> Dict[str, Any]:
+        """What the inspector (``initialize(qc={...})``) has found since the renderer was made, ``qc_reset()`` or the last file wrapper
+        began: ``Runtime.qc_read`` with ``overview`` holding every complete bucket of the programme so far (the buckets of earlier reads
+        in front). ``elementary_amd.qc.report`` and ``findings`` derive the figures and the verdicts."""
+        if getattr(self, "_qc", None) is None:
+            raise RuntimeError("the inspector is off: initialize(qc={...})")
+        got = self._rt.qc_read()
+        if got["first_bucket"] == 0:
+            self._qc_overview = []             # (a new programme began since the last read)
+        self._qc_overview.append(got["overview"])
+        if len(self._qc_overview) > 1 and all(p.shape[0] == got["overview"].shape[0] for p in self._qc_overview):
+            got["overview"] = np.concatenate(self._qc_overview, axis=1)
+        self._qc_overview = [got["overview"]]
+        got["first_bucket"] = 0
+        return got
+
+    def qc_reset(self) -> None:
+        """A new programme for the inspector; what it had found is dropped."""
+        if getattr(self, "_qc", None) is None:
+            raise RuntimeError("the inspector is off: initialize(qc={...})")
+        self._rt.qc_reset()
+        self._qc_overview = []
+
+    def _qc_window(self, skip: int, keep: int) -> None:
+        """A file wrapper begins: a new programme whose window is the frames the file holds, not the latencies in front of them."""
+        if getattr(self, "_qc", None) is not None and keep > 0:
+            self._rt.qc(dict(self._qc, skip=int(skip), limit=int(keep)))
+            self._qc_overview = []
+
     def _with_loudness(self, stats):
         if self._loudness and stats is not None:
             got = self.loudness()
             stats = dict(stats, integrated_lufs=got["integrated_lufs"], true_peak_dbtp=got["true_peak_dbtp"])
         if getattr(self, "_limiter", False) and stats is not None:
             stats = dict(stats, limiter_max_reduction_db=self.limiter()["max_reduction_db"])
+        if getattr(self, "_qc", None) is not None and stats is not None:
+            stats = dict(stats, qc=self.qc())
         return stats
 
     def write_wav(self, path, inputs: Sequence[np.ndarray], num_frames: int, fmt="s16", channels_per_stream: Optional[int] = None,
@@ -675,6 +720,7 @@ class OfflineRenderer:
             raise ValueError(f"{S} streams need {S} paths")
         bs = self.block_size
         total, skip, keep = self._file_span(num_frames)
+        self._qc_window(skip, keep)
         chunk = max(bs, (int(chunk_frames) // bs) * bs)
         writers = [WavWriter(p, fmt if isinstance(fmt, str) else {1: "s16", 2: "s24", 3: "f32"}[int(fmt)], G, self.output_sample_rate) for p in paths]
         stats = None
@@ -825,6 +871,7 @@ class OfflineRenderer:
                 total, skip, keep = self._file_span(int(num_frames) if num_frames is not None else max([r.frames for r in readers], default=0))
             else:
                 total, skip, keep = self._file_span(max(r.frames for r in readers), input_frames=True)
+            self._qc_window(skip, keep)
             chunk = max(bs, (int(chunk_frames) // bs) * bs)
             in_fmt = readers[0].fmt if readers else "s16"
             verify = bool(verify_input) and bool(readers) and _is_flac(in_fmt)

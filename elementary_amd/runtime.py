@@ -146,6 +146,21 @@ def load_library() -> C.CDLL:
         lib.elemhip_spectrum_host.restype = C.c_int
         lib.elemhip_spectrum_launches.argtypes = []
         lib.elemhip_spectrum_launches.restype = C.c_uint64
+        _qsp, _qcp = C.POINTER(_QcSpec), C.POINTER(_QcChannel)
+        lib.elemhip_qc_set.argtypes = [C.c_void_p, _qsp]
+        lib.elemhip_qc_set.restype = C.c_int
+        lib.elemhip_qc_read.argtypes = [C.c_void_p, C.POINTER(_QcInfo), _qcp, C.c_size_t, _dp, C.c_size_t]
+        lib.elemhip_qc_read.restype = C.c_int
+        lib.elemhip_qc_overview.argtypes = [C.c_void_p, _fp, C.c_size_t]
+        lib.elemhip_qc_overview.restype = C.c_int
+        lib.elemhip_qc_reset.argtypes = [C.c_void_p]
+        lib.elemhip_qc_reset.restype = C.c_int
+        lib.elemhip_qc_state_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        lib.elemhip_qc_state_bytes.restype = C.c_size_t
+        lib.elemhip_qc_host.argtypes = [_qsp, _fp, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint64, _u8p, _qcp, _dp, _fp]
+        lib.elemhip_qc_host.restype = C.c_int
+        lib.elemhip_qc_launches.argtypes = []
+        lib.elemhip_qc_launches.restype = C.c_uint64
         _app = C.POINTER(_AutomationPoint)
         lib.elemhip_automation_set.argtypes = [C.c_void_p, C.c_uint32, _app, C.c_size_t]
         lib.elemhip_automation_set.restype = C.c_int
@@ -424,6 +439,131 @@ def spectrum_host(x, size: int, hop: int, window="hann", bands=None, center: boo
     frames = np.concatenate(parts, axis=1)
     del keep
     return frames, sums, (None if flush else {"tail": tail, "sums": sums, "delivered": n0 + n, "emitted": j1})
+
+
+class _QcSpec(C.Structure):
+    _fields_ = [("silence_level", C.c_float), ("clip_level", C.c_float), ("clip_run", C.c_uint32), ("dropout_frames", C.c_uint32),
+                ("bucket", C.c_uint32), ("num_pairs", C.c_uint32), ("pairs", C.POINTER(C.c_uint32)), ("skip", C.c_uint64), ("limit", C.c_uint64)]
+
+
+class _QcInfo(C.Structure):
+    _fields_ = [("channels", C.c_uint32), ("pairs", C.c_uint32), ("bucket", C.c_uint32), ("reserved", C.c_uint32), ("frames", C.c_uint64),
+                ("delivered", C.c_uint64), ("first_bucket", C.c_uint64), ("queued", C.c_uint64)]
+
+
+class _QcRuns(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("longest", C.c_uint64), ("longest_at", C.c_uint64), ("first_at", C.c_uint64)]
+
+
+class _QcChannel(C.Structure):
+    _fields_ = [("frames", C.c_uint64), ("nonfinite", C.c_uint64), ("quiet_frames", C.c_uint64), ("clipped_frames", C.c_uint64),
+                ("peak_at", C.c_uint64), ("head_silence", C.c_uint64), ("tail_silence", C.c_uint64), ("dropouts", _QcRuns),
+                ("clip_events", _QcRuns), ("sum", C.c_double), ("sum_sq", C.c_double), ("min", C.c_float), ("max", C.c_float),
+                ("bucket_min", C.c_float), ("bucket_max", C.c_float), ("bucket_frames", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+QC_DEFAULTS = {"silence_level": 0.0, "clip_level": 1.0, "clip_run": 3, "dropout_frames": 64, "bucket": 0, "pairs": (), "skip": 0, "limit": 0}
+
+
+def _qc_spec(params: Dict[str, Any]):
+    """``(spec, keep)``: the C struct of an inspector spec (``QC_DEFAULTS`` under the caller's keys) and the array it points into."""
+    import numpy as np
+    unknown = set(params) - set(QC_DEFAULTS)
+    if unknown:
+        raise ValueError(f"qc: unknown keys {sorted(unknown)}; known: {sorted(QC_DEFAULTS)}")
+    p = dict(QC_DEFAULTS, **params)
+    pairs = np.ascontiguousarray(np.array(list(p["pairs"]), dtype=np.int64).reshape(-1, 2))
+    if pairs.size and (pairs.min() < 0 or pairs.max() > 0xFFFFFFFF):
+        raise ValueError("qc: pairs are (a, b) channel indices")
+    flat = np.ascontiguousarray(pairs.astype(np.uint32).reshape(-1)) if pairs.size else np.zeros(2, dtype=np.uint32)
+    for key, top in (("clip_run", 0xFFFFFFFF), ("dropout_frames", 0xFFFFFFFF), ("bucket", 0xFFFFFFFF), ("skip", 2 ** 64 - 1), ("limit", 2 ** 64 - 1)):
+        if not 0 <= int(p[key]) <= top:
+            raise ValueError(f"qc: {key} {p[key]} is no unsigned integer")
+    spec = _QcSpec()
+    spec.silence_level, spec.clip_level = float(p["silence_level"]), float(p["clip_level"])
+    spec.clip_run, spec.dropout_frames, spec.bucket = int(p["clip_run"]), int(p["dropout_frames"]), int(p["bucket"])
+    spec.num_pairs = int(pairs.shape[0])
+    spec.pairs = flat.ctypes.data_as(C.POINTER(C.c_uint32))
+    spec.skip, spec.limit = int(p["skip"]), int(p["limit"])
+    return spec, [flat]
+
+
+def _qc_signed(v: int) -> int:
+    return -1 if v == 0xFFFFFFFFFFFFFFFF else int(v)
+
+
+def _qc_channels(recs, pair_list, pair_sums) -> Dict[str, Any]:
+    """The records of a read as arrays: one entry per channel under every key; "none" positions are -1."""
+    import numpy as np
+    n = len(recs)
+    u = lambda f: np.array([f(r) for r in recs], dtype=np.int64).reshape(n)
+    runs = lambda name: {k: u(lambda r, k=k: _qc_signed(getattr(getattr(r, name), k)) if k.endswith("_at") else int(getattr(getattr(r, name), k)))
+                         for k in ("count", "longest", "longest_at", "first_at")}
+    out = {k: u(lambda r, k=k: int(getattr(r, k))) for k in ("frames", "nonfinite", "quiet_frames", "clipped_frames", "head_silence", "tail_silence")}
+    out["peak_at"] = u(lambda r: _qc_signed(r.peak_at))
+    out["min"] = np.array([r.min for r in recs], dtype=np.float32)
+    out["max"] = np.array([r.max for r in recs], dtype=np.float32)
+    out["sum"] = np.array([r.sum for r in recs], dtype=np.float64)
+    out["sum_sq"] = np.array([r.sum_sq for r in recs], dtype=np.float64)
+    out["dropouts"], out["clip_events"] = runs("dropouts"), runs("clip_events")
+    out["open_bucket"] = {"min": np.array([r.bucket_min for r in recs], dtype=np.float32), "max": np.array([r.bucket_max for r in recs], dtype=np.float32),
+                          "frames": u(lambda r: int(r.bucket_frames))}
+    out["pairs"] = [tuple(int(v) for v in ab) for ab in pair_list]
+    out["sum_xy"] = np.array(pair_sums, dtype=np.float64).reshape(len(out["pairs"]))
+    out["channels"] = n
+    return out
+
+
+def qc_launches() -> int:
+    """``elemhip_qc_launches``: inspector kernels this process has launched so far (an engine whose inspector is off adds none)."""
+    return int(load_library().elemhip_qc_launches())
+
+
+def qc_host(x, state=None, **params):
+    """``elemhip_qc_host``: the scalar twin of the inspector's kernels, pure host arithmetic — ``x`` float32 ``[channels, frames]`` behind
+    the programme ``state`` describes (None: a programme's start) -> ``(read, state)``: ``read`` as ``Runtime.qc_read`` returns it (with
+    ``overview`` float32 ``[channels, buckets, 2]``, every complete bucket of the programme so far), and the state to hand on. ``skip``
+    and ``limit`` are applied here as the engine applies them."""
+    import numpy as np
+    lib = load_library()
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    if a.ndim == 1:
+        a = a[None, :]
+    ch = a.shape[0]
+    spec, keep = _qc_spec(params)
+    npairs, bucket = int(spec.num_pairs), int(spec.bucket)
+    if state is None:
+        state = {"bytes": np.zeros(max(int(lib.elemhip_qc_state_bytes(ch, npairs)), 1), dtype=np.uint8), "frames": 0, "delivered": 0,
+                 "overview": np.zeros((ch, 0, 2), dtype=np.float32)}
+    else:
+        state = {"bytes": np.array(state["bytes"], dtype=np.uint8), "frames": int(state["frames"]), "delivered": int(state["delivered"]),
+                 "overview": state["overview"]}
+    skip, limit, p0 = int(spec.skip), int(spec.limit), state["frames"]
+    lead = min(max(skip - state["delivered"], 0), a.shape[1])
+    take = a.shape[1] - lead
+    if limit:
+        take = min(take, max(limit - p0, 0))
+    part = np.ascontiguousarray(a[:, lead:lead + take])
+    buckets = ((p0 + take) // bucket - p0 // bucket) if bucket else 0
+    recs = (_QcChannel * max(ch, 1))()
+    sums = np.zeros(max(npairs, 1), dtype=np.float64)
+    ov = np.zeros((ch, buckets, 2), dtype=np.float32)
+    ovbuf = np.zeros(max(ov.size, 1), dtype=np.float32)
+    rc = lib.elemhip_qc_host(C.byref(spec), part.ctypes.data_as(C.POINTER(C.c_float)) if take else None, ch, max(take, 1), take, p0,
+                             state["bytes"].ctypes.data_as(C.POINTER(C.c_uint8)), recs, sums.ctypes.data_as(C.POINTER(C.c_double)),
+                             ovbuf.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        err = ElemHipError(f"elemhip_qc_host failed: {describe(rc)} (code {rc})")
+        err.code = rc
+        raise err
+    ov[...] = ovbuf[:ov.size].reshape(ov.shape)
+    pair_list = np.ctypeslib.as_array(spec.pairs, shape=(2 * max(npairs, 1),))[:2 * npairs].reshape(-1, 2).copy()
+    del keep
+    state["frames"], state["delivered"] = p0 + take, state["delivered"] + a.shape[1]
+    state["overview"] = np.concatenate([state["overview"], ov], axis=1)
+    read = _qc_channels([recs[c] for c in range(ch)], pair_list, sums[:npairs])
+    read["overview"], read["bucket"], read["delivered"] = state["overview"], bucket, state["delivered"]
+    return read, state
 
 
 class FlacMd5:
@@ -1294,6 +1434,47 @@ class Runtime(CRuntime):
     def spectrum_reset(self) -> None:
         """``elemhip_spectrum_reset``: a new programme; what was pending is dropped."""
         self._spectrum_check("elemhip_spectrum_reset", self._lib.elemhip_spectrum_reset(self._h))
+
+    def qc(self, spec: Optional[Dict[str, Any]] = None, **params) -> None:
+        """``elemhip_qc_set``: inspect what the host-buffer render calls deliver — ``silence_level`` (0), ``clip_level`` (1.0),
+        ``clip_run`` (3), ``dropout_frames`` (64), ``bucket`` (0: no overview), ``pairs`` (``(a, b)`` channel pairs, at most 128),
+        ``skip`` and ``limit`` (the programme's window in delivered frames; 0: unbounded), as a dict or as keywords. ``qc(None)``
+        without keywords turns the inspector off (the default). Starts a new programme. A spec the engine refuses raises with
+        ``.code`` 6 and changes nothing."""
+        if spec is None and not params:
+            return self._spectrum_check("elemhip_qc_set", self._lib.elemhip_qc_set(self._h, None))
+        cs, keep = _qc_spec(dict(spec or {}, **params))
+        rc = self._lib.elemhip_qc_set(self._h, C.byref(cs))
+        if rc == 0:
+            self._qc_pairs = keep[0][:2 * int(cs.num_pairs)].reshape(-1, 2).copy()
+        del keep
+        self._spectrum_check("elemhip_qc_set", rc)
+
+    def qc_read(self, overview: bool = True) -> Dict[str, Any]:
+        """``elemhip_qc_read`` (and ``elemhip_qc_overview``): the cumulative results so far, one array entry per channel — ``frames``,
+        ``nonfinite``, ``quiet_frames``, ``clipped_frames``, ``min``, ``max``, ``peak_at``, ``head_silence``, ``tail_silence``, ``sum``,
+        ``sum_sq``, ``dropouts`` and ``clip_events`` (dicts of ``count``, ``longest``, ``longest_at``, ``first_at``; -1: none),
+        ``open_bucket`` (``min``, ``max``, ``frames``), ``pairs`` and ``sum_xy``; with ``overview`` the complete buckets emitted since
+        the last such read, float32 ``[channels, n, 2]`` from bucket ``first_bucket`` on (drained). The programme is not disturbed.
+        Raises on an engine whose inspector is off."""
+        import numpy as np
+        info = _QcInfo()
+        self._spectrum_check("elemhip_qc_read", self._lib.elemhip_qc_read(self._h, C.byref(info), None, 0, None, 0))
+        ch, npairs, queued = int(info.channels), int(info.pairs), int(info.queued)
+        recs = (_QcChannel * max(ch, 1))()
+        sums = np.zeros(max(npairs, 1), dtype=np.float64)
+        self._spectrum_check("elemhip_qc_read", self._lib.elemhip_qc_read(self._h, C.byref(info), recs, ch, sums.ctypes.data_as(C.POINTER(C.c_double)), npairs))
+        out = _qc_channels([recs[c] for c in range(ch)], getattr(self, "_qc_pairs", np.zeros((0, 2), dtype=np.uint32))[:npairs], sums[:npairs])
+        out.update({"bucket": int(info.bucket), "delivered": int(info.delivered), "programme_frames": int(info.frames), "first_bucket": int(info.first_bucket)})
+        if overview:
+            buf = np.zeros(max(ch * queued * 2, 1), dtype=np.float32)
+            self._spectrum_check("elemhip_qc_overview", self._lib.elemhip_qc_overview(self._h, buf.ctypes.data_as(C.POINTER(C.c_float)), buf.size))
+            out["overview"] = buf[:ch * queued * 2].reshape(ch, queued, 2).copy()
+        return out
+
+    def qc_reset(self) -> None:
+        """``elemhip_qc_reset``: a new programme; buckets nobody read are dropped."""
+        self._spectrum_check("elemhip_qc_reset", self._lib.elemhip_qc_reset(self._h))
 
     def automation(self, channel: int, points) -> None:
         """``elemhip_automation_set``: binds a lane — ``(frame, value[, "hold" | "linear"])`` rows sorted by frame

@@ -340,6 +340,46 @@ int elemhip_automation_host(const elemhip_automation_point* points, size_t count
 int64_t elemhip_automation_segment_at(const elemhip_automation_point* points, size_t count, int64_t t);
 uint64_t elemhip_automation_launches(void);
 
+/* EXTENSION (no counterpart in the reference): the inspector — technical QC of what elemhip_process_blocks_host / _pcm / _pcm_io / _flac
+ * deliver, on the GPU (elementary_amd/csrc/qc.hip; the definitions: qc.h) — behind the delivery-rate converter and the limiter, on the
+ * floats the loudness meter reads, before any quantisation. It only reads. The programme is the frames those calls delivered since the
+ * spec was set or elemhip_qc_reset, less the first `skip`, cut after `limit` frames (0: unbounded); a call of another channel count, and
+ * a call that fails, start a new one. A non-finite sample is counted and then inspected as 0.0. A frame is quiet iff |x| <= silence_level
+ * (>= 0; 0: exact digital silence) and clipped iff |x| >= clip_level (> 0). A clip event is a maximal run of at least clip_run (1 ..
+ * 65535) clipped frames, the run at frame 0 and the open run at the end included; a dropout is a maximal run of at least dropout_frames
+ * (1 .. 2^31 - 1) quiet frames with a non-quiet frame before AND after it. Of equally long runs the earliest is the longest; "none" is
+ * UINT64_MAX. bucket (0: off; 16 .. 1048576): a min / max overview per `bucket` programme frames. pairs: up to 128 (a, b), a != b, whose
+ * sum of x_a x_b is kept; a call that delivers fewer channels than a pair names is refused with code 6. The float64 sums are added in an
+ * order that depends on programme frame indices alone (leaves of 64 frames in frame order, the leaves in leaf order): the same bits
+ * however the render is cut into calls and launch sets; everything else is exact. Code 6, and nothing changes, for a spec out of these
+ * ranges (dry handles validate too); a NULL spec, the default, turns the inspector off: no launch, no buffer, not one byte differs.
+ *   elemhip_qc_read      info: channels, pairs, bucket, programme frames, frames delivered, and `queued` complete buckets waiting from
+ *                        index first_bucket on. channels (NULL, or channelCapacity records): the cumulative results per channel, the
+ *                        open bucket's partial min, max and frame count with them. pairSums (NULL, or pairCapacity doubles). The
+ *                        programme is not disturbed.
+ *   elemhip_qc_overview  drains the queued buckets: out [channel][queued][2] (min, max), `capacity` floats (code 6 when too few)
+ *   elemhip_qc_reset     a new programme; buckets nobody read are dropped
+ *   elemhip_qc_host      the scalar twin on plain arrays, no handle: `planar` [channels] rows `stride` floats apart, `frames` frames
+ *                        behind programme frame p0; state: elemhip_qc_state_bytes(channels, num_pairs) bytes in-out (initialised here
+ *                        where p0 = 0); reports [channels], pairSums [num_pairs] (either may be NULL); overview [channels][k][2] for the
+ *                        k = (p0 + frames) / bucket - p0 / bucket buckets the frames complete. skip and limit are the caller's there.
+ *   elemhip_qc_launches  inspector kernels this process has launched so far */
+typedef struct elemhip_qc_spec { float silence_level, clip_level; uint32_t clip_run, dropout_frames, bucket, num_pairs; const uint32_t* pairs;
+                                 uint64_t skip, limit; } elemhip_qc_spec;
+typedef struct elemhip_qc_info { uint32_t channels, pairs, bucket, reserved; uint64_t frames, delivered, first_bucket, queued; } elemhip_qc_info;
+typedef struct elemhip_qc_runs { uint64_t count, longest, longest_at, first_at; } elemhip_qc_runs;
+typedef struct elemhip_qc_channel { uint64_t frames, nonfinite, quiet_frames, clipped_frames, peak_at, head_silence, tail_silence;
+                                    elemhip_qc_runs dropouts, clip_events; double sum, sum_sq;
+                                    float min, max, bucket_min, bucket_max; uint32_t bucket_frames, reserved; } elemhip_qc_channel;
+int elemhip_qc_set(elemhip_t*, const elemhip_qc_spec* spec);
+int elemhip_qc_read(elemhip_t*, elemhip_qc_info* info, elemhip_qc_channel* channels, size_t channelCapacity, double* pairSums, size_t pairCapacity);
+int elemhip_qc_overview(elemhip_t*, float* out, size_t capacity);
+int elemhip_qc_reset(elemhip_t*);
+size_t elemhip_qc_state_bytes(uint32_t channels, uint32_t num_pairs);
+int elemhip_qc_host(const elemhip_qc_spec* spec, const float* planar, uint32_t channels, size_t stride, size_t frames, uint64_t p0, uint8_t* state,
+                    elemhip_qc_channel* reports, double* pairSums, float* overview);
+uint64_t elemhip_qc_launches(void);
+
 /* EXTENSION (no counterpart in the reference): the same render delivered as FLAC, encoded on the GPU in the pack kernel's place
  * (elementary_amd/csrc/flac_encode.hip; the arithmetic and the decision rules: flac_encode.h) — behind the delivery-rate converter and
  * the limiter, next to the meter. RFC 9639 "subset" streams of a fixed block size (option "flac_frame": 256, 512, 1024, 2048 or 4096,

@@ -174,6 +174,14 @@ public:
     }
     int spectrumFlush() { return elemhip_spectrum_flush(h); }
     int spectrumReset() { return elemhip_spectrum_reset(h); }
+    // EXTENSION: the inspector — silence, dropouts, clip events, DC, energy, pair sums and a min / max overview of what the host-buffer
+    // render calls deliver (null spec: off)
+    int qcSet(const elemhip_qc_spec* spec) { return elemhip_qc_set(h, spec); }
+    int qcRead(elemhip_qc_info* info, elemhip_qc_channel* channels, size_t channelCapacity, double* pairSums, size_t pairCapacity) {
+        return elemhip_qc_read(h, info, channels, channelCapacity, pairSums, pairCapacity);
+    }
+    int qcOverview(float* out, size_t capacity) { return elemhip_qc_overview(h, out, capacity); }
+    int qcReset() { return elemhip_qc_reset(h); }
     // EXTENSION: breakpoint automation lanes on engine input channels of the host-buffer render calls, expanded on the GPU (count 0: cleared)
     int automationSet(uint32_t channel, const elemhip_automation_point* points, size_t count) { return elemhip_automation_set(h, channel, points, count); }
     int automationRead(uint32_t channel, elemhip_automation_info* info, elemhip_automation_point* points, size_t capacity) {
